@@ -17,12 +17,14 @@ SAM-ViT-B + SigLIP-B/16-384 + MaskAdapterPooling, batch 32 triplets per GPU, bf1
 random-init weights, 100k-row bf16 gallery at every N (51 MB: fits one GPU). For N>1 (configs[2]) the gallery is
 row-sharded over the ranks, queries are all-gathered over RCCL, each rank scores all queries against its shard, the packed
 per-shard top-k lists go to rank 0 in one gather and are merged on the host. A "step" = one such pass; inputs resident in HBM.
-The timed steps replay the forward as one captured hipGraph (`config.launch`; --graph 0 = eager launches); the GEMM events behind
-`roofline` then come from an eager re-run of the same steps right after the timed region (`roofline.events`).
-One JSON line on rank 0. `roofline` is for the dominant kernel (the bf16 MFMA GEMM); `cpu_baseline` is the CPU oracle
-timed on the host cores on a bounded sample (3 triplets) at N=1; `recall` (outside the timed region) compares the benchmarked
-pipeline's top-k over ALL 32 queries with the exact-fp32 HIP mode's (and the fp32 CPU oracle's on the 3 CPU triplets) against the
-same gallery with one planted positive per query; inputs are per-sample texture tiles so that the 32 queries are not collinear.
+The timed steps replay the forward as one captured hipGraph (`config.launch`; --graph 0 = eager launches).
+One JSON line on rank 0. A plain run sets up, warms up, times --steps steps and prints the headline line (`value`, `ms_per_step`, ...);
+--dump-outputs DIR also writes what the last timed step returned (dump_outputs). Everything else needs --full: `roofline` for the
+dominant kernel (the bf16 MFMA GEMM; under graph replay its GEMM events come from an eager re-run of the same steps right after the
+timed region, `roofline.events`), `clock` (shader clock sampled over the timed region), `cpu_baseline` (the CPU oracle timed on the
+host cores on a bounded sample, 3 triplets, at N=1) and `recall` (outside the timed region: the benchmarked pipeline's top-k over ALL
+32 queries against the exact-fp32 HIP mode's, and the fp32 CPU oracle's on the 3 CPU triplets, on the same gallery with one planted
+positive per query; inputs are per-sample texture tiles so that the 32 queries are not collinear).
 """
 from __future__ import annotations
 
@@ -59,7 +61,12 @@ def parse(argv=None):
                     "event (ForwardPipeline(stagger=True): measured equal at 4 hardware queues, slower at 8 / 16, profiles/r05_pipeline_queues.jsonl); 0 (default): "
                     "one graph per slot")
     ap.add_argument("--hw-queues", type=int, default=0, help="set GPU_MAX_HW_QUEUES before HIP initialises (0: leave the environment / runtime default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: roofline of the dominant "
+                    "kernel (eager re-run of the steps under --graph 1, HIP events around every GEMM inside the timed region under --graph 0), "
+                    "shader clock, CPU baseline and recall legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and recall legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all; see dump_outputs)")
     ap.add_argument("--overlap", type=int, default=-1, choices=[-1, 0, 1, 2], help="2: as 1, with the two SigLIP towers as two chains on two streams (round 4); 1: support branch (SigLIP towers, adapter, fusion) beside the SAM encoder: a parallel branch of "
                     "the captured graph / a second HIP stream in eager mode (+3-4 %% end to end). -1 (default): on under --graph 1, off in eager mode, "
                     "where concurrent kernels would inflate the per-launch GEMM events")
@@ -85,6 +92,8 @@ def parse(argv=None):
     ap.add_argument("--launch-check", action="store_true", help="rehearse the launch path only: every rank joins the process group (gloo: no GPU "
                     "needed), all-reduces its rank and rank 0 prints one JSON line; nothing is benchmarked (tests/test_cpu_host.py)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     given = {a.split("=")[0] for a in (argv if argv is not None else sys.argv[1:]) if a.startswith("--")}
     if args.config:
         args.config_text = BASELINE_CONFIGS[args.config]
@@ -287,6 +296,65 @@ def stated_cpu_baseline():
         return None
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, fwd, topk):
+    """--dump-outputs: what the last timed step returned, one DIR/<name>.npy each: the merged top-k lists (what a caller of the step
+    receives; indices as float64, exact below 2^53) and this rank's forward outputs (final masks, query image embeddings, the query
+    features the search consumed) in float32. Each file holds at most DUMP_BYTES / 5: a larger output keeps a fixed seeded sample of
+    its rows (leading two axes flattened, rows in ascending order), the same rows in every run with the same arguments."""
+    import numpy as np
+    import torch
+    masks, emb, feat = fwd
+    arrays = {"topk_scores": topk[0].float(), "topk_indices": topk[1].double(), "query_features": feat[:, 0].float(),
+              "final_masks": masks.float(), "image_embeddings": emb.float()}
+    cap = DUMP_BYTES // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.numel() * a.element_size() > cap:
+            rows = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = cap // (rows.shape[1] * a.element_size())
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = rows[pick.to(rows.device)]
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
+def roofline(args, prof, T, dt, world, B, events_from):
+    """--full: the dominant kernel (the MFMA GEMM) from the HIP events recorded around every cor_gemm launch on the launch stream."""
+    import torch
+    gemm_ms = sum(p[0].elapsed_time(p[1]) for p in prof if p[3] == T)
+    gemm_flops = sum(p[2] for p in prof if p[3] == T)
+    gemm_bytes = sum(p[4] for p in prof if p[3] == T)
+    n_launch = sum(1 for p in prof if p[3] == T)
+    # HBM traffic of that kernel cannot be read live: it comes from the committed rocprofv3 --pmc passes of THIS command
+    # (tools/pmc_traffic.py -> profiles/*pmc_traffic.json; FETCH_SIZE doubled per the gfx950 correction), per launch.
+    traffic, traffic_note, traffic_ratio = None, "no PMC pass for this build", None
+    lps = n_launch // max(args.steps, 1)
+    if os.path.exists(PMC_TRAFFIC_FILE) and args.dtype == "bf16" and world == 1 and B == 32 and args.sam == "sam_base":
+        try:
+            tj = json.load(open(PMC_TRAFFIC_FILE))
+            rel = os.path.relpath(PMC_TRAFFIC_FILE, ROOT)
+            if tj.get("gemm_source_id") != gemm_source_id():
+                traffic_note = f"{rel} was measured on other GEMM sources ({tj.get('gemm_source_id')}): not quoted"
+            elif tj.get("launches_per_step") != lps:
+                # same denominators or nothing (VERDICT r4: a 215-launch PMC pass was quoted beside a 200-launch step)
+                traffic_note = f"{rel} counts {tj.get('launches_per_step')} GEMM launches per step, this run has {lps}: not quoted"
+            else:
+                traffic = tj["bytes_per_step"] / lps
+                traffic_ratio = tj["bytes_per_step"] / (gemm_bytes / max(args.steps, 1))
+                traffic_note = f"{rel} (same GEMM sources {tj['gemm_source_id']}, same {lps} launches per step; bytes per step {tj['bytes_per_step']:.4g})"
+        except Exception as e:                           # noqa: BLE001
+            traffic_note = f"unreadable PMC file: {e}"
+    peak = 2500.0 if T == torch.bfloat16 else 157.3
+    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    return {"bound": "mfma", "kernel": ("cor_gemm, bf16 operands: gemm_pp<*> (persistent 256x256 ping-pong, >= 140 tiles) + gemm_tile<bf16,*,128,128> (the rest)" if args.dtype == "bf16" else "cor_gemm, fp32 operands: gemm_tile<float,float,128,128> on v_mfma_f32_32x32x2_f32"), "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+            "frac": achieved / peak, "traffic": traffic, "traffic_unit": "bytes per launch (PMC, offline pass)", "traffic_source": traffic_note,
+            "traffic_over_algorithmic": traffic_ratio,
+            "algorithmic_bytes_per_launch": gemm_bytes / max(n_launch, 1), "launches_per_step": n_launch // max(args.steps, 1),
+            "avg_launch_us": gemm_ms * 1e3 / max(n_launch, 1), "gemm_share_of_step": gemm_ms / (dt * 1e3), "events": events_from}
+
+
 def main():
     args = parse()
     plan, detail = launch_plan(args.gpus, os.environ)
@@ -382,15 +450,19 @@ def main():
         # defer: the lists' device-to-host copy is enqueued behind an event; the host merge of step i runs after step i + 1 is enqueued
         return retrieval.distributed_search(out[2][:, 0], shard, args.topk, max_local=B, timing=timing, always_collective=rehearse, defer=True)   # (awaited at once under --defer 0)
 
+    last = {}                                            # the forward outputs of the latest step (--dump-outputs)
+
     def step():
         if pipe is not None:                             # every slot's input buffers hold the synthetic batch (resident inputs)
-            return pipe.submit(None, then=search)[1]
+            last["forward"], res, _ = pipe.submit(None, then=search)
+            return res
         if h2d is not None:
             b = h2d.take()
             h2d.stage(host_batch)                      # next step's inputs start crossing PCIe now, on the copy stream
         else:
             b = batch
-        return search(graphed(**b) if graphed is not None else model(**b, multimask_output=mm))
+        last["forward"] = graphed(**b) if graphed is not None else model(**b, multimask_output=mm)
+        return search(last["forward"])
 
     def barrier():
         if multi:
@@ -403,8 +475,8 @@ def main():
     barrier()
     prof = []
     timing = [] if multi else None                       # per-step marks around the two collectives and the shard search
-    clock = utils.ClockSampler(dev).start()
-    if graphed is None:
+    clock = utils.ClockSampler(dev).start() if args.full else None
+    if graphed is None and args.full:
         ops.GEMM_PROFILE = prof                          # HIP events around every cor_gemm, on the launch stream
     t0 = time.perf_counter()
     pend = collections.deque()
@@ -420,12 +492,14 @@ def main():
         done_at.append(time.perf_counter() - t0)
     barrier()
     dt = time.perf_counter() - t0
-    clk = clock.stop()
+    clk = clock.stop() if clock is not None else None
     ops.GEMM_PROFILE = None
     coll = retrieval.resolve_timing(timing) if timing else None
     timing = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["forward"], out)
     events_from = "the timed region"
-    if graphed is not None:
+    if graphed is not None and args.full:
         # the same kernels, launched eagerly so that events can bracket every GEMM (not part of `value`)
         events_from = "an eager re-run of the same steps right after the timed region (no per-launch events inside a replayed hipGraph on ROCm)"
         ops.GEMM_PROFILE = prof
@@ -439,33 +513,6 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # dominant kernel: the MFMA GEMM. HIP events were recorded around every launch on the launch stream.
-    gemm_ms = sum(p[0].elapsed_time(p[1]) for p in prof if p[3] == T)
-    gemm_flops = sum(p[2] for p in prof if p[3] == T)
-    gemm_bytes = sum(p[4] for p in prof if p[3] == T)
-    n_launch = sum(1 for p in prof if p[3] == T)
-    # HBM traffic of that kernel cannot be read live: it comes from the committed rocprofv3 --pmc passes of THIS command
-    # (tools/pmc_traffic.py -> profiles/*pmc_traffic.json; FETCH_SIZE doubled per the gfx950 correction), per launch.
-    traffic, traffic_note, traffic_ratio = None, "no PMC pass for this build", None
-    lps = n_launch // max(args.steps, 1)
-    if os.path.exists(PMC_TRAFFIC_FILE) and args.dtype == "bf16" and world == 1 and B == 32 and args.sam == "sam_base":
-        try:
-            tj = json.load(open(PMC_TRAFFIC_FILE))
-            rel = os.path.relpath(PMC_TRAFFIC_FILE, ROOT)
-            if tj.get("gemm_source_id") != gemm_source_id():
-                traffic_note = f"{rel} was measured on other GEMM sources ({tj.get('gemm_source_id')}): not quoted"
-            elif tj.get("launches_per_step") != lps:
-                # same denominators or nothing (a 215-launch PMC pass was quoted beside a 200-launch step)
-                traffic_note = f"{rel} counts {tj.get('launches_per_step')} GEMM launches per step, this run has {lps}: not quoted"
-            else:
-                traffic = tj["bytes_per_step"] / lps
-                traffic_ratio = tj["bytes_per_step"] / (gemm_bytes / max(args.steps, 1))
-                traffic_note = f"{rel} (same GEMM sources {tj['gemm_source_id']}, same {lps} launches per step; bytes per step {tj['bytes_per_step']:.4g})"
-        except Exception as e:                           # noqa: BLE001
-            traffic_note = f"unreadable PMC file: {e}"
-    peak = 2500.0 if T == torch.bfloat16 else 157.3
-    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-
     if rank == 0:
         res = {
             "metric": "query triplets/sec (forward + similarity + top-k)", "value": world * B * args.steps / dt, "unit": "triplets/s",
@@ -475,11 +522,6 @@ def main():
                                    + f"{args.sam}+{args.siglip}+MaskAdapterPooling, {B} triplets/GPU, {Gtot}-row {args.gallery_dtype} gallery"
                                    + (f" sharded {world} ways ({'RCCL' if args.backend == 'nccl' else 'gloo REHEARSAL on one GPU:'} all-gather of queries, host top-k merge)" if world > 1 else ""),
                        "global_batch": world * B, "gallery_rows": Gtot, "topk": args.topk, "parallelism": f"dp{world}+gallery-shard{world}"},
-            "roofline": {"bound": "mfma", "kernel": ("cor_gemm, bf16 operands: gemm_pp<*> (persistent 256x256 ping-pong, >= 140 tiles) + gemm_tile<bf16,*,128,128> (the rest)" if args.dtype == "bf16" else "cor_gemm, fp32 operands: gemm_tile<float,float,128,128> on v_mfma_f32_32x32x2_f32"), "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak, "traffic": traffic, "traffic_unit": "bytes per launch (PMC, offline pass)", "traffic_source": traffic_note,
-                         "traffic_over_algorithmic": traffic_ratio,
-                         "algorithmic_bytes_per_launch": gemm_bytes / max(n_launch, 1), "launches_per_step": n_launch // max(args.steps, 1),
-                         "avg_launch_us": gemm_ms * 1e3 / max(n_launch, 1), "gemm_share_of_step": gemm_ms / (dt * 1e3)},
         }
         res["config"]["launch"] = launch_mode
         res["config"]["multimask_output"] = mm
@@ -489,14 +531,15 @@ def main():
         res["config"]["gallery_dtype"] = args.gallery_dtype
         res["config"]["results"] = ("every step's top-k lists reach the host inside the timed region; step i's lists are awaited and merged after step i + 1 "
                                     "is enqueued (pinned copy behind an event)") if args.defer else "each step's top-k lists are awaited before the next step is enqueued"
-        res["roofline"]["events"] = events_from
-        res["clock"] = clk
+        if args.full:
+            res["roofline"] = roofline(args, prof, T, dt, world, B, events_from)
+            res["clock"] = clk
         res["step_done_ms"] = [round(t * 1e3, 2) for t in done_at]   # with two forwards in flight the first result arrives late, then one per steady-state interval
         if multi:
             res["rccl"] = dict(backend=dist.get_backend(), world_size=dist.get_world_size(), **coll,
                                note="rank 0's means over the timed steps; device events on the launch stream under nccl (= RCCL), host clocks under the "
                                     "gloo rehearsal (whose collectives work on host copies); collective_ms = query all-gather + packed-list gather")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:                                         # a failure in the checker legs must not discard the measured throughput
                 with torch.no_grad():                    # the benchmarked pipeline's features of this batch (graph replay when --graph 1)
                     feat_fast = (graphed(**batch) if graphed is not None else model(**batch, multimask_output=mm))[2][:, 0].clone()

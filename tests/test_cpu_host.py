@@ -222,6 +222,10 @@ def test_bench_launch_plan_and_command():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[cmd.index("--master-port") + 1] == "29511"
     assert cmd[-5:] == [os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "5"]
     assert b.parse(["--gpus", "2", "--backend", "gloo"]).backend == "gloo" and b.parse([]).multimask == 1
+    assert b.parse([]).full is False and b.parse([]).dump_outputs is None            # a plain run: the headline figures only
+    assert b.parse(["--full", "--dump-outputs", "d"]).full is True and b.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])                                                    # every result line times at least one step
     src = open(os.path.join(ROOT, "bench.py")).read()
     head = src[:src.index("def main()")]
     assert not re.search(r"^(import|from)\s+(torch|cor_amd)", head, flags=re.M), "the launching parent must not import torch / cor_amd at module level"

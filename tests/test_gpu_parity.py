@@ -1996,10 +1996,10 @@ def test_distributed_search_on_a_one_rank_rccl_group():
 
 
 def test_bench_contract_smoke(tmp_path):
-    """bench.py end to end at a reduced batch (the driver runs the default line at round end): ONE JSON line with the contract's keys,
-    `roofline` and `cpu_baseline` objects, recall over all queries with the planted positives found by both pipelines."""
+    """bench.py --full end to end at a reduced batch: ONE JSON line with the contract's keys, `roofline` and `cpu_baseline` objects,
+    recall over all queries with the planted positives found by both pipelines."""
     import subprocess, sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4", "--gallery", "20000", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "4", "--gallery", "20000", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2018,6 +2018,35 @@ def test_bench_contract_smoke(tmp_path):
     assert d["fp32_mode_topk_index_mismatches_vs_cpu_oracle"] == 0 and d["cpu_oracle_recall_at_1"] == 1.0
     assert "clock" in d and d["config"]["multimask_output"] is True and "awaited and merged after step i + 1" in d["config"]["results"]
     assert d["config"]["forwards_in_flight"] == 2 and "capture_pipeline" in d["config"]["launch"] and len(d["step_done_ms"]) == 2   # the default
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the --full records, runs exactly --steps timed steps, and
+    --dump-outputs writes the last step's top-k lists and forward outputs: the dumped lists are BITWISE the chain oracle's top-k of
+    the dumped query features against the bench's seeded bf16 gallery."""
+    import subprocess, sys
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "4", "--gallery", "20000", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and len(d["step_done_ms"]) == 3 and d["value"] > 0 and d["unit"] == "triplets/s" and d["dtype"] == "bf16"
+    assert d["higher_is_better"] is True and abs(d["ms_per_step"] - 4 * 1e3 / d["value"]) < 1e-6 * d["ms_per_step"]
+    assert not {"roofline", "clock", "cpu_baseline", "recall"} & set(d), sorted(d)
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    shapes = dict(topk_scores=(4, 10), topk_indices=(4, 10), query_features=(4, 256), final_masks=(4, 1, 256, 256))
+    assert set(got) == set(shapes) | {"image_embeddings"}
+    for k, s in shapes.items():
+        assert got[k].shape == s and got[k].dtype in (np.float32, np.float64), (k, got[k].shape, got[k].dtype)
+    # 16.8 MB of embeddings exceed one file's share (64 MB / 5): a sample of whole 64x64 maps
+    assert got["image_embeddings"].shape == ((64 << 20) // 5 // (4 * 64 * 64), 64 * 64) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    gen = torch.Generator(device="cpu").manual_seed(1234)                 # bench.py's gallery rows
+    rows = torch.nn.functional.normalize(torch.randn((20000, 256), generator=gen), dim=-1).to(torch.bfloat16).float()
+    rs, ri = oret.similarity_topk_chain(torch.from_numpy(got["query_features"]).to(torch.bfloat16).float(), rows, 10)
+    assert np.array_equal(got["topk_indices"], ri.numpy().astype(np.float64))
+    assert np.array_equal(got["topk_scores"].view(np.int32), rs.numpy().view(np.int32))
 
 
 def test_bench_multi_rank_code_path_on_a_one_rank_rccl_group(tmp_path):

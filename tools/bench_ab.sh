@@ -7,7 +7,7 @@ mkdir -p "$out"
 : > "$out/bench_ab.jsonl"
 for r in $(seq 1 "$rounds"); do
   for v in "$@"; do
-    python bench.py --steps "$steps" --warmup 3 --no-cpu-baseline $v | tail -1 > "$out/line.json"
+    python bench.py --full --steps "$steps" --warmup 3 --no-cpu-baseline $v | tail -1 > "$out/line.json"
     python - "$out/line.json" "$v" >> "$out/bench_ab.jsonl" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
