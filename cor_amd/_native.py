@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COR_AMD_LIB") or os.path.join(_HERE, "csrc", "libcor_amd.so")   # COR_AMD_LIB: another build of the SAME ABI (same-box A/B runs of tools/)
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16, BF16X3 = 0, 1, 2, 3    # BF16X3: x3 split rows (exact-query mode, include/cor_amd.h)
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TANH = 0, 1, 2, 3, 4
 EINVAL, ENOSUPPORT = -1, -2
 TOPK_FORCE_LISTS, TOPK_NO_FALLBACK, TOPK_FORCE_GLOBAL_THRESHOLD, TOPK_WAVE_FINAL = 1, 2, 8, 16
@@ -28,12 +28,14 @@ SIGNATURES = {
     "cor_gemm": [_p, _l, _p, _l, _i, _p, _l, _i, _i, _i, _i, _p, _i, _p, _p, _l, _i, _i, _p],
     "cor_layernorm": [_p, _i, _p, _i, _p, _p, _i, _i, _f, _i, _p],
     "cor_attention": [_p, _l, _l, _p, _l, _l, _p, _l, _l, _i, _p, _l, _l, _i, _i, _i, _i, _i, _i, _f, _p],
+    "cor_attention_f32": [_p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _i, _i, _i, _i, _i, _i, _f, _p],
     "cor_attention_kernel_id": [_i, _i, _i, _i, _i, _i],
     "cor_sam_attention": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p],
     "cor_patchify": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "cor_im2col3x3": [_p, _i, _p, _i, _i, _i, _i, _p],
     "cor_add": [_p, _i, _p, _i, _p, _i, _l, _l, _p],
     "cor_copy_rows": [_p, _l, _i, _p, _l, _i, _i, _i, _p],
+    "cor_split_x3": [_p, _l, _p, _l, _l, _i, _i, _p],
     "cor_tokens_to_nchw": [_p, _i, _p, _i, _i, _i, _p],
     "cor_nchw_to_tokens": [_p, _p, _i, _i, _i, _i, _p],
     "cor_l2norm_rows": [_p, _i, _p, _i, _i, _i, _f, _p],

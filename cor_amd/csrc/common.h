@@ -51,6 +51,33 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, f32x4 v) {
   *(uint2*)p = u;
 }
 
+// ---- x3 split rows (exact-query mode). An fp32 value x travels as hi = bf16_rne(x), lo = bf16_rne(x - hi) (x - hi is exact in
+// fp32). A split ROW of C logical values is bf16 [lo(0..C) | hi(0..C) | hi(0..C)] with segment stride `seg` (>= C): as the A operand of
+// a bf16 GEMM over 3K against weight rows [hi | lo | hi] it computes A_lo.W_hi + A_hi.W_lo + A_hi.W_hi in one fp32 accumulator.
+struct x3_t {};   // dtype tag of COR_BF16X3 outputs
+__device__ __forceinline__ void split_bf16(float x, bf16_t& hi, bf16_t& lo) {
+#pragma clang fp contract(off)   // x - hi on the ROUNDED x: never fused with the multiply / add that produced x
+  hi = f2bf(x);
+  lo = f2bf(x - bf2f(hi));
+}
+// four consecutive logical values at column c of a split row (c, seg and the row base 4-element aligned: 8-B stores)
+__device__ __forceinline__ void st4_x3(bf16_t* row, long seg, int c, f32x4 v) {
+  bf16_t h[4], l[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) split_bf16(v[e], h[e], l[e]);
+  uint2 uh, ul;
+  uh.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16); uh.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+  ul.x = (uint32_t)l[0] | ((uint32_t)l[1] << 16); ul.y = (uint32_t)l[2] | ((uint32_t)l[3] << 16);
+  *(uint2*)(row + c) = ul;
+  *(uint2*)(row + seg + c) = uh;
+  *(uint2*)(row + 2 * seg + c) = uh;
+}
+// row-major store of 4 values at (row, c) of a [rows, C] output in TO; for x3_t the output is bf16 [rows, 3C] split rows
+template <typename TO> __device__ __forceinline__ void st4_row(TO* y, long row, int C, int c, f32x4 v) { st4<TO>(y + row * C + c, v); }
+template <> __device__ __forceinline__ void st4_row<x3_t>(x3_t* y, long row, int C, int c, f32x4 v) {
+  st4_x3((bf16_t*)y + row * 3L * C, C, c, v);
+}
+
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 round-off level), ~15 VALU ops instead of libm's ~40:
 // the GELU epilogue of the MLP GEMMs runs once per output element.
 __device__ __forceinline__ float erf_as(float x) {

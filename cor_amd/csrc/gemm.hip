@@ -1014,6 +1014,14 @@ extern "C" int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab
 #endif
   }
   if (residual && ldr < N) return COR_EINVAL;
+  if (ab_dtype == COR_BF16X3) {
+    // x3 split operands (exact-query mode): A rows [lo | hi | hi], W rows [hi | lo | hi], each segment K wide. The K loop of the bf16
+    // kernels runs over the three segments in order into one fp32 accumulator: A_lo.W_hi + A_hi.W_lo + A_hi.W_hi. Same tiles, same
+    // epilogues, same dispatch (which depends on M, N and the 3K bytes of a row), so results stay deterministic and batch-invariant.
+    if (lda < 3L * K || ldw < 3L * K || K > (1 << 29)) return COR_EINVAL;
+    ab_dtype = COR_BF16;
+    K *= 3;
+  }
   hipStream_t s = (hipStream_t)stream;
   if (ab_dtype == COR_F32 && c_dtype == COR_F32)
     return launch_gemm<float, float>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);

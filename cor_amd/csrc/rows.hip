@@ -32,7 +32,6 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TI* x, TO* y, cons
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / C + eps);
-  TO* yr = y + (long)row * C;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     const int j = lane + 64 * i;
@@ -41,7 +40,7 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const TI* x, TO* y, cons
       f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = apply_act((v[i][e] - mean) * rstd * wv[e] + bv[e], act);
-      st4<TO>(yr + 4 * j, o);
+      st4_row<TO>(y, row, C, 4 * j, o);
     }
   }
 }
@@ -74,7 +73,6 @@ __global__ void __launch_bounds__(256) layernorm_half_kernel(const TI* x, TO* y,
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; q += d * d; }
   const float rstd = 1.0f / sqrtf(hsum(q) / C + eps);
-  TO* yr = y + (long)row * C;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int j = lane + 32 * i;
@@ -82,7 +80,7 @@ __global__ void __launch_bounds__(256) layernorm_half_kernel(const TI* x, TO* y,
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = apply_act((v[i][e] - mean) * rstd * wv[e] + bv[e], act);
-    st4<TO>(yr + 4 * j, o);
+    st4_row<TO>(y, row, C, 4 * j, o);
   }
 }
 
@@ -207,6 +205,28 @@ __global__ void __launch_bounds__(256) copy_rows_kernel(const TI* in, long ld_in
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const long r = i / C; const int c = (int)(i - r * C);
     st<TO>(out + r * ld_out + c, ld<TI>(in + r * ld_in + c));
+  }
+}
+
+// ---------------------------------------------------------------- fp32 -> x3 split rows (exact-query mode, see st4_x3)
+// 4 values per thread: one 16-B load, three 8-B stores (lo, hi, hi); HBM-bound.
+__global__ void __launch_bounds__(256) split_x3_4_kernel(const float* in, long ld_in, bf16_t* out, long ld_out, long seg, int rows, int C) {
+  const int c4 = C >> 2;
+  const long n = (long)rows * c4;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / c4; const int c = (int)(i - r * c4) * 4;
+    st4_x3(out + r * ld_out, seg, c, *(const f32x4*)(in + r * ld_in + c));
+  }
+}
+
+__global__ void __launch_bounds__(256) split_x3_kernel(const float* in, long ld_in, bf16_t* out, long ld_out, long seg, int rows, int C) {
+  const long n = (long)rows * C;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / C; const int c = (int)(i - r * C);
+    bf16_t hi, lo;
+    split_bf16(in[r * ld_in + c], hi, lo);
+    bf16_t* o = out + r * ld_out + c;
+    o[0] = lo; o[seg] = hi; o[2 * seg] = hi;
   }
 }
 
@@ -355,6 +375,7 @@ extern "C" int cor_layernorm(const void* x, int x_dtype, void* y, int y_dtype, c
   const int rev = (act & COR_ORDER_REVERSE) ? 1 : 0;   // rows from the last to the first (see COR_ORDER_REVERSE)
   act &= ~COR_ORDER_REVERSE;
 #define CALL(TI, TO) return launch_ln<TI, TO>(x, y, w, b, rows, C, eps, act, rev, (hipStream_t)stream)
+  if (x_dtype == COR_F32 && y_dtype == COR_BF16X3) { CALL(float, x3_t); }   // split rows [lo | hi | hi] for an x3 GEMM
   DISPATCH2(x_dtype, y_dtype, CALL)
 #undef CALL
 }
@@ -387,6 +408,20 @@ extern "C" int cor_add(const void* a, int a_dtype, const void* b, int b_dtype, v
     default: return COR_ENOSUPPORT;
   }
 #undef ADD3
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int cor_split_x3(const float* in, long ld_in, void* out, long ld_out, long seg, int rows, int C, void* stream) {
+  if (!in || !out || rows <= 0 || C <= 0 || ld_in < C || seg < C || ld_out < 2 * seg + C) return COR_EINVAL;
+  const bool vec4 = (C & 3) == 0 && (ld_in & 3) == 0 && (ld_out & 3) == 0 && (seg & 3) == 0 && ((uintptr_t)in & 15) == 0 &&
+                    ((uintptr_t)out & 7) == 0;
+  if (vec4)
+    hipLaunchKernelGGL(split_x3_4_kernel, dim3(grid_for((long)rows * (C >> 2))), dim3(256), 0, (hipStream_t)stream, in, ld_in,
+                       (bf16_t*)out, ld_out, seg, rows, C);
+  else
+    hipLaunchKernelGGL(split_x3_kernel, dim3(grid_for((long)rows * C)), dim3(256), 0, (hipStream_t)stream, in, ld_in, (bf16_t*)out,
+                       ld_out, seg, rows, C);
   COR_CHECK_LAUNCH();
   return 0;
 }

@@ -4,7 +4,10 @@ Every arithmetic step is a launch of a hand-written gfx950 kernel through cor_am
 include/cor_amd.h). torch only owns memory. Data layout in HBM:
   * activations are token-major [tokens, C] (channels-last) everywhere; NCHW exists only at the API boundary;
   * the residual stream is fp32; GEMM operands are `T` (torch.float32 = exact mode, torch.bfloat16 = fast mode);
-  * weights are packed once per (state_dict version, T): [N,K] row-major in T, biases / LN / rel-pos in fp32.
+  * weights are packed once per (state_dict version, T, Q): [N,K] row-major in T, biases / LN / rel-pos in fp32;
+  * Q is the support branch's operand mode: T itself, or ops.X3 in exact-query mode (query_dtype fp32 beside a bf16 SAM): the
+    branch's GEMM operands are x3 split rows (bf16 [rows, 3K], see ops.X3), its attention the exact f32-MFMA kernel, everything
+    else fp32. The SAM encoder and decoder never see Q.
 The schedule follows lib/sam_with_sup_branch.py:57-104 of the reference; each function cites what it replaces.
 """
 from __future__ import annotations
@@ -15,7 +18,7 @@ import torch
 
 from . import _native as nat
 from . import ops
-from .ops import ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TANH
+from .ops import ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TANH, X3
 
 F32 = torch.float32
 
@@ -40,7 +43,8 @@ class _Packer:
         self.W[k] = (self.sd[k] if t is None else t).detach().to(F32).contiguous()
 
     def mat(self, k, t=None):
-        self.W[k] = (self.sd[k] if t is None else t).detach().to(self.T).contiguous()
+        t = self.sd[k] if t is None else t
+        self.W[k] = ops.split_weight_x3(t) if self.T == X3 else t.detach().to(self.T).contiguous()
 
     def lin(self, p):
         self.mat(p + "weight")
@@ -185,23 +189,27 @@ def pack_mask_decoder(pk: _Packer, q="mask_decoder."):
         pk.f32(q + "heads.b2", torch.cat([sd[n + "2.bias"].detach() for n in names], 0))
 
 
-def pack(sd: dict, scfg: dict, gcfg: dict, mask_pooling: str, T: torch.dtype) -> dict:
-    """Full-model state_dict -> kernel-ready tensors. One-off, at load / after load_state_dict."""
+def pack(sd: dict, scfg: dict, gcfg: dict, mask_pooling: str, T: torch.dtype, Q=None) -> dict:
+    """Full-model state_dict -> kernel-ready tensors. One-off, at load / after load_state_dict. Q: the support branch's operand
+    mode (None = T); Q = ops.X3 packs the SigLIP towers and the support head as x3 split weights [N, 3K] and nothing else twice."""
     pk = _Packer(sd, T)
+    pkq = pk if Q is None or Q == T else _Packer(sd, Q)
     pack_sam_encoder(pk, scfg)
     pack_prompt_encoder(pk)
-    pack_siglip(pk, gcfg)
-    pack_support_head(pk, mask_pooling)
+    pack_siglip(pkq, gcfg)
+    pack_support_head(pkq, mask_pooling)
     pack_mask_decoder(pk)
+    if pkq is not pk:
+        pk.W.update(pkq.W)
     return pk.W
 
 
 # =====================================================================================================
 # building blocks
 # =====================================================================================================
-def _lin(W, p, a, out_dtype, act=ACT_NONE, residual=None, col_scale=None, out=None, reverse=False):
+def _lin(W, p, a, out_dtype, act=ACT_NONE, residual=None, col_scale=None, out=None, reverse=False, x3=False):
     return ops.gemm(a, W[p + "weight"], out_dtype=out_dtype, bias=W[p + "bias"], act=act, residual=residual,
-                    col_scale=col_scale, out=out, reverse=reverse)
+                    col_scale=col_scale, out=out, reverse=reverse, x3=x3)
 
 
 def _ln(W, p, x, eps, out_dtype, act=ACT_NONE, reverse=False):
@@ -246,28 +254,36 @@ def sam_encoder(W, img, cfg, T, p="image_encoder."):
 
 def _vit_mha(qkv, N, Tn, heads, D, T):
     hd = D // heads
+    if T == X3:                                    # exact-query mode: fp32 qkv -> flash_fwd_f32 -> split rows for the proj GEMM
+        return ops.attention_f32(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], N, heads, Tn, Tn, hd, hd ** -0.5, out_dtype=X3)
     return ops.attention(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], N, heads, Tn, Tn, hd, hd ** -0.5, out_dtype=T)
+
+
+def _qkv_dtype(T):
+    """dtype of a tower's qkv activation: T, or fp32 in exact-query mode (the f32 attention reads fp32 q / k / v)."""
+    return F32 if T == X3 else T
 
 
 def siglip_vision(W, img, g, T, p="support_branch.siglip.model.visual.trunk."):
     """ref: lib/support_model/siglip_openclip.py:30-35 (trunk run ONCE; the MAP-head pass of :26 is dead on the
-    live path). img fp32 [N,3,384,384] -> last hidden states fp32 [N*P, D]."""
+    live path). img fp32 [N,3,384,384] -> last hidden states fp32 [N*P, D]. T: the support branch's mode (T or X3)."""
     N = img.shape[0]
     D, P = g["dim"], (g["image"] // g["patch"]) ** 2
+    x3 = T == X3
     assert img.shape[1:] == (3, g["image"], g["image"]), f"SigLIP input must be [N,3,{g['image']},{g['image']}], got {tuple(img.shape)}"
     cols = ops.patchify(img, g["patch"], W[p + "patch.K"], T)
     x = ops.gemm(cols, W[p + "patch_embed.proj.weight"], out_dtype=F32, bias=W[p + "patch_embed.proj.bias"],
-                 residual=W[p + "pos_embed"], res_row_mod=P)
+                 residual=W[p + "pos_embed"], res_row_mod=P, x3=x3)
     act = _gelu(g.get("v_gelu", g.get("gelu", "erf")))
     for i in range(g["depth"]):
         b = f"{p}blocks.{i}."
         h = _ln(W, b + "norm1.", x, 1e-6, T)
-        qkv = _lin(W, b + "attn.qkv.", h, T)
+        qkv = _lin(W, b + "attn.qkv.", h, _qkv_dtype(T), x3=x3)
         a = _vit_mha(qkv, N, P, g["heads"], D, T)
-        _lin(W, b + "attn.proj.", a, F32, residual=x, out=x)
+        _lin(W, b + "attn.proj.", a, F32, residual=x, out=x, x3=x3)
         h = _ln(W, b + "norm2.", x, 1e-6, T)
-        m = _lin(W, b + "mlp.fc1.", h, T, act=act)
-        _lin(W, b + "mlp.fc2.", m, F32, residual=x, out=x)
+        m = _lin(W, b + "mlp.fc1.", h, T, act=act, x3=x3)
+        _lin(W, b + "mlp.fc2.", m, F32, residual=x, out=x, x3=x3)
     return _ln(W, p + "norm.", x, 1e-6, F32)
 
 
@@ -276,21 +292,22 @@ def siglip_text(W, tokens, g, T, p="support_branch.siglip.model.text."):
     tokens int64 [N,64] -> fp32 [N, D] unit-norm."""
     N, ctx = tokens.shape
     D = g["dim"]
+    x3 = T == X3
     x = ops.embed_tokens(tokens.contiguous(), W[p + "token_embedding.weight"], W[p + "positional_embedding"])
     act = _gelu(g.get("t_gelu", g.get("gelu", "erf")))
     for i in range(g["t_depth"]):
         b = f"{p}transformer.resblocks.{i}."
         h = _ln(W, b + "ln_1.", x, 1e-6, T)
-        qkv = ops.gemm(h, W[b + "attn.in_proj_weight"], out_dtype=T, bias=W[b + "attn.in_proj_bias"])
+        qkv = ops.gemm(h, W[b + "attn.in_proj_weight"], out_dtype=_qkv_dtype(T), bias=W[b + "attn.in_proj_bias"], x3=x3)
         a = _vit_mha(qkv, N, ctx, g["t_heads"], D, T)
-        _lin(W, b + "attn.out_proj.", a, F32, residual=x, out=x)
+        _lin(W, b + "attn.out_proj.", a, F32, residual=x, out=x, x3=x3)
         h = _ln(W, b + "ln_2.", x, 1e-6, T)
-        m = _lin(W, b + "mlp.c_fc.", h, T, act=act)
-        _lin(W, b + "mlp.c_proj.", m, F32, residual=x, out=x)
+        m = _lin(W, b + "mlp.c_fc.", h, T, act=act, x3=x3)
+        _lin(W, b + "mlp.c_proj.", m, F32, residual=x, out=x, x3=x3)
     last = torch.empty((N, D), dtype=F32, device=x.device)
     ops.copy_rows(x, ctx * D, N, D, last, src_offset=(ctx - 1) * D)                       # pool_type 'last'
     last = _ln(W, p + "ln_final.", last, 1e-6, T)
-    feat = _lin(W, p + "text_projection.", last, F32)
+    feat = _lin(W, p + "text_projection.", last, F32, x3=x3)
     return ops.l2norm_rows(feat)
 
 
@@ -298,9 +315,10 @@ def mask_adapter_pooling(W, feat, mask, N, gh, D, T, p="support_branch.mask_pool
     """ref: lib/support_model/mask_adapter.py:52-80 (+ :83-94, :144-179, :210-223).
     feat fp32 tokens [N*P, D] (already ln_channel_first-ed), mask fp32 [N,1,h,w] -> pooled fp32 [N, D]."""
     P = gh * gh
+    x3 = T == X3
     m24 = ops.bilinear(mask, gh, gh) if tuple(mask.shape[-2:]) != (gh, gh) else mask     # :57-58
     c = p + "channel_clip_to_maskadapter."
-    dense = ops.gemm(ops.cast(feat, T), W[c + "conv.weight"], out_dtype=F32, bias=W[c + "conv.bias"])
+    dense = ops.gemm(ops.cast(feat, T), W[c + "conv.weight"], out_dtype=F32, bias=W[c + "conv.bias"], x3=x3)
     dense = _ln(W, c + "norm.", dense, 1e-6, F32, act=ACT_GELU_ERF)                       # :90-93
     g = p + "get_mask_map."
     md = g + "mask_downscaling."
@@ -309,16 +327,16 @@ def mask_adapter_pooling(W, feat, mask, N, gh, D, T, p="support_branch.mask_pool
     c1 = _ln(W, md + "1.", c1.view(-1, c1.shape[-1]), 1e-6, F32, act=ACT_GELU_ERF)
     c2 = ops.conv3x3s2_small(c1, True, W[md + "3.weight"], W[md + "3.bias"], N, W[md + "3.weight"].shape[1], 2 * gh, 2 * gh)
     c2 = _ln(W, md + "4.", c2.view(-1, c2.shape[-1]), 1e-6, T, act=ACT_GELU_ERF)
-    summed = ops.gemm(c2, W[md + "6.weight"], out_dtype=F32, bias=W[md + "6.bias"], residual=dense)   # :159-161
-    y = ops.gemm(ops.cast(summed, T), W[g + "fuse.weight"], out_dtype=F32, bias=W[g + "fuse.bias"])   # :163
+    summed = ops.gemm(c2, W[md + "6.weight"], out_dtype=F32, bias=W[md + "6.bias"], residual=dense, x3=x3)   # :159-161
+    y = ops.gemm(ops.cast(summed, T), W[g + "fuse.weight"], out_dtype=F32, bias=W[g + "fuse.bias"], x3=x3)   # :163
     for i in (1, 2, 3):                                                                   # :210-223
         b = f"{g}cnext{i}."
         dw = ops.dwconv7x7(y, W[b + "dwconv.weight"], W[b + "dwconv.bias"], N, gh, gh)
         h = _ln(W, b + "norm.", dw, 1e-6, T)
-        h = _lin(W, b + "pwconv1.", h, T, act=ACT_GELU_ERF)
-        _lin(W, b + "pwconv2.", h, F32, residual=y, col_scale=W[b + "gamma"], out=y)
+        h = _lin(W, b + "pwconv1.", h, T, act=ACT_GELU_ERF, x3=x3)
+        _lin(W, b + "pwconv2.", h, F32, residual=y, col_scale=W[b + "gamma"], out=y, x3=x3)
     h = _ln(W, g + "norm.", y, 1e-6, T)
-    maps = ops.gemm(h, W[g + "final.weight"], out_dtype=F32, bias=W[g + "final.bias"])    # [N*P, 8]
+    maps = ops.gemm(h, W[g + "final.weight"], out_dtype=F32, bias=W[g + "final.bias"], x3=x3)    # [N*P, 8]
     M = maps.shape[1]
     # :62-67 interpolate to the same size is the identity (scale 1 => lambda 0)
     return ops.adapter_pool(maps, feat, N, P, M, D), maps
@@ -338,19 +356,25 @@ def support_head(W, vis_tokens, text_feat, mask, g, mask_pooling, T, p="support_
         pooled = ops.masked_pool(feat, m, N, gh * gh, D)
     img = _ln(W, p + "ln_channel_last.", pooled, 1e-6, F32)
     f = p + "cir_fuse."
-    raw = torch.empty((N, 2 * D), dtype=T, device=img.device)
-    ops.copy_rows(img, D, N, D, raw, ld_out=2 * D)
-    ops.copy_rows(text_feat, D, N, D, raw[:, D:], ld_out=2 * D)
+    x3 = T == X3
+    if x3:                                                                                 # split rows of cat(img, text): K segments 2D wide
+        raw = torch.empty((N, 6 * D), dtype=torch.bfloat16, device=img.device)
+        ops.split_x3(img, raw, seg=2 * D)
+        ops.split_x3(text_feat, raw[:, D:], seg=2 * D)
+    else:
+        raw = torch.empty((N, 2 * D), dtype=T, device=img.device)
+        ops.copy_rows(img, D, N, D, raw, ld_out=2 * D)
+        ops.copy_rows(text_feat, D, N, D, raw[:, D:], ld_out=2 * D)
 
     def gate(name, x):
-        h = _lin(W, f"{f}{name}.0.", x, T, act=ACT_RELU)
-        return _lin(W, f"{f}{name}.3.", h, F32, act=ACT_SIGMOID)
+        h = _lin(W, f"{f}{name}.0.", x, T, act=ACT_RELU, x3=x3)
+        return _lin(W, f"{f}{name}.3.", h, F32, act=ACT_SIGMOID, x3=x3)
 
     cat = ops.fuse_gate(img, text_feat, gate("atten_Image", raw), gate("atten_Text", raw))
     dyn = gate("dynamic_scalar", ops.cast(cat, T))
     fused = ops.fuse_mix(cat, dyn)
-    h = _lin(W, p + "dim_proj.0.", ops.cast(fused, T), T, act=ACT_GELU_ERF)               # Dropout(0.8): identity in eval
-    h = _lin(W, p + "dim_proj.3.", h, F32, act=ACT_GELU_ERF)
+    h = _lin(W, p + "dim_proj.0.", ops.cast(fused, T), T, act=ACT_GELU_ERF, x3=x3)        # Dropout(0.8): identity in eval
+    h = _lin(W, p + "dim_proj.3.", h, F32, act=ACT_GELU_ERF, x3=x3)
     return ops.l2norm_rows(h)
 
 
@@ -449,7 +473,8 @@ def _side_stream(device, which=0):
 
 def forward_support(W, gcfg, mask_pooling, T, support_image_inputs, change_text_inputs, support_mask_inputs, two_chains=True, text_stream=None):
     """The support branch on the CURRENT stream (ref: lib/sam_with_sup_branch.py:79-80 -> lib/support_branch.py:56-87): SigLIP towers,
-    mask adapter, fusion, dim_proj -> comb_support_feat fp32 [B,256]. two_chains: the text tower on one more stream (the towers are
+    mask adapter, fusion, dim_proj -> comb_support_feat fp32 [B,256]. T: the BRANCH's mode (torch.float32 / torch.bfloat16, or ops.X3
+    in exact-query mode), independent of the SAM encoder's. two_chains: the text tower on one more stream (the towers are
     independent: each is a CHAIN of ~110 small dependent kernels, and a chain advances only where the encoder's persistent GEMMs
     leave CUs free, 2-3 kernels per big-kernel boundary). text_stream: a stream the CALLER has already forked from the stream its own
     stream was forked from (a fork of a forked stream inside a graph capture crashed hipGraph's capture_end on ROCm 7.0: forks stay flat)."""
@@ -493,20 +518,22 @@ def forward_decode(W, scfg, T, emb_tokens, feat, multimask_output=True, return_a
 
 
 def forward(W, scfg, gcfg, mask_pooling, T, query_image_inputs, support_image_inputs, change_text_inputs, support_mask_inputs,
-            multimask_output=True, return_aux=False, overlap_branches=None):
-    """ref: lib/sam_with_sup_branch.py:57-104. overlap_branches (None = module default OVERLAP_BRANCHES): per-call choice."""
+            multimask_output=True, return_aux=False, overlap_branches=None, Q=None):
+    """ref: lib/sam_with_sup_branch.py:57-104. overlap_branches (None = module default OVERLAP_BRANCHES): per-call choice.
+    Q: the support branch's mode (None = T; ops.X3 = exact-query mode beside a bf16 SAM); W must have been packed for (T, Q)."""
     emb_tokens, feat = forward_encode(W, scfg, gcfg, mask_pooling, T, query_image_inputs, support_image_inputs, change_text_inputs,
-                                      support_mask_inputs, overlap_branches)
+                                      support_mask_inputs, overlap_branches, Q)
     return forward_decode(W, scfg, T, emb_tokens, feat, multimask_output, return_aux)
 
 
 def forward_encode(W, scfg, gcfg, mask_pooling, T, query_image_inputs, support_image_inputs, change_text_inputs, support_mask_inputs,
-                   overlap_branches=None):
+                   overlap_branches=None, Q=None):
     """Everything up to the mask decoder (ref: lib/sam_with_sup_branch.py:76-80): SAM encoder tokens fp32 [B*4096,256] and
     comb_support_feat fp32 [B,256], both complete on the current stream on return. forward() = forward_encode + forward_decode; the
     two halves are captured as separate graphs by ForwardPipeline(stagger=True)."""
     if overlap_branches is None:
         overlap_branches = OVERLAP_BRANCHES
+    Q = T if Q is None else Q
     q_img = query_image_inputs.to(F32).contiguous()
     if overlap_branches:
         # The support branch (SigLIP towers + ~100 tiny adapter/fusion kernels) is independent of the SAM encoder until
@@ -519,12 +546,12 @@ def forward_encode(W, scfg, gcfg, mask_pooling, T, query_image_inputs, support_i
             side2 = _side_stream(q_img.device, 1)
             side2.wait_stream(main)
         with torch.cuda.stream(side):
-            feat = forward_support(W, gcfg, mask_pooling, T, support_image_inputs, change_text_inputs, support_mask_inputs,
+            feat = forward_support(W, gcfg, mask_pooling, Q, support_image_inputs, change_text_inputs, support_mask_inputs,
                                    two_chains=side2 is not None, text_stream=side2)
         emb_tokens = sam_encoder(W, q_img, scfg, T)                                        # :76
         main.wait_stream(side)
         feat.record_stream(main)
     else:
         emb_tokens = sam_encoder(W, q_img, scfg, T)
-        feat = forward_support(W, gcfg, mask_pooling, T, support_image_inputs, change_text_inputs, support_mask_inputs, two_chains=False)
+        feat = forward_support(W, gcfg, mask_pooling, Q, support_image_inputs, change_text_inputs, support_mask_inputs, two_chains=False)
     return emb_tokens, feat

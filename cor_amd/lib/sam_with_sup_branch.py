@@ -29,12 +29,39 @@ class CirSegModelWithQuerySupportFeat(nn.Module):
         self.register_buffer("pixel_mean", torch.Tensor(pixel_mean).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.Tensor(pixel_std).view(-1, 1, 1), False)
         self.compute_dtype = torch.float32      # torch.float32: exact-fp32 MFMA ; torch.bfloat16: fast mode
+        self.query_dtype = None                 # None: the support branch follows the compute dtype; torch.float32: exact-query mode
         self._packed = {}
         self._fp_tensors = None                 # _fingerprint(): tensor list of the last module walk, dropped by _apply / load_state_dict
 
     @property
     def device(self) -> Any:
         return self.pixel_mean.device
+
+    @property
+    def query_dtype(self):
+        """Accuracy of the support branch, which alone computes comb_support_feat (the retrieval query).
+        None (default): the branch follows the resolved compute dtype, as the rest of the model does.
+        torch.float32: EXACT-QUERY MODE. The SigLIP towers, mask adapter, fusion and dim_proj run fp32-accurate while the SAM encoder
+        and mask decoder keep the resolved compute dtype (bf16 included, under torch.autocast too). Beside a bf16 SAM the branch's
+        GEMMs run as x3 split products on the bf16 matrix cores (A_lo.W_hi + A_hi.W_lo + A_hi.W_hi, one fp32 accumulator) and its
+        attention on the f32 matrix cores; with compute_dtype float32 it is the fp32 path itself, bit for bit."""
+        return self._query_dtype
+
+    @query_dtype.setter
+    def query_dtype(self, value):
+        if value is not None and not (isinstance(value, torch.dtype) and value == torch.float32):
+            raise ValueError(f"query_dtype must be None or torch.float32, got {value!r}")
+        self._query_dtype = value
+
+    def _query_mode(self, T):
+        """The support branch's operand mode for SAM dtype T: T itself, torch.float32, or engine.X3 (fp32-accurate x3 split products)."""
+        if self._query_dtype is None or T == torch.float32:
+            return T
+        return engine.X3
+
+    @staticmethod
+    def _pack_key(T, Q):
+        return T if Q == T else (T, Q)
 
     # ---- packed-weight cache: rebuilt after anything that can change parameters or their device
     def invalidate_packed(self):
@@ -67,15 +94,19 @@ class CirSegModelWithQuerySupportFeat(nn.Module):
         return hash(tuple((t._version, t.data_ptr()) for t in self._fp_tensors))
 
     def packed(self, T=None):
+        """Kernel-ready weights for SAM dtype T (None: resolved) and the support-branch mode that query_dtype gives with it; cached
+        under T (query_dtype None, or a branch mode equal to T) or (T, branch mode): one pack per combination, SAM weights packed once."""
         T = T or self._resolve_dtype()
+        Q = self._query_mode(T)
+        key = self._pack_key(T, Q)
         fp = self._fingerprint()
         if self._packed.get("fp") != fp:
             self._packed = {"fp": fp}
-        if T not in self._packed:
+        if key not in self._packed:
             with torch.no_grad():
-                self._packed[T] = engine.pack(self.state_dict(), self.image_encoder.cfg, self.support_branch.siglip.cfg,
-                                              self.support_branch.mask_pooling_name, T)
-        return self._packed[T]
+                self._packed[key] = engine.pack(self.state_dict(), self.image_encoder.cfg, self.support_branch.siglip.cfg,
+                                                self.support_branch.mask_pooling_name, T, Q)
+        return self._packed[key]
 
     @torch.no_grad()
     def forward(self, query_image_inputs, support_image_inputs, change_text_inputs, support_mask_inputs, multimask_output=True):
@@ -88,7 +119,7 @@ class CirSegModelWithQuerySupportFeat(nn.Module):
         with torch.cuda.device(self.device):       # the kernels launch on the CURRENT device: make it the model's
             return engine.forward(self.packed(T), self.image_encoder.cfg, self.support_branch.siglip.cfg,
                                   self.support_branch.mask_pooling_name, T, query_image_inputs, support_image_inputs,
-                                  change_text_inputs, support_mask_inputs, multimask_output)
+                                  change_text_inputs, support_mask_inputs, multimask_output, Q=self._query_mode(T))
 
     @torch.no_grad()
     def capture(self, query_image_inputs, support_image_inputs, change_text_inputs, support_mask_inputs, multimask_output=True,
@@ -136,7 +167,7 @@ class CirSegModelWithQuerySupportFeat(nn.Module):
         with torch.cuda.device(self.device):
             return engine.forward(self.packed(T), self.image_encoder.cfg, self.support_branch.siglip.cfg,
                                   self.support_branch.mask_pooling_name, T, query_image_inputs, support_image_inputs,
-                                  change_text_inputs, support_mask_inputs, multimask_output, return_aux=True)
+                                  change_text_inputs, support_mask_inputs, multimask_output, return_aux=True, Q=self._query_mode(T))
 
 
 class GraphedForward:
@@ -148,6 +179,8 @@ class GraphedForward:
         self.model, self.multimask_output, self.calls, self.split = model, multimask_output, 0, split
         dev = model.device
         self.T = model._resolve_dtype()
+        self.Q = model._query_mode(self.T)                  # the mode is fixed at capture time, like the dtype
+        self.key = model._pack_key(self.T, self.Q)
         self.fingerprint = model._fingerprint()
         with torch.cuda.device(dev):
             self.static_in = [t.detach().to(dev).clone() for t in inputs]
@@ -160,19 +193,19 @@ class GraphedForward:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                  # warm-up off the capture: per-device kernel attributes, allocator pools
                 for _ in range(max(1, warmup)):
-                    engine.forward(*args, *self.static_in, multimask_output, overlap_branches=overlap_branches)
+                    engine.forward(*args, *self.static_in, multimask_output, overlap_branches=overlap_branches, Q=self.Q)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             # thread_local: API calls of OTHER host threads (e.g. a process group's watchdog) must not invalidate the capture
             if not split:
                 with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    self.static_out = engine.forward(*args, *self.static_in, multimask_output, overlap_branches=overlap_branches)
+                    self.static_out = engine.forward(*args, *self.static_in, multimask_output, overlap_branches=overlap_branches, Q=self.Q)
             else:
                 # two graphs over ONE memory pool: [SAM encoder || support branch] and [mask decoder + output layout]; the pipeline
                 # orders the next slot's first graph behind this slot's first graph (ForwardPipeline, stagger)
                 with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    self._mid = engine.forward_encode(*args, *self.static_in, overlap_branches=overlap_branches)
+                    self._mid = engine.forward_encode(*args, *self.static_in, overlap_branches=overlap_branches, Q=self.Q)
                 self.graph_dec = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_dec, pool=self.graph.pool(), capture_error_mode="thread_local"):
                     self.static_out = engine.forward_decode(W, model.image_encoder.cfg, self.T, *self._mid, multimask_output)
@@ -181,11 +214,11 @@ class GraphedForward:
         self.calls += 1
         if self.model._fingerprint(walk=self.calls % 64 == 1) != self.fingerprint:
             raise RuntimeError("cor_amd: the model's parameters changed (or moved) since capture(): capture again")
-        if self.model._packed.get(self.T) is not self.W:
+        if self.model._packed.get(self.key) is not self.W:
             # the cache was dropped (_apply / load_state_dict / invalidate_packed) or rebuilt: the next eager forward would pack NEW
             # tensors while this graph keeps reading the old ones - same parameters today, silently stale after the next update
-            if self.model._packed.get(self.T) is None and self.model._packed.get("fp") in (None, self.fingerprint):
-                self.model._packed = {"fp": self.fingerprint, **{k: v for k, v in self.model._packed.items() if k != "fp"}, self.T: self.W}
+            if self.model._packed.get(self.key) is None and self.model._packed.get("fp") in (None, self.fingerprint):
+                self.model._packed = {"fp": self.fingerprint, **{k: v for k, v in self.model._packed.items() if k != "fp"}, self.key: self.W}
             else:
                 raise RuntimeError("cor_amd: the model's packed weights were rebuilt since capture(): capture again")
         for dst, src in zip(self.static_in, inputs):

@@ -13,6 +13,12 @@ from ._native import ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TAN
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
+# Operand mode of the support branch in exact-query mode (model.query_dtype = torch.float32 beside a bf16 SAM): "x3 split rows". A
+# logical fp32 [rows, C] activation is carried as a bf16 tensor [rows, 3C] = [lo | hi | hi] (hi = bf16(x), lo = bf16(x - hi)), a
+# weight [N, K] as bf16 [N, 3K] = [hi | lo | hi]; their bf16 GEMM over 3K is A_lo.W_hi + A_hi.W_lo + A_hi.W_hi (include/cor_amd.h).
+# Functions below that take an `out_dtype` accept X3 where noted.
+X3 = "bf16x3"
+
 # bench.py sets this to a list to time every GEMM launch with HIP events recorded on the launch stream:
 # entries are (start_event, end_event, algorithmic_flops, ab_dtype, algorithmic_bytes). None = no instrumentation.
 GEMM_PROFILE = None
@@ -67,13 +73,31 @@ def _f32vec(t, n, name):
     assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n, f"{name}: need contiguous fp32[{n}]"
 
 
-def gemm(a, w, out_dtype=None, bias=None, act=ACT_NONE, col_scale=None, residual=None, res_row_mod=0, out=None, cfg=0, reverse=False):
+def split_weight_x3(w):
+    """fp32 weight [N, K] -> x3 split weight rows bf16 [N, 3K] = [hi | lo | hi] (host-side torch: runs once, at pack time)."""
+    w = w.detach().to(torch.float32)
+    hi = w.to(torch.bfloat16)
+    lo = (w - hi.to(torch.float32)).to(torch.bfloat16)
+    return torch.cat([hi, lo, hi], dim=1).contiguous()
+
+
+def gemm(a, w, out_dtype=None, bias=None, act=ACT_NONE, col_scale=None, residual=None, res_row_mod=0, out=None, cfg=0, reverse=False,
+         x3=False):
     """out[M,N] = residual + col_scale * act(a[M,K] @ w[N,K]^T + bias). cfg: per-call kernel choice (0 = automatic).
-    reverse: walk the tiles from the last row panel to the first (same result; see ORDER_REVERSE)."""
+    reverse: walk the tiles from the last row panel to the first (same result; see ORDER_REVERSE).
+    x3: a [M, 3K] / w [N, 3K] are x3 split rows (see X3); out_dtype X3 writes the result as split rows [M, 3N] (an fp32 result, then
+    cor_split_x3)."""
+    if out_dtype == X3:
+        assert out is None and x3
+        y = gemm(a, w, torch.float32, bias, act, col_scale, residual, res_row_mod, None, cfg, reverse, x3)
+        return split_x3(y)
     _dev(a, w, bias, col_scale, residual, out)
     M, K, lda = _rows(a)
     N, K2, ldw = _rows(w)
     assert K == K2 and a.dtype == w.dtype, (a.shape, w.shape, a.dtype, w.dtype)
+    if x3:
+        assert a.dtype == torch.bfloat16 and K % 3 == 0, (a.shape, a.dtype)
+        K //= 3
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype or a.dtype, device=a.device)
     Mo, No, ldc = _rows(out)
@@ -88,25 +112,33 @@ def gemm(a, w, out_dtype=None, bias=None, act=ACT_NONE, col_scale=None, residual
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    nat.check(_lib().cor_gemm(a.data_ptr(), lda, w.data_ptr(), ldw, _dt(a), out.data_ptr(), ldc, _dt(out), M, N, K,
+    nat.check(_lib().cor_gemm(a.data_ptr(), lda, w.data_ptr(), ldw, nat.BF16X3 if x3 else _dt(a), out.data_ptr(), ldc, _dt(out), M, N, K,
                               _p(bias), act, _p(col_scale), _p(residual), ldr, res_row_mod, int(cfg) | (nat.ORDER_REVERSE if reverse else 0), _s()), "cor_gemm")
     if prof is not None:
         e1.record()
-        nbytes = (M * K + N * K) * a.element_size() + M * N * out.element_size() + (M * N * 4 if residual is not None else 0)
-        prof.append((e0, e1, 2.0 * M * N * K, a.dtype, float(nbytes)))
+        k_run = 3 * K if x3 else K
+        nbytes = (M * k_run + N * k_run) * a.element_size() + M * N * out.element_size() + (M * N * 4 if residual is not None else 0)
+        prof.append((e0, e1, 2.0 * M * N * k_run, a.dtype, float(nbytes)))
     return out
 
 
 def layernorm(x, w, b, eps, out_dtype=None, act=ACT_NONE, out=None, reverse=False):
+    """out_dtype X3 (fp32 x): the normalised rows as x3 split rows [rows, 3C]."""
     _dev(x, w, b, out)
     assert x.is_contiguous() and x.dim() == 2
     rows, C = x.shape
     _f32vec(w, C, "ln.weight")
     _f32vec(b, C, "ln.bias")
-    if out is None:
-        out = torch.empty((rows, C), dtype=out_dtype or x.dtype, device=x.device)
-    assert out.is_contiguous() and out.shape == x.shape
-    nat.check(_lib().cor_layernorm(x.data_ptr(), _dt(x), out.data_ptr(), _dt(out), w.data_ptr(), b.data_ptr(), rows, C,
+    if out_dtype == X3:
+        assert out is None and x.dtype == torch.float32
+        out = torch.empty((rows, 3 * C), dtype=torch.bfloat16, device=x.device)
+        y_dt = nat.BF16X3
+    else:
+        if out is None:
+            out = torch.empty((rows, C), dtype=out_dtype or x.dtype, device=x.device)
+        assert out.is_contiguous() and out.shape == x.shape
+        y_dt = _dt(out)
+    nat.check(_lib().cor_layernorm(x.data_ptr(), _dt(x), out.data_ptr(), y_dt, w.data_ptr(), b.data_ptr(), rows, C,
                                    float(eps), act | (nat.ORDER_REVERSE if reverse else 0), _s()), "cor_layernorm")
     return out
 
@@ -121,6 +153,26 @@ def attention(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=None):
     nat.check(_lib().cor_attention(q.data_ptr(), Tq * q.stride(0), q.stride(0), k.data_ptr(), Tk * k.stride(0), k.stride(0),
                                    v.data_ptr(), Tk * v.stride(0), v.stride(0), _dt(q), out.data_ptr(), Tq * H * hd, H * hd,
                                    _dt(out), B, H, Tq, Tk, hd, float(scale), _s()), "cor_attention")
+    return out
+
+
+def attention_f32(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=torch.float32):
+    """flash_fwd_f32 (cor_attention_f32): exact-fp32 MHA on the f32 matrix cores. q [B*Tq, >=H*hd] / k,v [B*Tk, ...] fp32 row-major 2-D
+    views (e.g. column slices of an fp32 qkv activation) -> fp32 [B*Tq, H*hd] or, out_dtype X3, split rows [B*Tq, 3*H*hd]."""
+    _dev(q, k, v)
+    for t, T in ((q, Tq), (k, Tk), (v, Tk)):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * T and t.shape[1] == H * hd, (t.shape, B, T, H, hd)
+    if out_dtype == X3:
+        out = torch.empty((B * Tq, 3 * H * hd), dtype=torch.bfloat16, device=q.device)
+        o_dt = nat.BF16X3
+    else:
+        assert out_dtype == torch.float32
+        out = torch.empty((B * Tq, H * hd), dtype=torch.float32, device=q.device)
+        o_dt = F32
+    ld = out.shape[1]
+    nat.check(_lib().cor_attention_f32(q.data_ptr(), Tq * q.stride(0), q.stride(0), k.data_ptr(), Tk * k.stride(0), k.stride(0),
+                                       v.data_ptr(), Tk * v.stride(0), v.stride(0), out.data_ptr(), Tq * ld, ld, o_dt,
+                                       B, H, Tq, Tk, hd, float(scale), _s()), "cor_attention_f32")
     return out
 
 
@@ -141,6 +193,8 @@ def sam_attention(qkv, pad_row, rel_h, rel_w, B, H, grid, window, out_dtype=None
 
 
 def patchify(img, p, Kpad, out_dtype):
+    if out_dtype == X3:
+        return split_x3(patchify(img, p, Kpad, torch.float32))
     _dev(img)
     assert img.dtype == torch.float32 and img.is_contiguous() and img.dim() == 4
     B, C, H, W = img.shape
@@ -185,8 +239,27 @@ def copy_rows(src_ptr_tensor, ld_in, rows, C, out, ld_out=None, src_offset=0):
     return out
 
 
+def split_x3(x, out=None, seg=None):
+    """fp32 rows x [rows, C] (row-major 2-D view) -> x3 split rows (cor_split_x3): lo at out[:, 0:C], hi at out[:, seg:seg+C] and
+    out[:, 2seg:2seg+C]. out: a bf16 2-D view whose row stride holds 2*seg + C (default: new [rows, 3C], seg = C)."""
+    _dev(x, out)
+    rows, C, ld_in = _rows(x)
+    assert x.dtype == torch.float32
+    seg = C if seg is None else seg
+    if out is None:
+        out = torch.empty((rows, 3 * C), dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == rows
+    ld_out = out.stride(0) if rows > 1 else out.shape[1]
+    assert 2 * seg + C <= out.shape[1] and seg >= C, (seg, C, out.shape)
+    nat.check(_lib().cor_split_x3(x.data_ptr(), ld_in, out.data_ptr(), ld_out, seg, rows, C, _s()), "cor_split_x3")
+    return out
+
+
 def cast(x, dtype):
-    """Contiguous dtype conversion through cor_copy_rows (no-op when already `dtype`)."""
+    """Contiguous dtype conversion through cor_copy_rows (no-op when already `dtype`); dtype X3: fp32 -> x3 split rows."""
+    if dtype == X3:
+        assert x.dim() == 2 and x.is_contiguous()
+        return split_x3(x)
     if x.dtype == dtype:
         return x
     assert x.is_contiguous()

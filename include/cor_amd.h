@@ -11,7 +11,8 @@
  *  - `stream` is a hipStream_t passed as void*; kernels are only enqueued, never synchronised;
  *  - return 0 on success, a positive hipError_t for a launch failure, COR_EINVAL (-1) for bad arguments,
  *    COR_ENOSUPPORT (-2) for a shape/dtype combination that has no kernel (never a silent fallback);
- *  - activations are token-major row matrices [rows, C] (channels-last); dtypes are COR_F32 or COR_BF16;
+ *  - activations are token-major row matrices [rows, C] (channels-last); dtypes are COR_F32 or COR_BF16 (COR_BF16X3 split rows
+ *    where stated: the exact-query mode's support branch);
  *    parameters that stay in fp32 (bias, LayerNorm affine, rel-pos tables) are `const float*`.
  */
 #ifndef COR_AMD_H
@@ -33,7 +34,12 @@ extern "C" {
 #define COR_TOPK_FORCE_GLOBAL_THRESHOLD 8 /* ... : never the two-launch local-threshold path of small shards (A/B partner, tests) */
 #define COR_TOPK_WAVE_FINAL 16 /* ... : global-threshold pipeline with the one-wave-per-query selection kernel fed from the records (slower A/B partner, tests) */
 
-enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */ };
+enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */, COR_BF16X3 = 3 /* x3 split rows, see below */ };
+/* COR_BF16X3 (exact-query mode: the support branch at fp32 accuracy on the bf16 matrix cores). An fp32 value x is carried as
+ * hi = bf16_rne(x) and lo = bf16_rne(x - hi); a SPLIT ROW of C logical values is bf16 [lo(0..C) | hi(0..C) | hi(0..C)] (3C elements,
+ * segment stride C unless stated), a split WEIGHT row is [hi | lo | hi]. A bf16 GEMM over the 3K columns then computes
+ * A_lo.W_hi + A_hi.W_lo + A_hi.W_hi into ONE fp32 accumulator in that order (error ~1e-6 of sum|a.b| at K = 768, ~500x below bf16).
+ * Accepted as cor_gemm's ab_dtype, cor_layernorm's y_dtype (fp32 x), cor_attention_f32's out_dtype; cor_split_x3 makes it from fp32. */
 enum { COR_ACT_NONE = 0, COR_ACT_GELU_ERF = 1, COR_ACT_RELU = 2, COR_ACT_SIGMOID = 3, COR_ACT_GELU_TANH = 4 };
 
 int cor_version(void);
@@ -50,6 +56,9 @@ int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab_dtype,
              void* C, long ldc, int c_dtype, int M, int N, int K,
              const float* bias, int act, const float* col_scale,
              const float* residual, long ldr, int res_row_mod, int cfg, void* stream);
+/* ab_dtype COR_BF16X3: A [M, >= 3K] split rows, W [N, >= 3K] split weight rows, K the LOGICAL depth; c_dtype COR_F32 or COR_BF16.
+ * Every cfg (and COR_ORDER_REVERSE) applies unchanged: the kernels run their K loop over the three K segments.
+ * ref: the support branch's nn.Linear / 1x1 convs in exact-query mode (lib/support_branch.py:56-87, siglip_openclip.py:30-59). */
 /* `cfg` is a PER-CALL kernel choice (no process-global state; safe from several threads / streams): 0 = automatic
  * (13 for bf16 operands from 200 output tiles of 256x256 up, else 2, or 1 when K has a ragged tail); 1: 128x128 register-staged
  * (any K); 2: 128x128 LDS-DMA; 3 / 4: 128x64 / 64x64; 9: 256x128, three LDS buffers; 13: persistent 256x256 ping-pong kernel
@@ -62,6 +71,8 @@ int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab_dtype,
  *      channels-last rows), transformer.py norm1..4. */
 int cor_layernorm(const void* x, int x_dtype, void* y, int y_dtype, const float* w, const float* b,
                   int rows, int C, float eps, int act, void* stream);
+/* y_dtype COR_BF16X3 (x fp32): y [rows, 3C] split rows, the A operand of the next x3 GEMM (SigLIP norm1 / norm2 / ln_1 / ln_2 ->
+ * qkv / fc1 in exact-query mode: timm vision_transformer Block, open_clip ResidualAttentionBlock). */
 
 /* ---- attention -------------------------------------------------------------------------------------------- */
 
@@ -78,6 +89,15 @@ int cor_attention(const void* q, long q_sb, long q_st, const void* k, long k_sb,
                   const void* v, long v_sb, long v_st, int dtype,
                   void* out, long o_sb, long o_st, int out_dtype,
                   int B, int H, int Tq, int Tk, int hd, float scale, void* stream);
+
+/* flash_fwd_f32: the same plain MHA as cor_attention with fp32 q / k / v, on the f32-input matrix cores (v_mfma_f32_16x16x4_f32: exact
+ * f32 products, fp32 online softmax, P kept in fp32): the SigLIP towers of exact-query mode. hd in {64, 72, 80}, any Tq / Tk >= 1;
+ * k / v 16-byte aligned, all strides multiples of 4. out_dtype COR_F32 (out [.., H*hd] rows) or COR_BF16X3 (split rows of H*hd logical
+ * values: o_st >= 3*H*hd bf16 elements), i.e. the A operand of the proj GEMM. cor_attention's fp32 path (row-per-lane kernel) is unchanged.
+ * ref: SigLIP towers' MHA (timm Attention, open_clip nn.MultiheadAttention; siglip_openclip.py:30-59). */
+int cor_attention_f32(const float* q, long q_sb, long q_st, const float* k, long k_sb, long k_st,
+                      const float* v, long v_sb, long v_st, void* out, long o_sb, long o_st, int out_dtype,
+                      int B, int H, int Tq, int Tk, int hd, float scale, void* stream);
 
 /* SAM ViTDet attention on the fused qkv activation [B*grid*grid, 3*H*hd] (q|k|v, head-major inside each;
  * hd = 64 for SAM-B/L and 80 for SAM-H (bf16: MFMA flash kernels), 16/32 for reduced test models (row-per-lane kernel)):
@@ -124,6 +144,12 @@ int cor_add(const void* a, int a_dtype, const void* b, int b_dtype, void* out, i
 
 /* dtype cast / strided row copy: out[r, :C] = in[r, :C]; ld_in == 0 broadcasts one source row. */
 int cor_copy_rows(const void* in, long ld_in, int in_dtype, void* out, long ld_out, int out_dtype, int rows, int C, void* stream);
+
+/* fp32 -> split rows (COR_BF16X3): out[r*ld_out + c] = lo, out[r*ld_out + seg + c] = out[r*ld_out + 2*seg + c] = hi for c < C
+ * (seg >= C: several logical column blocks can share one split row, e.g. [image | text] of the fusion gates; ld_out >= 2*seg + C).
+ * ref: the casts ahead of the support branch's GEMMs in exact-query mode (mask_adapter.py:90,163, cir_feature_fuse.py:44-58,
+ *      support_branch.py:86, patch embedding). */
+int cor_split_x3(const float* in, long ld_in, void* out, long ld_out, long seg, int rows, int C, void* stream);
 
 /* [rows, C] channels-last tokens -> NCHW [B, C, HW] (fp32 out) and back. */
 int cor_tokens_to_nchw(const void* x, int dtype, float* out, int B, int HW, int C, void* stream);
