@@ -16,6 +16,7 @@
 // order is, for c = 0..C/8-1, i = 0..3:  k = 8c+i  then  k = 8c+4+i. oracle/c/sim_chain.c restates exactly this
 // chain, so fp32 scores (and hence top-k indices) can be checked BITWISE against the CPU.
 // bf16 / fp16 gallery: v_mfma_f32_32x32x16_{bf16,f16}; Q is rounded to the gallery dtype in registers.
+// Everything up to the "WIDE k" section serves k <= 32; 33 <= k <= 256 takes the route of that section (launch_topk dispatches on k first).
 #include <limits.h>
 
 #include "common.h"
@@ -352,7 +353,9 @@ __device__ __forceinline__ float key2f_floor(unsigned key) {      // the smalles
   return __uint_as_float(u);
 }
 
-template <typename TG, int QB, bool SAMPLE>
+// WIDE (33 <= k <= 256, see the wide-k route below): SAMPLE stores every (slice, lane quarter) group maximum on its own, sg[q * Bqp + split * 4 + rq]
+// with Bqp = the group count (no super-group folding: tau needs >= k groups); APPEND reads tau_q from a.tau (sim_tau_wide ranked the groups).
+template <typename TG, int QB, bool SAMPLE, bool WIDE = false>
 __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int C = 256, TILE = 32 * C * 2, STILE = 2 * TILE, NS = SCAN_NS, AHEAD = SCAN_AHEAD;
@@ -415,7 +418,10 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   // -inf, every row is a candidate). Any lower bound of the k-th best score is valid, so 32 unions of the (slice, lane quarter) groups serve
   // as well as the 512 groups the launch ranked (~15 % more candidates).
   float* tau_s = (float*)(smem + (SCAN_NS - 1) * 2 * 32 * 256 * 2);   // in the LAST ring slot: first written by the copies behind the loop's first barrier
-  if (!SAMPLE) {
+  if (!SAMPLE && WIDE) {
+    if (tid < 256 * QB) tau_s[tid] = a.tau[min(qg * (256 * QB) + tid, a.Bq - 1)];
+    __syncthreads();
+  } else if (!SAMPLE) {
     const int ql = tid;                                // 256 * QB queries per block, 512 threads
     if (ql < 256 * QB) {
       const int qg_ = min(qg * (256 * QB) + ql, a.Bq - 1);
@@ -578,7 +584,8 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
     for (int qb = 0; qb < NQ; ++qb) {
       const int q = q0 + qb * 16 + n16;
       if (q < a.Bq) {
-        if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
+        if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
+        else if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
         else a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb];
       }
     }
@@ -627,6 +634,7 @@ __global__ void __launch_bounds__(256) sim_prep(const float* __restrict__ Q, int
 template <typename TG> __device__ __forceinline__ float round_to(float x);
 template <> __device__ __forceinline__ float round_to<bf16_t>(float x) { return bf2f(f2bf(x)); }
 template <> __device__ __forceinline__ float round_to<_Float16>(float x) { return (float)(_Float16)x; }
+template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
 
 // chain score of gallery row `idx` against the query in LDS (oracle/c/sim_chain.c order: chunk c of 8: k = 8c+i then 8c+4+i)
 template <typename TG>
@@ -1634,9 +1642,516 @@ int launch_small(const float* Q, const TG* G, int Bq, int Ng, int k, long long g
 #undef SB_GO
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// WIDE k (33 <= k <= COR_TOPK_KMAX = 256): Recall@50/100 and two-stage re-ranking. The k <= 32 kernels above keep sorted lists in
+// registers (KMAX <= 32) and bound the k-th best score by 32 super-group maxima; neither scales to k = 256. This route keeps the
+// threshold-and-append shape with more groups and a block-wide selection:
+//   scan: 16-bit galleries with C = 256 run sim_prep + sim_scan<.., WIDE> (the production scan; SAMPLE stores >= 2k group maxima per
+//     query instead of folding them into 32); fp32 galleries and 16-bit ones with C != 256 run sim_wide_scan, the tile loop of
+//     sim_topk_partial with a SAMPLE and an APPEND epilogue ((score, row) entries instead of register lists).
+//   sim_tau_wide: tau_q = k-th largest group maximum - delta_q (block radix select over the group keys; delta_q = 0 for fp32, whose
+//     MFMA scores ARE the chain; fewer than k groups: -inf, every row is a candidate).
+//   sim_final_wide: per query, the candidates >= tau_q are compacted into LDS, the EXACT k-th best scan score T is found by a 4-pass radix
+//     select, the short list {score >= T - delta_q} is re-scored with the chain of oracle/c/sim_chain.c over C / 8 chunks (16-bit only)
+//     and ranked by one bitonic sort of 64-bit keys (inverted order-preserving score bits, index). Exactness: the argument of v3 above,
+//     for any C <= 256 (C - 1 roundings per score either way).
+// Overflow (a stream list, the candidate buffer or the short list) is detected and repaired in the same block: an exact radix select
+// over the chain scores of the whole shard (wide_brute_force). Every wide call is bitwise the chain oracle, whatever the dtype and C.
+constexpr int FSW = 8192;                              // candidates per query in LDS (64 KiB)
+constexpr int SLW = 2048;                              // short list (>= 2 k_max, room for ties within delta)
+constexpr size_t FINAL_WIDE_LDS = (size_t)FSW * 8 + SLW * 8 + 256 * 4 + 256 * 4;
+
+// k-th largest (1-based, 1 <= k <= n) of the order-preserving keys key_at(i), i < n: a 4-pass radix select, 8 bits per pass, over the
+// NT = 256 threads of the block (wave 0 scans the histogram as sim_final does). *k_rem ends as the k-th key's rank among the keys EQUAL
+// to it (k - *k_rem keys are larger). key_at may be expensive (the brute-force path re-scores a row per call): it runs 4 n times.
+template <typename F>
+__device__ unsigned block_kth_key(F key_at, int n, int k, int* hist, int* sel_bin, int* k_rem) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned prefix = 0;
+  if (tid == 0) *k_rem = k;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+      const unsigned key = key_at(i);
+      if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1);
+    }
+    __syncthreads();
+    if (wave == 0) {                                   // bins 4*lane .. 4*lane+3; suffix sums from the top bin down
+      const int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+      const int mine = h0 + h1 + h2 + h3;
+      int above = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_down(above, o, 64); if (lane + o < 64) above += t; }
+      above -= mine;
+      const int kr = *k_rem;
+      if (above < kr && kr <= above + mine) {          // exactly one lane
+        int a3 = above, b = 3;
+        if (kr <= a3 + h3) b = 3; else { a3 += h3; if (kr <= a3 + h2) b = 2; else { a3 += h2; if (kr <= a3 + h1) b = 1; else { a3 += h1; b = 0; } } }
+        *sel_bin = 4 * lane + b; *k_rem = kr - a3;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | (unsigned)*sel_bin;
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// ascending bitonic sort of n (a power of two, <= 256 * 64) 64-bit keys in LDS by the block's 256 threads
+__device__ void block_sort_u64(unsigned long long* key, int n) {
+  for (int kk = 2; kk <= n; kk <<= 1)
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < n; i += 256) {
+        const int l = i ^ j;
+        if (l > i) {
+          const unsigned long long x = key[i], y = key[l];
+          if ((x > y) == ((i & kk) == 0)) { key[i] = y; key[l] = x; }
+        }
+      }
+      __syncthreads();
+    }
+}
+// (score desc, index asc) as one ascending 64-bit key, and back
+__device__ __forceinline__ unsigned long long rank_key(float s, int idx) { return ((unsigned long long)~f2key(s) << 32) | (unsigned)idx; }
+__device__ __forceinline__ float rank_key_score(unsigned long long key) { return key2f_floor(~(unsigned)(key >> 32)); }
+
+// chain score of gallery row idx (C values, C % 16 == 0) against qs: the order of oracle/c/sim_chain.c for any C (chunks of 8:
+// k = 8c+i then 8c+4+i); fp32 rows as stored, 16-bit rows widened exactly
+template <typename TG>
+__device__ __forceinline__ float chain_score_c(const TG* __restrict__ G, long idx, int C, const float* qs) {
+  float acc = 0.f;
+  if constexpr (sizeof(TG) == 4) {
+    const f32x4* row = (const f32x4*)(G + idx * C);
+#pragma unroll 4
+    for (int c = 0; c < C / 8; ++c) {
+      const f32x4 a = row[2 * c], b = row[2 * c + 1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { acc = fmaf(a[i], qs[8 * c + i], acc); acc = fmaf(b[i], qs[8 * c + 4 + i], acc); }
+    }
+  } else {
+    const uint4* row = (const uint4*)(G + idx * C);
+#pragma unroll 4
+    for (int c = 0; c < C / 8; ++c) {
+      const uint4 v = row[c];
+      float g[8];
+      if (__is_same(TG, bf16_t)) {
+        g[0] = __uint_as_float(v.x << 16); g[1] = __uint_as_float(v.x & 0xffff0000u); g[2] = __uint_as_float(v.y << 16); g[3] = __uint_as_float(v.y & 0xffff0000u);
+        g[4] = __uint_as_float(v.z << 16); g[5] = __uint_as_float(v.z & 0xffff0000u); g[6] = __uint_as_float(v.w << 16); g[7] = __uint_as_float(v.w & 0xffff0000u);
+      } else {
+        const f16x8 hv = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g[i] = (float)hv[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { acc = fmaf(g[i], qs[8 * c + i], acc); acc = fmaf(g[4 + i], qs[8 * c + 4 + i], acc); }
+    }
+  }
+  return acc;
+}
+
+// Exact top-k of ONE query over the whole shard (block of 256 threads), for overflowed queries: the k-th largest chain-score key by
+// block_kth_key (four passes, every row re-scored per pass), then one more pass collects the rows above it (fewer than k, any order)
+// and the first k_rem rows EQUAL to it in index order (a block-wide prefix count per 256 rows), and a bitonic sort ranks them.
+// Five chain passes over the shard: slow, exact, rare (DESIGN 3.4 gives the measured cost).
+template <typename TG>
+__device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float* sl_s, int* sl_i,
+                                 unsigned long long* keys, int* hist, float* out_s, long long* out_i) {
+  __shared__ int sel_bin, k_rem, n_above, wcnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kk = min(k, Ng);
+  auto key_at = [&](int g) { return f2key(chain_score_c<TG>(G, g, C, qs)); };
+  unsigned kth = 0u;                                   // Ng <= k: every row is above "key 0"
+  int above = kk, need = 0;
+  if (Ng > k) { kth = block_kth_key(key_at, Ng, k, hist, &sel_bin, &k_rem); need = k_rem; above = k - need; }
+  if (tid == 0) n_above = 0;
+  __syncthreads();
+  int taken = 0;                                       // rows equal to kth already collected (block-uniform)
+  for (int g0 = 0; g0 < Ng; g0 += 256) {
+    const int g = g0 + tid;
+    float s = -INFINITY; unsigned key = 0u;
+    if (g < Ng) { s = chain_score_c<TG>(G, g, C, qs); key = f2key(s); }
+    const bool up = g < Ng && key > kth, tie = g < Ng && key == kth && Ng > k;
+    if (up) { const int p = atomicAdd(&n_above, 1); sl_s[p] = s; sl_i[p] = g; }
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(tie);
+    if (lane == 0) wcnt[wave] = __builtin_popcountll(b);
+    __syncthreads();
+    int before = taken, tot = 0;
+    for (int w = 0; w < 4; ++w) { before += w < wave ? wcnt[w] : 0; tot += wcnt[w]; }
+    if (tie) {
+      const int pos = before + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+      if (pos < need) { sl_s[above + pos] = s; sl_i[above + pos] = g; }
+    }
+    taken += tot;
+    __syncthreads();
+  }
+  int P = 1;
+  while (P < kk) P <<= 1;
+  for (int j = tid; j < P; j += 256) keys[j] = j < kk ? rank_key(sl_s[j], sl_i[j]) : ~0ull;
+  __syncthreads();
+  block_sort_u64(keys, P);
+  for (int j = tid; j < k; j += 256) {
+    out_s[j] = j < kk ? rank_key_score(keys[j]) : -INFINITY;
+    out_i[j] = j < kk ? (long long)(unsigned)keys[j] + g_offset : -1LL;
+  }
+}
+
+// The tile loop of sim_topk_partial (fp32 galleries: the chain on the f32 MFMA; 16-bit: the 16-bit MFMA; any C <= 256, C % 16 == 0)
+// with the epilogues of the wide route. One wave = 32 queries x a slice of 32-row tiles; lane (r, h) holds 16 scores of query r per tile.
+//   SAMPLE: tiles t * tile_stride of the slice; the group (slice, lane half h) keeps its maximum: sg[q * ngroups + split * 2 + h].
+//   APPEND: every tile of the slice; scores >= tau_q go to the private list of stream (q, slice, h) as (score bits, row) entries.
+struct WideScanArgs {
+  int Bq, Ng, C, nqt, nsplit, tiles_per_split, ntiles, tile_stride;
+  unsigned* sg; int ngroups;
+  const float* tau; int* cnt; uint2* lst; int cap;
+};
+template <typename TG, bool SAMPLE>
+__global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q, const TG* __restrict__ G, const WideScanArgs a) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= a.nqt * a.nsplit) return;
+  const int qt = wid % a.nqt, split = wid / a.nqt;
+  const int q = qt * 32 + r, Ng = a.Ng, C = a.C;
+  const float* qrow = Q + (long)min(q, a.Bq - 1) * C;
+
+  constexpr bool F32 = sizeof(TG) == 4;
+  constexpr int CH = F32 ? 8 : 16;
+  constexpr int NCH = 256 / CH;
+  const int nch = C / CH;
+  uint4 qf[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (c < nch) {
+      if constexpr (F32) qf[c] = *(const uint4*)(qrow + c * 8 + 4 * h);
+      else qf[c] = q_frag16<TG>(qrow, c, h);
+    }
+  }
+  // padding lanes (q >= Bq) never append; the floor keeps masked -inf scores out of the lists when tau_q is -inf
+  const float tq = SAMPLE ? 0.f : (q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
+  const int stream = split * 2 + h, nstreams = 2 * a.nsplit;
+  float gmax = -INFINITY;
+  int n = 0;
+  const int t0 = split * a.tiles_per_split, t1 = min(t0 + a.tiles_per_split, a.ntiles);
+  for (int t = t0; t < t1; ++t) {
+    const int g0 = t * a.tile_stride * 32;
+    const char* grow = (const char*)(G + (long)min(g0 + r, Ng - 1) * C) + 16 * h;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c < nch) {
+        const uint4 av = *(const uint4*)(grow + c * 32);
+        if (F32) {
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.x), __uint_as_float(qf[c].x), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.y), __uint_as_float(qf[c].y), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.z), __uint_as_float(qf[c].z), acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.w), __uint_as_float(qf[c].w), acc, 0, 0, 0);
+        } else if (__is_same(TG, bf16_t)) {
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, qf[c]), acc, 0, 0, 0);
+        } else {
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av), __builtin_bit_cast(f16x8, qf[c]), acc, 0, 0, 0);
+        }
+      }
+    }
+    float sc[16], tmax = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      sc[e] = g0 + (e & 3) + 8 * (e >> 2) + 4 * h < Ng ? acc[e] : -INFINITY;
+      tmax = fmaxf(tmax, sc[e]);
+    }
+    if (SAMPLE) {
+      gmax = fmaxf(gmax, tmax);
+    } else if (__builtin_amdgcn_ballot_w64(tmax >= tq) != 0) {
+      uint2* dst = a.lst + ((long)q * nstreams + stream) * a.cap;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        if (sc[e] >= tq) {
+          if (n < a.cap) dst[n] = make_uint2(__float_as_uint(sc[e]), (unsigned)(g0 + (e & 3) + 8 * (e >> 2) + 4 * h));
+          ++n;
+        }
+      }
+    }
+  }
+  if (q < a.Bq) {
+    if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
+    else a.cnt[(long)q * nstreams + stream] = n;
+  }
+}
+
+// tau_q for the wide route: one block per query ranks its ngroups group-maximum keys (sg[q * ngroups + g]; 0 or key(-inf) = a group
+// without a finite score). delta_q bounds |scan score - chain score| for 16-bit galleries (sim_prep's form, any C <= 256); fp32: 0.
+template <typename TG>
+__global__ void __launch_bounds__(256) sim_tau_wide(const float* __restrict__ Q, int C, const unsigned* __restrict__ sg, int ngroups, int k,
+                                                    float* tau) {
+  __shared__ int hist[256], sel_bin, k_rem;
+  __shared__ float part[4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  float n2 = 0.f;
+  if (sizeof(TG) != 4 && tid < C) { const float x = round_to<TG>(Q[(long)q * C + tid]); n2 = x * x; }
+  n2 = wave_sum(n2);
+  if ((tid & 63) == 0) part[tid >> 6] = n2;
+  __syncthreads();
+  const float delta = sizeof(TG) == 4 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(part[0] + part[1] + part[2] + part[3]));
+  float t = -INFINITY;                                 // fewer than k groups: every row is a candidate
+  if (ngroups >= k) {
+    const unsigned* g = sg + (long)q * ngroups;
+    const unsigned kth = block_kth_key([&](int i) { return g[i]; }, ngroups, k, hist, &sel_bin, &k_rem);
+    if (kth > f2key(-INFINITY)) t = key2f_floor(kth) - delta;
+  }
+  if (tid == 0) tau[q] = t;
+}
+
+// Exact selection of the wide route, one block of 256 threads per query. RECORDS: the 8-score records of sim_scan<APPEND> (rec_s /
+// rec_g, the scores >= tau_q are kept); otherwise the (score, row) entry lists of sim_wide_scan<APPEND> (lst). fp32 galleries: the scan
+// scores are the chain, nothing is re-scored and delta = 0.
+template <typename TG, bool RECORDS>
+__global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C, int k, long long g_offset,
+                                                      const float* __restrict__ tau, const int* __restrict__ cnt, int nstreams, int cap,
+                                                      const float* __restrict__ rec_s, const int* __restrict__ rec_g, const uint2* __restrict__ lst,
+                                                      float* out_s, long long* out_i, int no_fallback) {
+  extern __shared__ __attribute__((aligned(16))) char fwraw[];
+  float* cs = (float*)fwraw; int* ci = (int*)(cs + FSW);
+  float* sl_s = (float*)(ci + FSW); int* sl_i = (int*)(sl_s + SLW);
+  float* qs = (float*)(sl_i + SLW); int* hist = (int*)(qs + 256);
+  unsigned long long* keys = (unsigned long long*)fwraw;   // the candidate buffer, dead once the short list is built (SLW * 8 B <= 64 KiB)
+  __shared__ int ovf, total, nsl, sel_bin, k_rem;
+  __shared__ float qn2[4];
+  constexpr bool F32 = sizeof(TG) == 4;
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) { ovf = 0; total = 0; nsl = 0; }
+  const float qv = tid < C ? round_to<TG>(Q[(long)q * C + tid]) : 0.f;   // the query as the scan saw it
+  if (tid < C) qs[tid] = qv;
+  const float part = wave_sum(qv * qv);
+  if (lane == 0) qn2[wave] = part;
+  __syncthreads();
+  const float delta = F32 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(qn2[0] + qn2[1] + qn2[2] + qn2[3]));
+  // 1. gather the candidates into LDS (thread <-> stream)
+  const float tq = tau[q];
+  for (int st = tid; st < nstreams; st += 256) {
+    const int c = cnt[(long)q * nstreams + st];
+    if (c > cap) ovf = 1;
+    const int nrec = min(c, cap);
+    const long rec0 = ((long)q * nstreams + st) * cap;
+    for (int j = 0; j < nrec; ++j) {
+      if (RECORDS) {                                   // score [g][i] of lane quarter st & 3 is row g0 + 16 g + 4 (st & 3) + i
+        const f32x4* sj = (const f32x4*)(rec_s + (rec0 + j) * 8);
+        const f32x4 v[2] = {sj[0], sj[1]};
+        const int g0 = rec_g[rec0 + j], r4 = 4 * (st & 3);
+        int np = 0;
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) np += (v[g][i] >= tq && v[g][i] > -INFINITY) ? 1 : 0;
+        if (np == 0) continue;
+        int p = atomicAdd(&total, np);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (v[g][i] >= tq && v[g][i] > -INFINITY) {
+              if (p < FSW) { cs[p] = v[g][i]; ci[p] = g0 + i + 16 * g + r4; }
+              ++p;
+            }
+      } else {
+        const uint2 e = lst[rec0 + j];
+        const int p = atomicAdd(&total, 1);
+        if (p < FSW) { cs[p] = __uint_as_float(e.x); ci[p] = (int)e.y; }
+      }
+    }
+  }
+  __syncthreads();
+  if (total > FSW) ovf = 1;
+  const int n = min(total, FSW);
+  __syncthreads();
+  // 2. T = the k-th best scan score, exactly (every row of the scan's top-k is a candidate); n <= k: every candidate is in
+  float T = -INFINITY;
+  if (!ovf && n > k) T = key2f_floor(block_kth_key([&](int i) { return f2key(cs[i]); }, n, k, hist, &sel_bin, &k_rem));
+  // 3. short list: scan score >= T - delta (fp32: the rows >= T, ties at T included)
+  if (!ovf) {
+    const float cut = T - delta;
+    for (int i = tid; i < n; i += 256) {
+      if (cs[i] >= cut) {
+        const int p = atomicAdd(&nsl, 1);
+        if (p < SLW) { sl_s[p] = cs[i]; sl_i[p] = ci[i]; }
+      }
+    }
+  }
+  __syncthreads();
+  if (nsl > SLW) ovf = 1;
+  __syncthreads();
+  if (ovf) {
+    if (no_fallback) {                                 // tests: expose the raw overflow marker
+      for (int j = tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -2LL; }
+      return;
+    }
+    wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
+    return;
+  }
+  const int m = nsl;
+  // 4. exact re-scoring (16-bit): the chain of oracle/c/sim_chain.c over the stored values
+  if (!F32)
+    for (int j = tid; j < m; j += 256) sl_s[j] = chain_score_c<TG>(G, sl_i[j], C, qs);
+  __syncthreads();
+  // 5. rank by (chain score desc, index asc): one bitonic sort; entries beyond the short list (Ng < k) are (-inf, -1)
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int j = tid; j < P; j += 256) keys[j] = j < m ? rank_key(sl_s[j], sl_i[j]) : ~0ull;
+  __syncthreads();
+  block_sort_u64(keys, P);
+  for (int j = tid; j < k; j += 256) {
+    out_s[(long)q * k + j] = j < m ? rank_key_score(keys[j]) : -INFINITY;
+    out_i[(long)q * k + j] = j < m ? (long long)(unsigned)keys[j] + g_offset : -1LL;
+  }
+}
+
+// plan of the wide route (host; shared by the launcher and cor_topk_workspace_bytes). scan = the sim_scan form (16-bit, C = 256).
+struct WidePlan {
+  bool scan;
+  int qb, nqg, nqt;                  // scan form: query blocks per wave, query groups of 256 * qb; tile form: 32-query tiles
+  int nsplit, tiles_per_split, ntiles, nstreams, cap;                // APPEND
+  int s_stride, s_tiles, s_nsplit, s_tiles_per_split, ngroups;       // SAMPLE (ngroups == 0: no sample, tau = -inf)
+  size_t off_img, off_sg, off_dq, off_tau, off_flags, off_ovf, off_cnt, off_recs, off_recg, bytes;
+};
+inline WidePlan make_wide(int Bq, int Ng, int k, bool scan) {
+  WidePlan p{};
+  p.scan = scan;
+  const int rows = scan ? 64 : 32;                     // rows per tile of the scan kernel
+  p.ntiles = cdiv(Ng, rows);
+  int want;
+  if (scan) {
+    p.qb = Bq > 256 ? 2 : 1;
+    p.nqg = cdiv(Bq, 256 * p.qb);
+    want = device_cus() / p.nqg;                       // one resident block per CU
+    if (want > 256) want = 256;
+  } else {
+    p.nqt = cdiv(Bq, 32);
+    want = cdiv(4096, p.nqt);                          // ~16 waves per CU
+  }
+  if (want > p.ntiles) want = p.ntiles;
+  if (want < 1) want = 1;
+  p.tiles_per_split = cdiv(p.ntiles, want);
+  p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
+  const int per_tile = scan ? 4 : 2;                   // streams per slice: lane quarters (scan) / lane halves (tiles)
+  p.nstreams = per_tile * p.nsplit;
+  const int stream_max = scan ? 2 * p.tiles_per_split : 16 * p.tiles_per_split;     // records / entries a stream can hold at most
+  if (Ng <= 4096) {                                    // tiny shard: no sample pass, every row is a candidate (<= FSW)
+    p.s_stride = 1;
+    p.cap = stream_max;
+  } else {
+    // Sample groups: >= 2 k per query keep tau near the k-th best score (k-th largest of G group maxima: the top ~G ln(G / (G - k))
+    // sampled rows, 1.4 k at G = 2 k), so the full scan admits ~1.4 k * stride candidates per query; the stride keeps that below
+    // FSW / 2. Groups: 4 per slice (scan form, up to 256 slices: 1024) or 2 (tile form, up to 512 slices); Ng > 4096 gives >= 260.
+    if (scan) p.s_stride = p.ntiles / 16 >= 128 ? 16 : (p.ntiles / 128 > 1 ? p.ntiles / 128 : 1);
+    else p.s_stride = p.ntiles / 512 > 1 ? p.ntiles / 512 : 1;
+    const int smax = 2048 / k > 1 ? 2048 / k : 1;
+    if (p.s_stride > smax) p.s_stride = smax;
+    p.s_tiles = cdiv(p.ntiles, p.s_stride);
+    int sw = scan ? 256 : 512;
+    if (sw > p.s_tiles) sw = p.s_tiles;
+    p.s_tiles_per_split = cdiv(p.s_tiles, sw);
+    p.s_nsplit = cdiv(p.s_tiles, p.s_tiles_per_split);
+    p.ngroups = per_tile * p.s_nsplit;
+    const long expect = 3L * k * p.s_stride;           // candidates per query, ~2x slack
+    // per stream: Poisson with mean ~ expect / nstreams; +10 keeps P(overflow) per search small
+    p.cap = (int)(2 * expect / p.nstreams) + 10;
+    if (p.cap > stream_max) p.cap = stream_max;
+  }
+  const int Bqp = scan ? p.nqg * 256 * p.qb : 0;
+  size_t o = 0;
+  auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
+  p.off_img = take(scan ? (size_t)p.nqg * 8 * p.qb * 16 * 64 * 16 : 0);
+  const size_t sg_n = (size_t)Bq * p.ngroups > (size_t)32 * Bqp ? (size_t)Bq * p.ngroups : (size_t)32 * Bqp;   // (sim_prep clears 32 x Bqp)
+  p.off_sg = take(sg_n * 4 + 4);
+  p.off_dq = take((size_t)Bq * 4);
+  p.off_tau = take((size_t)Bq * 4);
+  p.off_flags = take(16);
+  p.off_ovf = take((size_t)Bq * 4);
+  p.off_cnt = take((size_t)Bq * p.nstreams * 4);
+  p.off_recs = take((size_t)Bq * p.nstreams * p.cap * (scan ? 32 : 8));   // a record = 8 scores; an entry = (score, row)
+  p.off_recg = take(scan ? (size_t)Bq * p.nstreams * p.cap * 4 : 0);
+  p.bytes = o;
+  return p;
+}
+
+template <typename TG, int QB>
+int launch_wide_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long long g_offset, float* out_s, long long* out_i, char* w,
+                     const WidePlan& p, int flags, hipStream_t s) {
+  constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
+  static DevOnce once_s, once_a, once_f;
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true>, (int)lds, once_s);
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true>, (int)lds, once_a);
+  cor_max_dyn_lds((const void*)sim_final_wide<TG, true>, (int)FINAL_WIDE_LDS, once_f);
+  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
+  int* cnt = (int*)(w + p.off_cnt); float* rec_s = (float*)(w + p.off_recs); int* rec_g = (int*)(w + p.off_recg);
+  uint4* qimg = (uint4*)(w + p.off_img);
+  const int Bqp = p.nqg * 256 * QB;
+  hipLaunchKernelGGL((sim_prep<TG>), dim3(p.nqg * 8 * QB), dim3(256), 0, s, Q, Bq, qimg, (int*)(w + p.off_flags), (int*)(w + p.off_ovf), sg, Bqp,
+                     (float*)(w + p.off_dq));
+  COR_CHECK_LAUNCH();
+  ScanArgs a{};
+  a.Bq = Bq; a.Ng = Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups;
+  if (p.ngroups > 0) {
+    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
+    hipLaunchKernelGGL((sim_scan<TG, QB, true, true>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
+    COR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, 256, sg, p.ngroups, k, tau);
+  COR_CHECK_LAUNCH();
+  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
+  a.k = k; a.tau = tau; a.cnt = cnt; a.rec_s = rec_s; a.rec_g = rec_g; a.cap = p.cap; a.tau_add = 0.f;
+  hipLaunchKernelGGL((sim_scan<TG, QB, false, true>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
+  COR_CHECK_LAUNCH();
+  hipLaunchKernelGGL((sim_final_wide<TG, true>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     rec_s, rec_g, nullptr, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0);
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename TG>
+int launch_wide_tiles(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i, char* w,
+                      const WidePlan& p, int flags, hipStream_t s) {
+  static DevOnce once_f;
+  cor_max_dyn_lds((const void*)sim_final_wide<TG, false>, (int)FINAL_WIDE_LDS, once_f);
+  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
+  int* cnt = (int*)(w + p.off_cnt); uint2* lst = (uint2*)(w + p.off_recs);
+  WideScanArgs a{};
+  a.Bq = Bq; a.Ng = Ng; a.C = C; a.nqt = p.nqt; a.sg = sg; a.ngroups = p.ngroups;
+  if (p.ngroups > 0) {
+    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
+    hipLaunchKernelGGL((sim_wide_scan<TG, true>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
+    COR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, C, sg, p.ngroups, k, tau);
+  COR_CHECK_LAUNCH();
+  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
+  a.tau = tau; a.cnt = cnt; a.lst = lst; a.cap = p.cap;
+  hipLaunchKernelGGL((sim_wide_scan<TG, false>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
+  COR_CHECK_LAUNCH();
+  hipLaunchKernelGGL((sim_final_wide<TG, false>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     nullptr, nullptr, lst, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0);
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename TG>
+int launch_wide(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i, char* w,
+                int flags, hipStream_t s) {
+  if constexpr (sizeof(TG) == 2) {
+    if (C == 256) {
+      const WidePlan p = make_wide(Bq, Ng, k, true);
+      if (p.qb == 2) return launch_wide_scan<TG, 2>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s);
+      return launch_wide_scan<TG, 1>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s);
+    }
+  }
+  return launch_wide_tiles<TG>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false), flags, s);
+}
+
 template <typename TG>
 int launch_topk(const float* Q, const void* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i,
                 void* workspace, int flags, hipStream_t s) {
+  if (k > 32) return launch_wide<TG>(Q, (const TG*)G, Bq, Ng, C, k, g_offset, out_s, out_i, (char*)workspace, flags, s);   // 33 <= k <= COR_TOPK_KMAX
   float* ws_s = (float*)workspace;
   const bool force_lists = (flags & COR_TOPK_FORCE_LISTS) != 0;
   if constexpr (sizeof(TG) == 2) {
@@ -1663,7 +2178,11 @@ int launch_topk(const float* Q, const void* G, int Bq, int Ng, int C, int k, lon
 }  // namespace
 
 extern "C" long cor_topk_workspace_bytes(int Bq, int Ng, int k) {
-  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > 32) return COR_EINVAL;
+  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
+  if (k > 32) {                                        // the wide route: whichever form the gallery's dtype and C select
+    const long a = (long)make_wide(Bq, Ng, k, true).bytes, b = (long)make_wide(Bq, Ng, k, false).bytes;
+    return a > b ? a : b;
+  }
   const TopkPlan p = make_plan(Bq, Ng, k);
   const TopkPlan2 p2 = make_plan2(Bq, Ng, k, device_cus());
   const long a = (long)Bq * p.nparts * p.kmax * 8, b = (long)Bq * p2.nparts * p2.kmax * 8;
@@ -1677,7 +2196,8 @@ extern "C" long cor_topk_workspace_bytes(int Bq, int Ng, int k) {
 extern "C" int cor_similarity_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                                    float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
   if (!Q || !G || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
-  if (k > 32 || C > 256 || (C & 15)) return COR_ENOSUPPORT;
+  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
+  if (k > 32 && (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL))) return COR_ENOSUPPORT;   // register-list / one-wave kernels: k <= 32
   if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)workspace & 255)) return COR_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   switch (g_dtype) {

@@ -431,10 +431,15 @@ def iou_select(iou, hyper, k_off, Ksel):
 
 
 def similarity_topk(Q, G, k, g_offset=0, flags=0):
-    """Top-k gallery rows per query by dot product; (score desc, index asc). Q fp32 [Bq,C]; G [Ng,C] fp32/bf16/fp16.
-    fp32 galleries and 16-bit galleries with C = 256: scores and indices are bit-identical to the CPU fmaf-chain oracle
-    (oracle/c/sim_chain.c). A candidate overflow (pathological score distributions) is repaired ON THE DEVICE by the gated
-    list kernels: no host synchronisation here. flags: nat.TOPK_FORCE_LISTS | nat.TOPK_NO_FALLBACK (tests)."""
+    """Top-k gallery rows per query by dot product; (score desc, index asc). Q fp32 [Bq,C]; G [Ng,C] fp32/bf16/fp16;
+    1 <= k <= nat.TOPK_KMAX (256); Ng < k: the tail is (-inf, -1).
+    k <= 32: fp32 galleries and 16-bit galleries with C = 256 are bit-identical to the CPU fmaf-chain oracle
+    (oracle/c/sim_chain.c), scores and indices. 33 <= k <= 256 (the wide route: Recall@50/100, two-stage re-ranking): every
+    gallery dtype and every C is bit-identical to that oracle. A candidate overflow (pathological score distributions) is
+    repaired ON THE DEVICE: no host synchronisation here. flags: nat.TOPK_FORCE_LISTS | nat.TOPK_NO_FALLBACK (tests);
+    TOPK_FORCE_LISTS and TOPK_WAVE_FINAL need k <= 32."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"similarity_topk: k must be in [1, {nat.TOPK_KMAX}], got {k}")
     _dev(Q, G)
     assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
     Bq, Cq = Q.shape

@@ -40,6 +40,31 @@ def merge_topk_host(scores_parts, idx_parts, k: int):
     return torch.gather(s, 1, o2), torch.gather(i, 1, o2)
 
 
+def recall_at_k(idx, positives, ks=(1, 5, 10, 50, 100)) -> dict:
+    """Recall@K of ranked lists: the fraction of queries with a positive among their first K entries.
+    idx: i64[B, k] global gallery ids (as distributed_search / GalleryShard.search return them; -1 = missing).
+    positives: one global id per query (a sequence or an i64[B] tensor) or, per query, a collection of ids.
+    Returns {K: fraction} for every K in ks; raises ValueError if max(ks) > k."""
+    idx = torch.as_tensor(idx).cpu().long()
+    if idx.dim() != 2:
+        raise ValueError(f"recall_at_k: idx must be [B, k], got {tuple(idx.shape)}")
+    B, k = idx.shape
+    ks = tuple(int(K) for K in ks)
+    if not ks or min(ks) < 1 or max(ks) > k:
+        raise ValueError(f"recall_at_k: every K must be in [1, {k}] (the lists hold {k} entries), got {ks}")
+    if isinstance(positives, torch.Tensor) and positives.dim() == 1:
+        positives = positives.tolist()
+    if len(positives) != B:
+        raise ValueError(f"recall_at_k: {len(positives)} positives for {B} queries")
+    sets = [{int(p)} if isinstance(p, int) or (isinstance(p, torch.Tensor) and p.dim() == 0) else {int(x) for x in p} for p in positives]
+    hit = torch.zeros((B, k), dtype=torch.bool)
+    for b, pos in enumerate(sets):
+        if pos:
+            hit[b] = torch.isin(idx[b], torch.tensor(sorted(pos), dtype=torch.int64)) & (idx[b] >= 0)
+    first = torch.where(hit.any(1), hit.float().argmax(1), torch.full((B,), k))    # rank of the first positive (k: none)
+    return {K: int((first < K).sum()) / B if B else 0.0 for K in ks}
+
+
 class GalleryShard:
     """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16."""
 
@@ -53,7 +78,7 @@ class GalleryShard:
         return self.rows.shape[0]
 
     def search(self, queries: torch.Tensor, k: int):
-        """queries f32[Bq,C] (unit-norm) -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU."""
+        """queries f32[Bq,C] (unit-norm) -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU; 1 <= k <= 256."""
         q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
         if self.rows.shape[0] == 0:                  # an empty shard (more ranks than gallery rows): all-missing lists, like Ng < k
             return (torch.full((q.shape[0], k), float("-inf"), device=q.device),
@@ -163,7 +188,7 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     defer: return a PendingSearch instead of the tensors: the device-to-host copy is enqueued (pinned memory + event) and the host merge
     happens in its result() - call it after enqueuing the next step's forward, so that the GPU does not idle through the host's turn.
     Returns (scores f32[B_total,k], idx i64[B_total,k]) CPU tensors, queries ordered by rank, on rank `dst` (every rank
-    for dst=None); (None, None) on the other ranks."""
+    for dst=None); (None, None) on the other ranks. k: 1 .. 256 (recall_at_k turns the lists into Recall@K)."""
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
         s, i = shard.search(local_queries, k)

@@ -33,6 +33,7 @@ extern "C" {
 #define COR_TOPK_NO_FALLBACK 2  /* ... : no device-side fallback after a candidate overflow: such queries return index -2 */
 #define COR_TOPK_FORCE_GLOBAL_THRESHOLD 8 /* ... : never the two-launch local-threshold path of small shards (A/B partner, tests) */
 #define COR_TOPK_WAVE_FINAL 16 /* ... : global-threshold pipeline with the one-wave-per-query selection kernel fed from the records (slower A/B partner, tests) */
+#define COR_TOPK_KMAX 256     /* largest k cor_similarity_topk accepts (k > 32: the wide route, see below) */
 
 enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */, COR_BF16X3 = 3 /* x3 split rows, see below */ };
 /* COR_BF16X3 (exact-query mode: the support branch at fp32 accuracy on the bf16 matrix cores). An fp32 value x is carried as
@@ -262,7 +263,7 @@ int cor_resample_cols_u8(const unsigned char* in, float* out_f32, unsigned char*
 
 /* Per query b: the top-k rows g of the gallery shard by score = q[b,:].G[g,:] (fp32 accumulate), ordered by
  * (score desc, index asc); indices are returned as global ids (g + g_offset).
- * Q [Bq,C] fp32, G [Ng,C] in g_dtype (COR_F32 exact chain / COR_BF16 / COR_F16), C <= 256 and C % 16 == 0, k <= 32;
+ * Q [Bq,C] fp32, G [Ng,C] in g_dtype (COR_F32 exact chain / COR_BF16 / COR_F16), C <= 256 and C % 16 == 0, 1 <= k <= COR_TOPK_KMAX (256);
  * missing entries (Ng < k) come back as score -inf, index -1. workspace >= cor_topk_workspace_bytes(Bq,Ng,k).
  * The reference has no gallery/top-k code; the definition follows utils/loss_func.py:84 (cosine of unit vectors).
  * Scores are DEFINED as the fp32 fmaf chain of oracle/c/sim_chain.c (16-bit rows widened exactly), for every gallery dtype: the
@@ -273,7 +274,15 @@ int cor_resample_cols_u8(const unsigned char* in, float* out_f32, unsigned char*
  * sim_final_wave: one wave per query selects, re-scores, ranks); everything else by threshold-and-append with a GLOBAL threshold (a strided
  * sample pass bounds each query's k-th best score by 32 super-group maxima, the full MFMA pass ranks them in its prologue and appends the
  * rare score records above the bound, the final pass re-scores the short list: four launches). If a query's candidate list overflows (pathological score distributions, e.g. hundreds of identical rows)
- * it is ranked by an exact brute-force chain pass ON THE DEVICE (no host round trip). `flags` (per call, no process-global state):
+ * it is ranked by an exact brute-force chain pass ON THE DEVICE (no host round trip). All of the above is k <= 32.
+ * 33 <= k <= 256 (WIDE k: Recall@50/100, two-stage re-ranking) takes its own route, bit-identical to the chain oracle for EVERY g_dtype and C
+ * (for 16-bit galleries with C != 256 that is stronger than k <= 32 promises): a strided sample pass keeps >= 2k group maxima per query, a
+ * small kernel ranks them into the bound tau_q, the full scan appends the scores >= tau_q (16-bit C = 256: the threshold-and-append scan
+ * above; fp32 and 16-bit C != 256: the tile kernels of the list path), and one block per query selects the exact k-th best scan score,
+ * re-scores the short list with the chain (16-bit) and ranks it with a bitonic sort. An overflowed query is ranked in the same block by a
+ * radix select over the chain scores of the whole shard (exact; tens of ms at 1M rows). Wide k: COR_TOPK_FORCE_LISTS and COR_TOPK_WAVE_FINAL
+ * return COR_ENOSUPPORT, COR_TOPK_FORCE_GLOBAL_THRESHOLD has no effect, COR_TOPK_NO_FALLBACK keeps its meaning. k > 256: COR_ENOSUPPORT
+ * (cor_topk_workspace_bytes: COR_EINVAL). `flags` (per call, no process-global state):
  * 0 = default; COR_TOPK_FORCE_LISTS = per-lane sorted-list kernels only; COR_TOPK_NO_FALLBACK = report an overflow as index -2 in every
  * slot of the query instead of falling back (tests); COR_TOPK_FORCE_GLOBAL_THRESHOLD / COR_TOPK_WAVE_FINAL = A/B partners (tests). */
 long cor_topk_workspace_bytes(int Bq, int Ng, int k);
