@@ -16,6 +16,7 @@ ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TANH = 0, 1, 2, 3, 4
 EINVAL, ENOSUPPORT = -1, -2
 TOPK_FORCE_LISTS, TOPK_NO_FALLBACK, TOPK_FORCE_GLOBAL_THRESHOLD, TOPK_WAVE_FINAL = 1, 2, 8, 16
 TOPK_KMAX = 256    # largest k of cor_similarity_topk (COR_TOPK_KMAX)
+FILTER_EQ, FILTER_NE = 0, 1    # cor_similarity_topk_filtered modes (COR_FILTER_EQ / COR_FILTER_NE)
 ORDER_REVERSE = 1 << 30    # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
 KERNEL_ROWLANE, KERNEL_FEWQ, KERNEL_FLASH_MFMA, KERNEL_FLASH_PIPELINED, KERNEL_WINDOW_BLOCK = 1, 2, 3, 4, 5
 import numpy as _np
@@ -61,8 +62,10 @@ SIGNATURES = {
     "cor_mask_metrics": [_p, _p, _p, _i, _i, _f, _p],
     "cor_topk_workspace_bytes": [_i, _i, _i],
     "cor_similarity_topk": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p],
+    "cor_topk_filtered_workspace_bytes": [_i, _i, _i],
+    "cor_similarity_topk_filtered": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _i, _p, _p, _p, _i, _p],
 }
-_RESTYPE = {"cor_topk_workspace_bytes": _l}
+_RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l}
 
 _lib = None
 

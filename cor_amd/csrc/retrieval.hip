@@ -332,6 +332,7 @@ struct ScanArgs {
   int probe_same;                  // COR_PROBES (timing only): every block streams the same 8 super-tiles (cache-resident gallery)
   unsigned long long* stamps;      // COR_PROBES: cycle stamps of waves 0 and 4 of block 0 (tools/sim_stamps.py scan)
   float* tau; int* cnt; float* rec_s; int* rec_g; int cap;           // APPEND: tau_q (written by the blocks of slice 0 for the selection kernel); record i of stream (q, slice, lane quarter): 8 scores + first row
+  const int* rlab; const int* qlab; int ne;                           // FILTER: row / query labels, COR_FILTER_NE (filtered wide route only)
 };
 
 // One block = 8 waves = 256 * QB queries (wave w owns queries q0 + 32 * QB * w ..): with QB = 2 all 512 queries of an
@@ -355,10 +356,14 @@ __device__ __forceinline__ float key2f_floor(unsigned key) {      // the smalles
 
 // WIDE (33 <= k <= 256, see the wide-k route below): SAMPLE stores every (slice, lane quarter) group maximum on its own, sg[q * Bqp + split * 4 + rq]
 // with Bqp = the group count (no super-group folding: tau needs >= k groups); APPEND reads tau_q from a.tau (sim_tau_wide ranked the groups).
-template <typename TG, int QB, bool SAMPLE, bool WIDE = false>
+// FILTER (the filtered wide route, any k; implies WIDE): a disallowed score is -inf before every maximum and compare. Slice `split` walks the
+// super-tiles split, split + nsplit, ... (a class-sorted gallery spreads over every slice and stream), the labels of those rows are copied
+// into LDS once in the prologue (a 4-slot ring: the fifth slot holds them), SAMPLE keeps the FOUR best allowed scores per group
+// (sg[q * Bqp + (split * 4 + rq) * 4 + j]: a clustered subset still yields >= k values), and APPEND decides on the allow predicate.
+template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false>
 __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int C = 256, TILE = 32 * C * 2, STILE = 2 * TILE, NS = SCAN_NS, AHEAD = SCAN_AHEAD;
+  constexpr int C = 256, TILE = 32 * C * 2, STILE = 2 * TILE, NS = FILTER ? SCAN_NS - 1 : SCAN_NS, AHEAD = FILTER ? SCAN_AHEAD - 1 : SCAN_AHEAD;
   // Round 5: v_mfma_f32_16x16x32 instead of 32x32x16. A wave's 32 rows x 32 QB queries are 2 x NQ blocks of 16 x 16 = 2 NQ INDEPENDENT
   // accumulators of four registers (the 32 x 32 form had QB = 2 dependent chains: a wave alone issued an MFMA every ~43 cycles instead of 32),
   // and the chip holds a higher clock on this shape (MI355X guide, DVFS item 7): 512 x 1M 280-300 -> 185-200 us in the timing probe. Operand
@@ -386,12 +391,14 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   unsigned st_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) st_off[i] = (unsigned)(st_e * 512 + ((st_sl ^ ((8 * wave + 2 * i + st_e) & 15)) << 4));
-  const int t0 = split * a.tiles_per_split, t1 = min(t0 + a.tiles_per_split, a.ntiles);     // super-tiles of 64 rows
+  // super-tiles of 64 rows (FILTER: t counts the slice's walked super-tiles, super-tile split + t * nsplit)
+  const int t0 = FILTER ? 0 : split * a.tiles_per_split, t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
+  auto walked = [&](int t) { return FILTER ? split + t * a.nsplit : t; };
   auto issue = [&](int t) {
 #ifdef COR_PROBES
-    const long g0 = (long)((a.probe_same & 1) ? (t & 7) : t) * a.tile_stride * 64;
+    const long g0 = (long)((a.probe_same & 1) ? (walked(t) & 7) : walked(t)) * a.tile_stride * 64;
 #else
-    const long g0 = (long)t * a.tile_stride * 64;
+    const long g0 = (long)walked(t) * a.tile_stride * 64;
 #endif
     const unsigned dst = lds0 + ((t - t0) % NS) * STILE + wbase;
     if (g0 + 64 <= a.Ng) {                             // (scalar) every row of the super-tile is inside the shard
@@ -417,7 +424,21 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   // bitonic network in registers (the K-fragments are not loaded yet), tau_q = k-th largest - delta_q (fewer than k non-empty super-groups:
   // -inf, every row is a candidate). Any lower bound of the k-th best score is valid, so 32 unions of the (slice, lane quarter) groups serve
   // as well as the 512 groups the launch ranked (~15 % more candidates).
-  float* tau_s = (float*)(smem + (SCAN_NS - 1) * 2 * 32 * 256 * 2);   // in the LAST ring slot: first written by the copies behind the loop's first barrier
+  float* tau_s = (float*)(smem + (NS - 1) * STILE);   // in the LAST ring slot: first written by the copies behind the loop's first barrier
+  // FILTER: the labels of the rows this slice walks, lab_s[(t - t0) * 64 + row of the super-tile], behind the 4-slot ring (<= 128 super-tiles:
+  // make_wide keeps tiles_per_split below that); rows past the shard read label 0 (their scores are -inf anyway)
+  const int* lab_s = (const int*)(smem + NS * STILE);
+  if constexpr (FILTER) {
+    int* lab_w = (int*)(smem + NS * STILE);
+    for (int i = tid; i < (t1 - t0) * 16; i += 512) {
+      const long row = (long)walked(t0 + (i >> 4)) * a.tile_stride * 64 + 4 * (i & 15);
+      int4 v;
+      if (row + 4 <= a.Ng) v = *(const int4*)(a.rlab + row);
+      else { v.x = row < a.Ng ? a.rlab[row] : 0; v.y = row + 1 < a.Ng ? a.rlab[row + 1] : 0; v.z = row + 2 < a.Ng ? a.rlab[row + 2] : 0; v.w = 0; }
+      *(int4*)(lab_w + 4 * i) = v;
+    }
+    __syncthreads();
+  }
   if (!SAMPLE && WIDE) {
     if (tid < 256 * QB) tau_s[tid] = a.tau[min(qg * (256 * QB) + tid, a.Bq - 1)];
     __syncthreads();
@@ -453,6 +474,8 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   uint4 qf[NQ][8];
   float tau[NQ], gmax[NQ];
   int ncand[NQ];
+  int ql[NQ];                                          // FILTER: the lane's query labels (< 0: unrestricted)
+  float top4[NQ][4];                                   // FILTER SAMPLE: the group's four best allowed scores, descending
   const int nstreams = a.nsplit * 4;                   // a stream = (query, gallery slice, lane quarter rq)
 #pragma unroll
   for (int qb = 0; qb < NQ; ++qb) {
@@ -463,6 +486,11 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
     for (int kk = 0; kk < 8; ++kk) qf[qb][kk] = active ? qimg[kk * 64] : make_uint4(0, 0, 0, 0);
     tau[qb] = SAMPLE ? 0.f : tau_s[wave * (32 * QB) + qb * 16 + n16] + a.tau_add;
     gmax[qb] = -INFINITY; ncand[qb] = 0;
+    if constexpr (FILTER) {
+      ql[qb] = a.qlab[min(q0 + qb * 16 + n16, a.Bq - 1)];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) top4[qb][j] = -INFINITY;
+    }
   }
   // read address of 32-deep K-step kk, row block rb: row rb * 16 + n16, chunk (4 kk + rq) ^ n16 = ((kk ^ (n16 >> 2)) << 2) | (rq ^ (n16 & 3)): one XOR
   // per read. Conflict-free ds_read_b128: every 16-lane service group holds 16 different n16 (the two K quarters it mixes map onto disjoint slots).
@@ -473,8 +501,16 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   // epilogue of one 32-row tile (rows g0 ..): SAMPLE keeps the group maximum; APPEND compares the tile maximum with tau and
   // appends the rare scores >= tau to the lane's private stream list
   const int r4 = 4 * rq;
-  auto epilogue = [&](int g0) {
+  auto epilogue = [&](int g0, int lo) {               // lo: FILTER, the tile's first row in lab_s
     const int lim = a.Ng - g0;                         // rows of this tile inside the shard (scalar); < 32 only at the shard's end
+    int lr[2][4];                                      // FILTER: labels of the lane's 8 rows (16 rb + 4 rq + e)
+    if constexpr (FILTER) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) {
+        const int4 v = *(const int4*)(lab_s + lo + 16 * rb + r4);
+        lr[rb][0] = v.x; lr[rb][1] = v.y; lr[rb][2] = v.z; lr[rb][3] = v.w;
+      }
+    }
 #pragma unroll
     for (int qb = 0; qb < NQ; ++qb) {
       if (lim < 32) {
@@ -484,12 +520,48 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
           for (int e = 0; e < 4; ++e)
             if (16 * rb + r4 + e >= lim) acc[qb][rb][e] = -INFINITY;                 // clamped duplicate rows never count
       }
+      bool ok = false;                                 // FILTER: some row of the lane's 8 is inside the shard and allowed
+      if constexpr (FILTER) {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool allow = (ql[qb] < 0 || ((lr[rb][e] == ql[qb]) != (a.ne != 0))) && (lim >= 32 || 16 * rb + r4 + e < lim);
+            acc[qb][rb][e] = allow ? acc[qb][rb][e] : -INFINITY;
+            ok = ok || allow;
+          }
+      }
       float tmax = max3f(acc[qb][0][0], acc[qb][0][1], acc[qb][0][2]);
       tmax = max3f(tmax, acc[qb][0][3], acc[qb][1][0]);
       tmax = max3f(tmax, acc[qb][1][1], acc[qb][1][2]);
       tmax = fmaxf(tmax, acc[qb][1][3]);
-      if (SAMPLE) {
+      if (SAMPLE && FILTER) {                          // insertion of each allowed score into the sorted four (-inf: no change)
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float x = acc[qb][rb][e];
+            top4[qb][3] = fmaxf(top4[qb][3], fminf(top4[qb][2], x));
+            top4[qb][2] = fmaxf(top4[qb][2], fminf(top4[qb][1], x));
+            top4[qb][1] = fmaxf(top4[qb][1], fminf(top4[qb][0], x));
+            top4[qb][0] = fmaxf(top4[qb][0], x);
+          }
+      } else if (SAMPLE) {
         gmax[qb] = fmaxf(gmax[qb], tmax);
+      } else if (FILTER) {                             // the allow predicate decides (tau_q = -inf admits every ALLOWED row, never a masked one)
+        if (__builtin_amdgcn_ballot_w64(ok && tmax >= tau[qb]) != 0) {
+          int q = q0 + qb * 16 + n16;
+          asm volatile("" : "+v"(q));
+          if (ok && tmax >= tau[qb] && q < a.Bq) {
+            if (ncand[qb] < a.cap) {
+              const long rec = ((long)q * nstreams + split * 4 + rq) * a.cap + ncand[qb];
+              f32x4* dst = (f32x4*)(a.rec_s + rec * 8);
+              dst[0] = acc[qb][0]; dst[1] = acc[qb][1];  // masked slots are -inf: sim_final_wide skips them
+              a.rec_g[rec] = g0;
+            }
+            ++ncand[qb];
+          }
+        }
       } else if (__builtin_amdgcn_ballot_w64(tmax >= tau[qb]) != 0) {
         // Some lane of the wave has a candidate in this tile. Testing the registers one by one cost ~80 instructions per triggered tile
         // (70 us of a 270-us scan in round 2); instead a lane whose tile maximum passes appends its WHOLE 8-score column as one record
@@ -532,7 +604,7 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   // (s_setprio 1 for the younger half - waves 4-7 - before the loop, the guide's static-priority item, and a sample stride of 32 instead of 16
   // at 1M rows: no difference in a same-box A/B on the round-4 kernel. Round 5, measured with cycle stamps: priority 2 for the younger half
   // during its FIRST tile only balances the two halves, below.)
-  int g_pending = -1;                                  // late waves: tile whose epilogue is still owed
+  int g_pending = -1, lo_pending = 0;                  // late waves: tile whose epilogue is still owed
 #ifdef COR_PROBES
 #define SC_STAMP(i_) do { if (!SAMPLE && a.stamps && blockIdx.x == 0 && (tid & 255) == 0 && t - t0 < 24) { __builtin_amdgcn_sched_barrier(0); \
     a.stamps[((tid >> 8) * 24 + (t - t0)) * 8 + (i_)] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } } while (0)
@@ -561,30 +633,32 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
 #endif
     SC_STAMP(2);
     const char* buf = smem + ((t - t0) % NS) * STILE;
-    const int g0 = t * a.tile_stride * 64;
+    const int g0 = walked(t) * a.tile_stride * 64, lo = (t - t0) * 64;
     if (active) {
-      if (late && g_pending >= 0) epilogue(g_pending);
+      if (late && g_pending >= 0) epilogue(g_pending, lo_pending);
       SC_STAMP(3);
       if (late) __builtin_amdgcn_s_setprio(2);
       mfma_tile(buf);
       if (late) __builtin_amdgcn_s_setprio(0);
       SC_STAMP(4);
-      epilogue(g0);
+      epilogue(g0, lo);
       SC_STAMP(5);
       mfma_tile(buf + TILE);
       SC_STAMP(6);
-      if (late) g_pending = g0 + 32; else epilogue(g0 + 32);
+      if (late) { g_pending = g0 + 32; lo_pending = lo + 32; } else epilogue(g0 + 32, lo + 32);
       SC_STAMP(7);
     }
   }
-  if (active && late && g_pending >= 0) epilogue(g_pending);
+  if (active && late && g_pending >= 0) epilogue(g_pending, lo_pending);
 #undef SIM_RD
   if (active) {
 #pragma unroll
     for (int qb = 0; qb < NQ; ++qb) {
       const int q = q0 + qb * 16 + n16;
       if (q < a.Bq) {
-        if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
+        if (SAMPLE && FILTER)
+          *(uint4*)(a.sg + (long)q * a.Bqp + (split * 4 + rq) * 4) = make_uint4(f2key(top4[qb][0]), f2key(top4[qb][1]), f2key(top4[qb][2]), f2key(top4[qb][3]));
+        else if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
         else if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
         else a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb];
       }
@@ -1755,24 +1829,39 @@ __device__ __forceinline__ float chain_score_c(const TG* __restrict__ G, long id
 // block_kth_key (four passes, every row re-scored per pass), then one more pass collects the rows above it (fewer than k, any order)
 // and the first k_rem rows EQUAL to it in index order (a block-wide prefix count per 256 rows), and a bitonic sort ranks them.
 // Five chain passes over the shard: slow, exact, rare (DESIGN 3.4 gives the measured cost).
-template <typename TG>
+// FILTER: only the rows allowed for the query (label ql, COR_FILTER_NE if ne) are ranked: a disallowed row has key 0, below every score's
+// key, and a query with nA <= k allowed rows gets all of them followed by the (-inf, -1) tail.
+template <typename TG, bool FILTER = false>
 __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float* sl_s, int* sl_i,
-                                 unsigned long long* keys, int* hist, float* out_s, long long* out_i) {
+                                 unsigned long long* keys, int* hist, float* out_s, long long* out_i, const int* rlab = nullptr, int ql = -1,
+                                 int ne = 0) {
   __shared__ int sel_bin, k_rem, n_above, wcnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kk = min(k, Ng);
-  auto key_at = [&](int g) { return f2key(chain_score_c<TG>(G, g, C, qs)); };
-  unsigned kth = 0u;                                   // Ng <= k: every row is above "key 0"
+  auto allowed = [&](int g) { return !FILTER || ql < 0 || ((rlab[g] == ql) != (ne != 0)); };
+  int nA = Ng;                                         // rows that may be ranked (block-uniform)
+  if constexpr (FILTER) {
+    __shared__ int n_allowed;
+    if (tid == 0) n_allowed = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int g = tid; g < Ng; g += 256) mine += allowed(g) ? 1 : 0;
+    atomicAdd(&n_allowed, mine);
+    __syncthreads();
+    nA = n_allowed;
+  }
+  const int kk = min(k, nA);
+  auto key_at = [&](int g) { return allowed(g) ? f2key(chain_score_c<TG>(G, g, C, qs)) : 0u; };
+  unsigned kth = 0u;                                   // nA <= k: every allowed row is above "key 0"
   int above = kk, need = 0;
-  if (Ng > k) { kth = block_kth_key(key_at, Ng, k, hist, &sel_bin, &k_rem); need = k_rem; above = k - need; }
+  if (nA > k) { kth = block_kth_key(key_at, Ng, k, hist, &sel_bin, &k_rem); need = k_rem; above = k - need; }
   if (tid == 0) n_above = 0;
   __syncthreads();
   int taken = 0;                                       // rows equal to kth already collected (block-uniform)
   for (int g0 = 0; g0 < Ng; g0 += 256) {
     const int g = g0 + tid;
     float s = -INFINITY; unsigned key = 0u;
-    if (g < Ng) { s = chain_score_c<TG>(G, g, C, qs); key = f2key(s); }
-    const bool up = g < Ng && key > kth, tie = g < Ng && key == kth && Ng > k;
+    if (g < Ng && allowed(g)) { s = chain_score_c<TG>(G, g, C, qs); key = f2key(s); }
+    const bool up = g < Ng && key > kth, tie = g < Ng && key == kth && nA > k;
     if (up) { const int p = atomicAdd(&n_above, 1); sl_s[p] = s; sl_i[p] = g; }
     const unsigned long long b = __builtin_amdgcn_ballot_w64(tie);
     if (lane == 0) wcnt[wave] = __builtin_popcountll(b);
@@ -1801,12 +1890,15 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
 // with the epilogues of the wide route. One wave = 32 queries x a slice of 32-row tiles; lane (r, h) holds 16 scores of query r per tile.
 //   SAMPLE: tiles t * tile_stride of the slice; the group (slice, lane half h) keeps its maximum: sg[q * ngroups + split * 2 + h].
 //   APPEND: every tile of the slice; scores >= tau_q go to the private list of stream (q, slice, h) as (score bits, row) entries.
+//   FILTER: disallowed scores are -inf (never a group's best, never >= tau_q), slice `split` walks the tiles split, split + nsplit, ... and
+//   SAMPLE keeps the group's four best allowed scores, sg[q * ngroups + (split * 2 + h) * 4 + j] (ngroups counts the four), as sim_scan does.
 struct WideScanArgs {
   int Bq, Ng, C, nqt, nsplit, tiles_per_split, ntiles, tile_stride;
   unsigned* sg; int ngroups;
   const float* tau; int* cnt; uint2* lst; int cap;
+  const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
 };
-template <typename TG, bool SAMPLE>
+template <typename TG, bool SAMPLE, bool FILTER = false>
 __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q, const TG* __restrict__ G, const WideScanArgs a) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1832,9 +1924,11 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
   const int stream = split * 2 + h, nstreams = 2 * a.nsplit;
   float gmax = -INFINITY;
   int n = 0;
-  const int t0 = split * a.tiles_per_split, t1 = min(t0 + a.tiles_per_split, a.ntiles);
+  const int ql = FILTER ? a.qlab[min(q, a.Bq - 1)] : 0;
+  float top4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  const int t0 = FILTER ? 0 : split * a.tiles_per_split, t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
   for (int t = t0; t < t1; ++t) {
-    const int g0 = t * a.tile_stride * 32;
+    const int g0 = (FILTER ? split + t * a.nsplit : t) * a.tile_stride * 32;
     const char* grow = (const char*)(G + (long)min(g0 + r, Ng - 1) * C) + 16 * h;
     f32x16 acc;
 #pragma unroll
@@ -1861,7 +1955,31 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       sc[e] = g0 + (e & 3) + 8 * (e >> 2) + 4 * h < Ng ? acc[e] : -INFINITY;
       tmax = fmaxf(tmax, sc[e]);
     }
-    if (SAMPLE) {
+    if constexpr (FILTER) {                            // labels of rows g0 + 8 j + 4 h + i (score e = 4 j + i)
+      tmax = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = g0 + 8 * j + 4 * h;
+        int4 l;
+        if (row + 4 <= Ng) l = *(const int4*)(a.rlab + row);
+        else { l.x = row < Ng ? a.rlab[row] : 0; l.y = row + 1 < Ng ? a.rlab[row + 1] : 0; l.z = row + 2 < Ng ? a.rlab[row + 2] : 0; l.w = 0; }
+        const int lv[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (!(ql < 0 || ((lv[i] == ql) != (a.ne != 0)))) sc[4 * j + i] = -INFINITY;
+          tmax = fmaxf(tmax, sc[4 * j + i]);
+        }
+      }
+    }
+    if (SAMPLE && FILTER) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        top4[3] = fmaxf(top4[3], fminf(top4[2], sc[e]));
+        top4[2] = fmaxf(top4[2], fminf(top4[1], sc[e]));
+        top4[1] = fmaxf(top4[1], fminf(top4[0], sc[e]));
+        top4[0] = fmaxf(top4[0], sc[e]);
+      }
+    } else if (SAMPLE) {
       gmax = fmaxf(gmax, tmax);
     } else if (__builtin_amdgcn_ballot_w64(tmax >= tq) != 0) {
       uint2* dst = a.lst + ((long)q * nstreams + stream) * a.cap;
@@ -1875,7 +1993,8 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
     }
   }
   if (q < a.Bq) {
-    if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
+    if (SAMPLE && FILTER) *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[0]), f2key(top4[1]), f2key(top4[2]), f2key(top4[3]));
+    else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
     else a.cnt[(long)q * nstreams + stream] = n;
   }
 }
@@ -1905,12 +2024,14 @@ __global__ void __launch_bounds__(256) sim_tau_wide(const float* __restrict__ Q,
 
 // Exact selection of the wide route, one block of 256 threads per query. RECORDS: the 8-score records of sim_scan<APPEND> (rec_s /
 // rec_g, the scores >= tau_q are kept); otherwise the (score, row) entry lists of sim_wide_scan<APPEND> (lst). fp32 galleries: the scan
-// scores are the chain, nothing is re-scored and delta = 0.
-template <typename TG, bool RECORDS>
+// scores are the chain, nothing is re-scored and delta = 0. FILTER: the scans stored allowed scores only (masked record slots are -inf and
+// skipped); an overflowed query's brute force ranks its allowed rows (row labels rlab, query labels qlab, ne = COR_FILTER_NE).
+template <typename TG, bool RECORDS, bool FILTER = false>
 __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C, int k, long long g_offset,
                                                       const float* __restrict__ tau, const int* __restrict__ cnt, int nstreams, int cap,
                                                       const float* __restrict__ rec_s, const int* __restrict__ rec_g, const uint2* __restrict__ lst,
-                                                      float* out_s, long long* out_i, int no_fallback) {
+                                                      float* out_s, long long* out_i, int no_fallback, const int* __restrict__ rlab,
+                                                      const int* __restrict__ qlab, int ne) {
   extern __shared__ __attribute__((aligned(16))) char fwraw[];
   float* cs = (float*)fwraw; int* ci = (int*)(cs + FSW);
   float* sl_s = (float*)(ci + FSW); int* sl_i = (int*)(sl_s + SLW);
@@ -1986,7 +2107,10 @@ __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ 
       for (int j = tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -2LL; }
       return;
     }
-    wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
+    if constexpr (FILTER)
+      wide_brute_force<TG, true>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k, rlab, qlab[q], ne);
+    else
+      wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
     return;
   }
   const int m = nsl;
@@ -2007,6 +2131,8 @@ __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ 
 }
 
 // plan of the wide route (host; shared by the launcher and cor_topk_workspace_bytes). scan = the sim_scan form (16-bit, C = 256).
+// filter = the filtered route (any k): four sample values per group; the scan form's slices walk <= 128 super-tiles (their labels fill
+// the 32 KiB behind sim_scan's 4-slot ring).
 struct WidePlan {
   bool scan;
   int qb, nqg, nqt;                  // scan form: query blocks per wave, query groups of 256 * qb; tile form: 32-query tiles
@@ -2014,7 +2140,7 @@ struct WidePlan {
   int s_stride, s_tiles, s_nsplit, s_tiles_per_split, ngroups;       // SAMPLE (ngroups == 0: no sample, tau = -inf)
   size_t off_img, off_sg, off_dq, off_tau, off_flags, off_ovf, off_cnt, off_recs, off_recg, bytes;
 };
-inline WidePlan make_wide(int Bq, int Ng, int k, bool scan) {
+inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false) {
   WidePlan p{};
   p.scan = scan;
   const int rows = scan ? 64 : 32;                     // rows per tile of the scan kernel
@@ -2032,6 +2158,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan) {
   if (want > p.ntiles) want = p.ntiles;
   if (want < 1) want = 1;
   p.tiles_per_split = cdiv(p.ntiles, want);
+  if (filter && scan && p.tiles_per_split > 128) p.tiles_per_split = 128;
   p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
   const int per_tile = scan ? 4 : 2;                   // streams per slice: lane quarters (scan) / lane halves (tiles)
   p.nstreams = per_tile * p.nsplit;
@@ -2051,8 +2178,9 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan) {
     int sw = scan ? 256 : 512;
     if (sw > p.s_tiles) sw = p.s_tiles;
     p.s_tiles_per_split = cdiv(p.s_tiles, sw);
+    if (filter && scan && p.s_tiles_per_split > 128) p.s_tiles_per_split = 128;
     p.s_nsplit = cdiv(p.s_tiles, p.s_tiles_per_split);
-    p.ngroups = per_tile * p.s_nsplit;
+    p.ngroups = per_tile * p.s_nsplit * (filter ? 4 : 1);
     const long expect = 3L * k * p.s_stride;           // candidates per query, ~2x slack
     // per stream: Poisson with mean ~ expect / nstreams; +10 keeps P(overflow) per search small
     p.cap = (int)(2 * expect / p.nstreams) + 10;
@@ -2075,14 +2203,15 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan) {
   return p;
 }
 
-template <typename TG, int QB>
+// FILTER: the filtered route (rlab / qlab / ne: cor_similarity_topk_filtered's labels and mode)
+template <typename TG, int QB, bool FILTER = false>
 int launch_wide_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long long g_offset, float* out_s, long long* out_i, char* w,
-                     const WidePlan& p, int flags, hipStream_t s) {
+                     const WidePlan& p, int flags, hipStream_t s, const int* rlab = nullptr, const int* qlab = nullptr, int ne = 0) {
   constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
   static DevOnce once_s, once_a, once_f;
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true>, (int)lds, once_s);
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true>, (int)lds, once_a);
-  cor_max_dyn_lds((const void*)sim_final_wide<TG, true>, (int)FINAL_WIDE_LDS, once_f);
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER>, (int)lds, once_s);
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER>, (int)lds, once_a);
+  cor_max_dyn_lds((const void*)sim_final_wide<TG, true, FILTER>, (int)FINAL_WIDE_LDS, once_f);
   unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
   int* cnt = (int*)(w + p.off_cnt); float* rec_s = (float*)(w + p.off_recs); int* rec_g = (int*)(w + p.off_recg);
   uint4* qimg = (uint4*)(w + p.off_img);
@@ -2092,45 +2221,47 @@ int launch_wide_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long lo
   COR_CHECK_LAUNCH();
   ScanArgs a{};
   a.Bq = Bq; a.Ng = Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups;
+  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_scan<TG, QB, true, true>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
+    hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
     COR_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, 256, sg, p.ngroups, k, tau);
   COR_CHECK_LAUNCH();
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.k = k; a.tau = tau; a.cnt = cnt; a.rec_s = rec_s; a.rec_g = rec_g; a.cap = p.cap; a.tau_add = 0.f;
-  hipLaunchKernelGGL((sim_scan<TG, QB, false, true>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
+  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
   COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_wide<TG, true>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     rec_s, rec_g, nullptr, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0);
+  hipLaunchKernelGGL((sim_final_wide<TG, true, FILTER>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     rec_s, rec_g, nullptr, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
   COR_CHECK_LAUNCH();
   return 0;
 }
 
-template <typename TG>
+template <typename TG, bool FILTER = false>
 int launch_wide_tiles(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i, char* w,
-                      const WidePlan& p, int flags, hipStream_t s) {
+                      const WidePlan& p, int flags, hipStream_t s, const int* rlab = nullptr, const int* qlab = nullptr, int ne = 0) {
   static DevOnce once_f;
-  cor_max_dyn_lds((const void*)sim_final_wide<TG, false>, (int)FINAL_WIDE_LDS, once_f);
+  cor_max_dyn_lds((const void*)sim_final_wide<TG, false, FILTER>, (int)FINAL_WIDE_LDS, once_f);
   unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
   int* cnt = (int*)(w + p.off_cnt); uint2* lst = (uint2*)(w + p.off_recs);
   WideScanArgs a{};
   a.Bq = Bq; a.Ng = Ng; a.C = C; a.nqt = p.nqt; a.sg = sg; a.ngroups = p.ngroups;
+  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_wide_scan<TG, true>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
+    hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
     COR_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, C, sg, p.ngroups, k, tau);
   COR_CHECK_LAUNCH();
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.tau = tau; a.cnt = cnt; a.lst = lst; a.cap = p.cap;
-  hipLaunchKernelGGL((sim_wide_scan<TG, false>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
+  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
   COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_wide<TG, false>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     nullptr, nullptr, lst, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0);
+  hipLaunchKernelGGL((sim_final_wide<TG, false, FILTER>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     nullptr, nullptr, lst, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
   COR_CHECK_LAUNCH();
   return 0;
 }
@@ -2146,6 +2277,20 @@ int launch_wide(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long 
     }
   }
   return launch_wide_tiles<TG>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false), flags, s);
+}
+
+// the filtered route: every k (1 .. COR_TOPK_KMAX) on the wide route's kernels with FILTER set
+template <typename TG>
+int launch_filtered(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* rlab, const int* qlab, int ne,
+                    float* out_s, long long* out_i, char* w, int flags, hipStream_t s) {
+  if constexpr (sizeof(TG) == 2) {
+    if (C == 256) {
+      const WidePlan p = make_wide(Bq, Ng, k, true, true);
+      if (p.qb == 2) return launch_wide_scan<TG, 2, true>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
+      return launch_wide_scan<TG, 1, true>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
+    }
+  }
+  return launch_wide_tiles<TG, true>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false, true), flags, s, rlab, qlab, ne);
 }
 
 template <typename TG>
@@ -2204,6 +2349,31 @@ extern "C" int cor_similarity_topk(const float* Q, const void* G, int g_dtype, i
     case COR_F32: return launch_topk<float>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
     case COR_BF16: return launch_topk<bf16_t>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
     case COR_F16: return launch_topk<_Float16>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
+    default: return COR_ENOSUPPORT;
+  }
+}
+
+extern "C" long cor_topk_filtered_workspace_bytes(int Bq, int Ng, int k) {
+  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
+  const long a = (long)make_wide(Bq, Ng, k, true, true).bytes, b = (long)make_wide(Bq, Ng, k, false, true).bytes;
+  return a > b ? a : b;
+}
+
+extern "C" int cor_similarity_topk_filtered(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
+                                            const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
+                                            long long* out_idx, void* workspace, int flags, void* stream) {
+  if (!Q || !G || !row_labels || !query_labels || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
+  if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
+  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
+  if (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL)) return COR_ENOSUPPORT;     // filtered calls always take the wide route
+  if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)row_labels & 15) || ((uintptr_t)workspace & 255)) return COR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int ne = filter_mode == COR_FILTER_NE ? 1 : 0;
+  char* w = (char*)workspace;
+  switch (g_dtype) {
+    case COR_F32: return launch_filtered<float>(Q, (const float*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
+    case COR_BF16: return launch_filtered<bf16_t>(Q, (const bf16_t*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
+    case COR_F16: return launch_filtered<_Float16>(Q, (const _Float16*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
     default: return COR_ENOSUPPORT;
   }
 }

@@ -138,6 +138,19 @@ class _DeviceLoader:
             yield self.collate(samples)
 
 
+def gallery_labels(csv_path, column="Target"):
+    """One int32 label per gallery row, for the rows gallery_batches yields and in its order (read_pairs_csv): ids of the names in
+    `column` by first appearance. Returns (labels int32[n], names) with names[label] the column value. column="Target" (the object
+    class) or "Dataset" restrict a filtered search with mode "eq"; column="Query_img" gives image ids, to exclude a query's own image
+    with mode "ne"."""
+    import pandas as pd
+    df = read_pairs_csv(csv_path)
+    if column not in df.columns:
+        raise ValueError(f"gallery_labels: no column {column!r} in {csv_path}")
+    codes, names = pd.factorize(df[column], sort=False)
+    return torch.from_numpy(np.asarray(codes, dtype=np.int32)), list(names)
+
+
 def gallery_batches(csv_path, dataset_path, batch_size=8, device="cuda", num_workers=0):
     """Offline gallery builder input: yields {"query_img", "query_mask"} device batches for
     cor_amd.retrieval.build_gallery from the same CSV schema (one gallery row per CSV pair: query image + query mask)."""

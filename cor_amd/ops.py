@@ -457,6 +457,51 @@ def similarity_topk(Q, G, k, g_offset=0, flags=0):
     return scores, idx
 
 
+_FILTER_MODES = {"eq": nat.FILTER_EQ, "ne": nat.FILTER_NE}
+
+
+def _labels(t, n, name, device):
+    t = torch.as_tensor(t)
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError(f"similarity_topk_filtered: {name} must be a vector of {n} labels, got shape {tuple(t.shape)}")
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"similarity_topk_filtered: {name} must be int32 (int64 is converted), got {t.dtype}")
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    if t.data_ptr() % 16:                                     # the kernels read row labels 16 B at a time (a view into a larger tensor)
+        t = t.clone()
+    return t
+
+
+def similarity_topk_filtered(Q, G, k, row_labels, query_labels, mode="eq", g_offset=0, flags=0):
+    """similarity_topk over the ALLOWED rows only: row g is allowed for query b if query_labels[b] < 0 (unrestricted) or, for
+    mode "eq", row_labels[g] == query_labels[b] (restrict to a class / subset), for mode "ne", row_labels[g] != query_labels[b]
+    (exclude a source, e.g. the query's own image). row_labels int32[Ng], query_labels int32[Bq] (int64 is converted). 1 <= k <= 256
+    for every gallery dtype and C; bit-identical to the chain oracle on the allowed rows; fewer than k allowed rows: the tail is
+    (-inf, -1). No host synchronisation when the labels already live on the device. flags: nat.TOPK_NO_FALLBACK (tests)."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"similarity_topk_filtered: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if mode not in _FILTER_MODES:
+        raise ValueError(f"similarity_topk_filtered: mode must be 'eq' or 'ne', got {mode!r}")
+    _dev(Q, G)
+    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
+    Bq, Cq = Q.shape
+    Ng, Cg = G.shape
+    assert Cq == Cg
+    rl = _labels(row_labels, Ng, "row_labels", Q.device)
+    qlab = _labels(query_labels, Bq, "query_labels", Q.device)
+    lib = _lib()
+    nbytes = lib.cor_topk_filtered_workspace_bytes(Bq, Ng, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_topk_filtered_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)
+    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
+    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
+    nat.check(lib.cor_similarity_topk_filtered(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), rl.data_ptr(),
+                                               qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                               int(flags), _s()), "cor_similarity_topk_filtered")
+    return scores, idx
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

@@ -66,25 +66,40 @@ def recall_at_k(idx, positives, ks=(1, 5, 10, 50, 100)) -> dict:
 
 
 class GalleryShard:
-    """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16."""
+    """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16. labels: optional int32[n], one label
+    per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches."""
 
-    def __init__(self, rows: torch.Tensor, offset: int = 0, dtype: torch.dtype | None = None):
+    def __init__(self, rows: torch.Tensor, offset: int = 0, dtype: torch.dtype | None = None, labels=None):
         if not rows.is_cuda:
             raise RuntimeError("GalleryShard lives in GPU memory (no CPU path)")
         self.rows = rows.to(dtype or rows.dtype).contiguous()
         self.offset = int(offset)
+        self.labels = None
+        if labels is not None:
+            labels = torch.as_tensor(labels)
+            if labels.dim() != 1 or labels.shape[0] != self.rows.shape[0]:
+                raise ValueError(f"GalleryShard: {tuple(labels.shape)} labels for {self.rows.shape[0]} rows")
+            self.labels = labels.to(self.rows.device, torch.int32).contiguous()
 
     def __len__(self):
         return self.rows.shape[0]
 
-    def search(self, queries: torch.Tensor, k: int):
-        """queries f32[Bq,C] (unit-norm) -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU; 1 <= k <= 256."""
+    def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq"):
+        """queries f32[Bq,C] (unit-norm) -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU; 1 <= k <= 256.
+        query_labels (int32[Bq], < 0 = unrestricted): only the rows allowed by the shard's labels and `mode` ("eq": same label, "ne":
+        another label) are ranked (ops.similarity_topk_filtered); None: the whole shard."""
         q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        if query_labels is not None:
+            if self.labels is None:
+                raise ValueError("GalleryShard.search: query_labels given but the shard has no row labels")
+            query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
         if self.rows.shape[0] == 0:                  # an empty shard (more ranks than gallery rows): all-missing lists, like Ng < k
             return (torch.full((q.shape[0], k), float("-inf"), device=q.device),
                     torch.full((q.shape[0], k), -1, dtype=torch.int64, device=q.device))
         with torch.cuda.device(self.rows.device):
-            return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
+            if query_labels is None:
+                return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
+            return ops.similarity_topk_filtered(q, self.rows, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):
@@ -165,7 +180,8 @@ def _to_host_async(t: torch.Tensor):
 
 
 def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int, group=None, max_local: int | None = None,
-                       dst: int | None = 0, timing: list | None = None, always_collective: bool = False, defer: bool = False):
+                       dst: int | None = 0, timing: list | None = None, always_collective: bool = False, defer: bool = False,
+                       query_labels=None, filter_mode: str = "eq"):
     """All ranks call this with their own queries [B_local, C] and their gallery shard.
 
     Two collectives in all, as BASELINE.json's north_star describes it:
@@ -188,10 +204,16 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     defer: return a PendingSearch instead of the tensors: the device-to-host copy is enqueued (pinned memory + event) and the host merge
     happens in its result() - call it after enqueuing the next step's forward, so that the GPU does not idle through the host's turn.
     Returns (scores f32[B_total,k], idx i64[B_total,k]) CPU tensors, queries ordered by rank, on rank `dst` (every rank
-    for dst=None); (None, None) on the other ranks. k: 1 .. 256 (recall_at_k turns the lists into Recall@K)."""
+    for dst=None); (None, None) on the other ranks. k: 1 .. 256 (recall_at_k turns the lists into Recall@K).
+    query_labels: int32[B_local] (< 0 = unrestricted), best on the queries' device: a filtered search (GalleryShard.search with
+    filter_mode "eq" / "ne" over each shard's row labels). The labels travel bit-cast in one extra column of the same fixed-size
+    all-gather block, so the call keeps its two collectives; None leaves the payload and the call shard.search(q, k) as they were."""
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
-        s, i = shard.search(local_queries, k)
+        if query_labels is None:
+            s, i = shard.search(local_queries, k)
+        else:
+            s, i = shard.search(local_queries, k, query_labels=query_labels, mode=filter_mode)
         if defer:
             both, ev = _to_host_async(_pack_lists(s, i))         # one copy instead of two
             return PendingSearch(lambda: _unpack_lists(both), ev)
@@ -205,19 +227,29 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     dev = shard.rows.device
     host_coll = dist.get_backend(group) == "gloo"               # CPU rehearsal backend: collectives on host copies
     cdev = torch.device("cpu") if host_coll else dev
-    block = torch.zeros((cap + 1, C), dtype=torch.float32, device=cdev)
-    block[:b_local] = q.to(cdev)
+    width = C if query_labels is None else C + 1                  # filtered: column C carries each query's label (int32 bits)
+    block = torch.zeros((cap + 1, width), dtype=torch.float32, device=cdev)
+    block[:b_local, :C] = q.to(cdev)
+    if query_labels is not None:
+        ql = torch.as_tensor(query_labels).reshape(-1)
+        if ql.shape[0] != b_local:
+            raise ValueError(f"distributed_search: {ql.shape[0]} query labels for {b_local} local queries")
+        block[:b_local, C] = ql.to(cdev, torch.int32).view(torch.float32)
     block[cap, :1].fill_(float(b_local))                         # (a fill kernel; `block[cap, 0] = x` copies a host scalar: the host would wait for the stream)
-    allb = torch.empty((world * (cap + 1), C), dtype=torch.float32, device=cdev)
+    allb = torch.empty((world * (cap + 1), width), dtype=torch.float32, device=cdev)
     marks = _Marks(dev, host_coll) if timing is not None else None
     if marks:
         marks.mark()
     dist.all_gather_into_tensor(allb, block, group=group)        # collective 1 (RCCL over xGMI)
     if marks:
         marks.mark()
-    allb = allb.view(world, cap + 1, C)
-    slots = allb[:, :cap].reshape(world * cap, C).to(dev)        # every slot is scored; counts stay where they are
-    s, i = shard.search(slots, k)                                # local shard vs ALL query slots
+    allb = allb.view(world, cap + 1, width)
+    slots = allb[:, :cap, :C].reshape(world * cap, C).to(dev)    # every slot is scored; counts stay where they are
+    if query_labels is None:
+        s, i = shard.search(slots, k)                            # local shard vs ALL query slots
+    else:
+        slot_labels = allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
+        s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode)
     packed = _pack_lists(s, i).to(cdev)
     if marks:
         marks.mark()
@@ -278,21 +310,31 @@ def build_gallery(model, batches, dtype=torch.float16):
     return torch.cat(rows, dim=0)
 
 
-def save_gallery(path, rows, world=1):
-    """On-disk format: <path>.shardNN.pt (rows of shard NN as a tensor) + <path>.manifest.json (row ranges)."""
+def save_gallery(path, rows, world=1, labels=None):
+    """On-disk format: <path>.shardNN.pt (rows of shard NN as a tensor) + <path>.manifest.json (row ranges). labels (int32[n], one
+    per row): also <path>.shardNN.labels.pt per shard and "labels": true in the manifest."""
     import json
     n = rows.shape[0]
+    if labels is not None:
+        labels = torch.as_tensor(labels).reshape(-1).to(torch.int32).cpu()
+        if labels.shape[0] != n:
+            raise ValueError(f"save_gallery: {labels.shape[0]} labels for {n} rows")
     shards = []
     for r in range(world):
         lo, hi = shard_bounds(n, world, r)
         torch.save(rows[lo:hi].cpu().contiguous(), f"{path}.shard{r:02d}.pt")
         shards.append(dict(rank=r, lo=lo, hi=hi, file=f"{path}.shard{r:02d}.pt"))
+        if labels is not None:
+            torch.save(labels[lo:hi].clone(), f"{path}.shard{r:02d}.labels.pt")
+            shards[-1]["labels_file"] = f"{path}.shard{r:02d}.labels.pt"
     with open(f"{path}.manifest.json", "w") as f:
-        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, shards=shards), f, indent=1)
+        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels=labels is not None, shards=shards), f,
+                  indent=1)
 
 
 def load_gallery_shard(path, rank, device):
     import json
     man = json.load(open(f"{path}.manifest.json"))
     sh = man["shards"][rank]
-    return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"])
+    labels = torch.load(sh["labels_file"]) if man.get("labels") else None
+    return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"], labels=labels)

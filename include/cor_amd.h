@@ -34,6 +34,8 @@ extern "C" {
 #define COR_TOPK_FORCE_GLOBAL_THRESHOLD 8 /* ... : never the two-launch local-threshold path of small shards (A/B partner, tests) */
 #define COR_TOPK_WAVE_FINAL 16 /* ... : global-threshold pipeline with the one-wave-per-query selection kernel fed from the records (slower A/B partner, tests) */
 #define COR_TOPK_KMAX 256     /* largest k cor_similarity_topk accepts (k > 32: the wide route, see below) */
+#define COR_FILTER_EQ 0       /* cor_similarity_topk_filtered: a row is allowed if its label equals the query's */
+#define COR_FILTER_NE 1       /* ... : a row is allowed if its label differs from the query's */
 
 enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */, COR_BF16X3 = 3 /* x3 split rows, see below */ };
 /* COR_BF16X3 (exact-query mode: the support branch at fp32 accuracy on the bf16 matrix cores). An fp32 value x is carried as
@@ -288,6 +290,27 @@ int cor_resample_cols_u8(const unsigned char* in, float* out_f32, unsigned char*
 long cor_topk_workspace_bytes(int Bq, int Ng, int k);
 int cor_similarity_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                         float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
+
+/* Filtered top-k: per query b, the top-k of the ALLOWED gallery rows only, ordered by (score desc, global index asc), indices global
+ * (g + g_offset). Every row has an int32 label row_labels[g] (shard-local row g; 16-byte aligned), every query an int32 label
+ * query_labels[b]. Row g is allowed for query b if query_labels[b] < 0 (unrestricted), else, by filter_mode, if
+ * row_labels[g] == query_labels[b] (COR_FILTER_EQ: restrict to a class or subset) or row_labels[g] != query_labels[b] (COR_FILTER_NE:
+ * exclude a source, e.g. the query's own image). Scores are the fmaf-chain scores of cor_similarity_topk: the result is bit-identical to
+ * the chain oracle run on the allowed rows, scores and indices, for COR_F32 / COR_BF16 / COR_F16, every C that cor_similarity_topk
+ * accepts and 1 <= k <= COR_TOPK_KMAX. A query with fewer than k allowed rows gets them first and then the (-inf, -1) tail; a query with
+ * no allowed row gets only the tail. Other arguments and alignment as for cor_similarity_topk; workspace >=
+ * cor_topk_filtered_workspace_bytes(Bq, Ng, k). A null label pointer or a bad filter_mode: COR_EINVAL.
+ * Route: every filtered call, whatever k, takes the wide route above with the filter inside the scans: a disallowed score is -inf before
+ * the sample's group values, the threshold and the append decision (which tests the allow predicate, so tau_q = -inf never admits a
+ * disallowed row). The sample keeps the four best allowed scores per group and the scan slices walk the gallery interleaved, so a
+ * class-sorted gallery (one label's rows in one block) neither loses its threshold nor crowds a few candidate streams. An overflowed
+ * query is ranked over its allowed rows by the in-kernel brute force. Flags: COR_TOPK_NO_FALLBACK keeps its meaning (index -2 in every
+ * slot of an overflowed query); COR_TOPK_FORCE_LISTS and COR_TOPK_WAVE_FINAL return COR_ENOSUPPORT; COR_TOPK_FORCE_GLOBAL_THRESHOLD has
+ * no effect. */
+long cor_topk_filtered_workspace_bytes(int Bq, int Ng, int k);
+int cor_similarity_topk_filtered(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
+                                 const int* row_labels, const int* query_labels, int filter_mode, float* out_scores, long long* out_idx,
+                                 void* workspace, int flags, void* stream);
 
 #ifdef __cplusplus
 }
