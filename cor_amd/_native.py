@@ -64,8 +64,11 @@ SIGNATURES = {
     "cor_similarity_topk": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p],
     "cor_topk_filtered_workspace_bytes": [_i, _i, _i],
     "cor_similarity_topk_filtered": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _i, _p, _p, _p, _i, _p],
+    "cor_topk_distinct_workspace_bytes": [_i, _i, _i],
+    "cor_topk_distinct_sample_values": [_i, _i, _i],
+    "cor_similarity_topk_distinct": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p, _p, _p, _i, _p],
 }
-_RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l}
+_RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l}
 
 _lib = None
 

@@ -333,6 +333,7 @@ struct ScanArgs {
   unsigned long long* stamps;      // COR_PROBES: cycle stamps of waves 0 and 4 of block 0 (tools/sim_stamps.py scan)
   float* tau; int* cnt; float* rec_s; int* rec_g; int cap;           // APPEND: tau_q (written by the blocks of slice 0 for the selection kernel); record i of stream (q, slice, lane quarter): 8 scores + first row
   const int* rlab; const int* qlab; int ne;                           // FILTER: row / query labels, COR_FILTER_NE (filtered wide route only)
+  int* sgrow;                                                         // GROUP SAMPLE: the shard row behind every stored sample value (distinct-group route only)
 };
 
 // One block = 8 waves = 256 * QB queries (wave w owns queries q0 + 32 * QB * w ..): with QB = 2 all 512 queries of an
@@ -360,7 +361,10 @@ __device__ __forceinline__ float key2f_floor(unsigned key) {      // the smalles
 // super-tiles split, split + nsplit, ... (a class-sorted gallery spreads over every slice and stream), the labels of those rows are copied
 // into LDS once in the prologue (a 4-slot ring: the fifth slot holds them), SAMPLE keeps the FOUR best allowed scores per group
 // (sg[q * Bqp + (split * 4 + rq) * 4 + j]: a clustered subset still yields >= k values), and APPEND decides on the allow predicate.
-template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false>
+// GROUP (the distinct-group route; SAMPLE only, implies WIDE; APPEND is the plain WIDE / FILTER instantiation): every stored sample value
+// keeps its ROW beside it (a.sgrow, same index as a.sg), NV = 1 (4 with FILTER) best allowed scores per (slice, lane quarter) group:
+// sim_tau_distinct needs the rows' group ids to count DISTINCT groups above the threshold.
+template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false, bool GROUP = false>
 __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int C = 256, TILE = 32 * C * 2, STILE = 2 * TILE, NS = FILTER ? SCAN_NS - 1 : SCAN_NS, AHEAD = FILTER ? SCAN_AHEAD - 1 : SCAN_AHEAD;
@@ -476,6 +480,8 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   int ncand[NQ];
   int ql[NQ];                                          // FILTER: the lane's query labels (< 0: unrestricted)
   float top4[NQ][4];                                   // FILTER SAMPLE: the group's four best allowed scores, descending
+  constexpr int NV = GROUP && FILTER ? 4 : 1;          // GROUP SAMPLE: the group's NV best allowed scores, descending, and their rows
+  float gv[NQ][NV]; int gr[NQ][NV];
   const int nstreams = a.nsplit * 4;                   // a stream = (query, gallery slice, lane quarter rq)
 #pragma unroll
   for (int qb = 0; qb < NQ; ++qb) {
@@ -490,6 +496,10 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
       ql[qb] = a.qlab[min(q0 + qb * 16 + n16, a.Bq - 1)];
 #pragma unroll
       for (int j = 0; j < 4; ++j) top4[qb][j] = -INFINITY;
+    }
+    if constexpr (GROUP) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) { gv[qb][j] = -INFINITY; gr[qb][j] = 0; }
     }
   }
   // read address of 32-deep K-step kk, row block rb: row rb * 16 + n16, chunk (4 kk + rq) ^ n16 = ((kk ^ (n16 >> 2)) << 2) | (rq ^ (n16 & 3)): one XOR
@@ -535,7 +545,25 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
       tmax = max3f(tmax, acc[qb][0][3], acc[qb][1][0]);
       tmax = max3f(tmax, acc[qb][1][1], acc[qb][1][2]);
       tmax = fmaxf(tmax, acc[qb][1][3]);
-      if (SAMPLE && FILTER) {                          // insertion of each allowed score into the sorted four (-inf: no change)
+      if constexpr (SAMPLE && GROUP) {                 // (score, row) into the sorted NV; rare after warm-up: one wave-uniform test skips it
+        if (__builtin_amdgcn_ballot_w64(tmax > gv[qb][NV - 1]) != 0) {
+#pragma unroll
+          for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float x = acc[qb][rb][e];          // masked / out-of-shard scores are -inf: never stored
+              if (x > gv[qb][NV - 1]) { gv[qb][NV - 1] = x; gr[qb][NV - 1] = g0 + 16 * rb + r4 + e; }
+#pragma unroll
+              for (int j = NV - 1; j > 0; --j) {
+                const float s0 = gv[qb][j - 1], s1 = gv[qb][j];
+                const int i0 = gr[qb][j - 1], i1 = gr[qb][j];
+                const bool up = s1 > s0;
+                gv[qb][j - 1] = up ? s1 : s0; gv[qb][j] = up ? s0 : s1;
+                gr[qb][j - 1] = up ? i1 : i0; gr[qb][j] = up ? i0 : i1;
+              }
+            }
+        }
+      } else if (SAMPLE && FILTER) {                   // insertion of each allowed score into the sorted four (-inf: no change)
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -656,7 +684,13 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
     for (int qb = 0; qb < NQ; ++qb) {
       const int q = q0 + qb * 16 + n16;
       if (q < a.Bq) {
-        if (SAMPLE && FILTER)
+        if constexpr (SAMPLE && GROUP) {
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const long at = (long)q * a.Bqp + (split * 4 + rq) * NV + j;
+            a.sg[at] = f2key(gv[qb][j]); a.sgrow[at] = gr[qb][j];
+          }
+        } else if (SAMPLE && FILTER)
           *(uint4*)(a.sg + (long)q * a.Bqp + (split * 4 + rq) * 4) = make_uint4(f2key(top4[qb][0]), f2key(top4[qb][1]), f2key(top4[qb][2]), f2key(top4[qb][3]));
         else if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
         else if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
@@ -1897,8 +1931,10 @@ struct WideScanArgs {
   unsigned* sg; int ngroups;
   const float* tau; int* cnt; uint2* lst; int cap;
   const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
+  int* sgrow;                                        // GROUP SAMPLE: the shard row behind every stored sample value
 };
-template <typename TG, bool SAMPLE, bool FILTER = false>
+//   GROUP (distinct-group route, SAMPLE only): NV = 1 (4 with FILTER) best allowed scores per group WITH their rows (a.sgrow), as sim_scan does.
+template <typename TG, bool SAMPLE, bool FILTER = false, bool GROUP = false>
 __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q, const TG* __restrict__ G, const WideScanArgs a) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1926,6 +1962,12 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
   int n = 0;
   const int ql = FILTER ? a.qlab[min(q, a.Bq - 1)] : 0;
   float top4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  constexpr int NV = GROUP && FILTER ? 4 : 1;
+  float gv[NV]; int gr[NV];
+  if constexpr (GROUP) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { gv[j] = -INFINITY; gr[j] = 0; }
+  }
   const int t0 = FILTER ? 0 : split * a.tiles_per_split, t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
   for (int t = t0; t < t1; ++t) {
     const int g0 = (FILTER ? split + t * a.nsplit : t) * a.tile_stride * 32;
@@ -1971,7 +2013,22 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
         }
       }
     }
-    if (SAMPLE && FILTER) {
+    if constexpr (SAMPLE && GROUP) {
+      if (__builtin_amdgcn_ballot_w64(tmax > gv[NV - 1]) != 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          if (sc[e] > gv[NV - 1]) { gv[NV - 1] = sc[e]; gr[NV - 1] = g0 + (e & 3) + 8 * (e >> 2) + 4 * h; }
+#pragma unroll
+          for (int j = NV - 1; j > 0; --j) {
+            const float s0 = gv[j - 1], s1 = gv[j];
+            const int i0 = gr[j - 1], i1 = gr[j];
+            const bool up = s1 > s0;
+            gv[j - 1] = up ? s1 : s0; gv[j] = up ? s0 : s1;
+            gr[j - 1] = up ? i1 : i0; gr[j] = up ? i0 : i1;
+          }
+        }
+      }
+    } else if (SAMPLE && FILTER) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         top4[3] = fmaxf(top4[3], fminf(top4[2], sc[e]));
@@ -1993,7 +2050,10 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
     }
   }
   if (q < a.Bq) {
-    if (SAMPLE && FILTER) *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[0]), f2key(top4[1]), f2key(top4[2]), f2key(top4[3]));
+    if constexpr (SAMPLE && GROUP) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) { a.sg[(long)q * a.ngroups + stream * NV + j] = f2key(gv[j]); a.sgrow[(long)q * a.ngroups + stream * NV + j] = gr[j]; }
+    } else if (SAMPLE && FILTER) *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[0]), f2key(top4[1]), f2key(top4[2]), f2key(top4[3]));
     else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
     else a.cnt[(long)q * nstreams + stream] = n;
   }
@@ -2130,6 +2190,335 @@ __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// DISTINCT GROUPS (cor_similarity_topk_distinct): every row has an int32 group id grp[row] (the source image of a region; a negative id
+// makes the row a group of its own); per query the k best group REPRESENTATIVES (a group's best allowed row by (chain score desc, index
+// asc)), ordered the same way. The wide route with three changes: the sample keeps rows (sim_scan / sim_wide_scan GROUP), the threshold
+// counts distinct groups (sim_tau_distinct), the selection reduces to one row per group (sim_final_distinct). The APPEND scans are the
+// wide / filtered instantiations unchanged: they append scores >= tau_q whatever the groups are.
+// one unsigned per group: the id, or for a negative id the row itself behind a set top bit (rows < 2^31: never equal to an id or another row)
+__device__ __forceinline__ unsigned group_key(const int* __restrict__ grp, int row) {
+  const int g = grp[row];
+  return g >= 0 ? (unsigned)g : (0x80000000u | (unsigned)row);
+}
+
+// tau_q of the distinct route, one block per query. The sample pass stored n values (order-preserving keys, sg) and the row of each
+// (sgrow); the values are reduced to ONE PER GROUP ID (the best kept; a sort of (group key, inverted score key) puts a group's best
+// first) and tau_q = the k-th largest of those - delta_q. Validity: the k values at or above it belong to k DIFFERENT groups, each with an
+// allowed row whose scan score is >= tau_q + delta_q, so at least k groups have a representative that good: the k-th best representative's
+// scan score is >= tau_q + delta_q and every row of the answer passes tau_q (the argument of sim_final_distinct). The k-th largest sampled
+// value itself proves nothing here: two sampled rows may be regions of one image. Fewer than k distinct sampled groups: -inf.
+// The sort runs in a fixed LDS array of TAU_DISTINCT_MAX keys. make_wide's group plan keeps ngroups within it for every Ng (it widens the
+// sample stride, see there), cor_similarity_topk_distinct refuses a plan that does not, and the kernel itself never touches more: it
+// ranks the FIRST TAU_DISTINCT_MAX stored values only, which is still a valid bound (any subset of the sampled rows proves the same
+// thing, with a lower threshold).
+constexpr int TAU_DISTINCT_MAX = 4096;
+template <typename TG>
+__global__ void __launch_bounds__(256) sim_tau_distinct(const float* __restrict__ Q, int C, const unsigned* __restrict__ sg, const int* __restrict__ sgrow,
+                                                        int nstored, int k, const int* __restrict__ grp, float* tau) {
+  __shared__ unsigned long long keys[TAU_DISTINCT_MAX];
+  const int n = nstored < TAU_DISTINCT_MAX ? nstored : TAU_DISTINCT_MAX;   // values ranked; nstored = the row stride of sg / sgrow
+  __shared__ int hist[256], sel_bin, k_rem, nheads;
+  __shared__ float part[4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  float n2 = 0.f;
+  if (sizeof(TG) != 4 && tid < C) { const float x = round_to<TG>(Q[(long)q * C + tid]); n2 = x * x; }
+  n2 = wave_sum(n2);
+  if ((tid & 63) == 0) part[tid >> 6] = n2;
+  if (tid == 0) nheads = 0;
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int i = tid; i < P; i += 256) {
+    unsigned long long key = ~0ull;                    // padding and groups without a finite allowed score: behind everything
+    if (i < n) {
+      const unsigned v = sg[(long)q * nstored + i];
+      if (v > f2key(-INFINITY)) key = ((unsigned long long)group_key(grp, sgrow[(long)q * nstored + i]) << 32) | (unsigned)~v;
+    }
+    keys[i] = key;
+  }
+  __syncthreads();
+  const float delta = sizeof(TG) == 4 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(part[0] + part[1] + part[2] + part[3]));
+  block_sort_u64(keys, P);
+  auto head = [&](int i) { return keys[i] != ~0ull && (i == 0 || (keys[i - 1] >> 32) != (keys[i] >> 32)); };
+  int mine = 0;
+  for (int i = tid; i < P; i += 256) mine += head(i) ? 1 : 0;
+  if (mine) atomicAdd(&nheads, mine);
+  __syncthreads();
+  float t = -INFINITY;
+  if (nheads >= k) {                                   // (block-uniform)
+    const unsigned kth = block_kth_key([&](int i) { return head(i) ? ~(unsigned)keys[i] : 0u; }, P, k, hist, &sel_bin, &k_rem);
+    t = key2f_floor(kth) - delta;
+  }
+  if (tid == 0) tau[q] = t;
+}
+
+// flag[j] = 1 iff entry j of rk[0 .. m) is the FIRST of its group there (rk: rank keys, low word = row, in rank order), else 0:
+// sort (group key, position) and mark the head of every group run. k2: scratch for the next power of two >= m keys. 256 threads.
+__device__ void first_of_group(const unsigned long long* rk, int m, const int* __restrict__ grp, unsigned long long* k2, int* flag) {
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int j = threadIdx.x; j < P; j += 256)
+    k2[j] = j < m ? (((unsigned long long)group_key(grp, (int)(unsigned)rk[j]) << 32) | (unsigned)j) : ~0ull;
+  __syncthreads();
+  block_sort_u64(k2, P);
+  for (int j = threadIdx.x; j < m; j += 256) {
+    const unsigned long long x = k2[j];
+    flag[(unsigned)x] = (j == 0 || (k2[j - 1] >> 32) != (x >> 32)) ? 1 : 0;
+  }
+  __syncthreads();
+}
+// exclusive prefix of flag[0 .. m) (m <= 8 * 256) at position 8 * tid (thread tid owns entries 8 tid .. 8 tid + 7); *total = the sum
+__device__ int block_prefix8(const int* flag, int m, int* wtot, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int local = 0;
+  for (int u = 0; u < 8; ++u) { const int j = 8 * tid + u; local += j < m ? flag[j] : 0; }
+  int incl = local;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+  __syncthreads();                                     // wtot of an earlier call is no longer read
+  if (lane == 63) wtot[wave] = incl;
+  __syncthreads();
+  int base = incl - local, tot = 0;
+  for (int w = 0; w < 4; ++w) { base += w < wave ? wtot[w] : 0; tot += wtot[w]; }
+  *total = tot;
+  return base;
+}
+
+// Exact fallback of ONE overflowed query of the distinct route (block of 256 threads): the shard is paged through IN RANK ORDER. A page =
+// the next <= SLW allowed rows behind the last page's last rank key (score desc, index asc): the page's lowest score key by
+// block_kth_key over the chain scores of the rows not yet paged, one pass collects the rows above it and the first ties at it in index
+// order (wide_brute_force's scheme), a bitonic sort ranks the page. Each page is folded into a table of the <= k groups found so far:
+// first_of_group marks the page's first row of every group, the marks of groups already in the table are dropped, and the survivors -
+// representatives, in rank order - go straight to the output. Stops at k groups or when the rows run out. Every page consumes SLW rows,
+// so it terminates; five chain passes over the shard per page: slow only for inputs that are pathological anyway (thousands of rows of
+// one group ahead of everything else). rlab == nullptr: unfiltered.
+template <typename TG>
+__device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, const int* __restrict__ grp,
+                                     float* sl_s, int* sl_i, int* flag, unsigned long long* keys, unsigned long long* k2, unsigned* found, int* hist,
+                                     float* out_s, long long* out_i, const int* __restrict__ rlab, int ql, int ne) {
+  __shared__ int sel_bin, k_rem, n_above, n_allowed, wcnt[4], wtot[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  auto allowed = [&](int g) { return rlab == nullptr || ql < 0 || ((rlab[g] == ql) != (ne != 0)); };
+  if (tid == 0) n_allowed = 0;
+  __syncthreads();
+  {
+    int mine = 0;
+    for (int g = tid; g < Ng; g += 256) mine += allowed(g) ? 1 : 0;
+    atomicAdd(&n_allowed, mine);
+  }
+  __syncthreads();
+  int remaining = n_allowed, nfound = 0;               // allowed rows not yet paged; groups written (both block-uniform)
+  bool first = true;
+  unsigned long long last = 0ull;                      // rank key of the last row of the last page
+  while (remaining > 0 && nfound < k) {
+    const int P = min(SLW, remaining);
+    // score and eligibility of row g: allowed and behind `last` in rank order; key 0 = not eligible (below every score's key)
+    auto score_of = [&](int g, float& s) {
+      if (!allowed(g)) return 0u;
+      s = chain_score_c<TG>(G, g, C, qs);
+      return (first || rank_key(s, g) > last) ? f2key(s) : 0u;
+    };
+    unsigned kth = 0u;
+    int need = 0, above = P;
+    if (remaining > P) {
+      kth = block_kth_key([&](int g) { float s; return score_of(g, s); }, Ng, P, hist, &sel_bin, &k_rem);
+      need = k_rem; above = P - need;
+    }
+    if (tid == 0) n_above = 0;
+    __syncthreads();
+    int taken = 0;
+    for (int g0 = 0; g0 < Ng; g0 += 256) {
+      const int g = g0 + tid;
+      float s = -INFINITY; unsigned key = 0u;
+      if (g < Ng) key = score_of(g, s);
+      const bool up = key > kth, tie = key != 0u && key == kth;
+      if (up) { const int p = atomicAdd(&n_above, 1); sl_s[p] = s; sl_i[p] = g; }
+      const unsigned long long b = __builtin_amdgcn_ballot_w64(tie);
+      if (lane == 0) wcnt[wave] = __builtin_popcountll(b);
+      __syncthreads();
+      int before = taken, tot = 0;
+      for (int w = 0; w < 4; ++w) { before += w < wave ? wcnt[w] : 0; tot += wcnt[w]; }
+      if (tie) {
+        const int pos = before + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (pos < need) { sl_s[above + pos] = s; sl_i[above + pos] = g; }
+      }
+      taken += tot;
+      __syncthreads();
+    }
+    int P2 = 1;
+    while (P2 < P) P2 <<= 1;
+    for (int j = tid; j < P2; j += 256) keys[j] = j < P ? rank_key(sl_s[j], sl_i[j]) : ~0ull;
+    __syncthreads();
+    block_sort_u64(keys, P2);
+    __syncthreads();
+    first_of_group(keys, P, grp, k2, flag);
+    for (int j = tid; j < P; j += 256) {
+      if (flag[j]) {
+        const unsigned gk = group_key(grp, (int)(unsigned)keys[j]);
+        for (int t = 0; t < nfound; ++t) if (found[t] == gk) { flag[j] = 0; break; }
+      }
+    }
+    __syncthreads();
+    int tot;
+    int slot = nfound + block_prefix8(flag, P, wtot, &tot);
+    for (int u = 0; u < 8; ++u) {
+      const int j = 8 * tid + u;
+      if (j < P && flag[j]) {
+        if (slot < k) {
+          const int row = (int)(unsigned)keys[j];
+          out_s[slot] = rank_key_score(keys[j]); out_i[slot] = (long long)row + g_offset;
+          found[slot] = group_key(grp, row);
+        }
+        ++slot;
+      }
+    }
+    last = keys[P - 1];
+    __syncthreads();
+    nfound = min(k, nfound + tot);
+    remaining -= P;
+    first = false;
+  }
+  for (int j = nfound + tid; j < k; j += 256) { out_s[j] = -INFINITY; out_i[j] = -1LL; }
+}
+
+// Exact selection of the distinct route, one block of 256 threads per query; the gather front ends of sim_final_wide (RECORDS / entry
+// lists). LDS: cs/ci [FSW] | keys [FSW] | sl_s/sl_i/flag [SLW] | qs[256] | hist[256] = 154 KiB.
+//   2. the candidates are reduced to one per group by SCAN score (sort of (group key, inverted score key): a group's best comes first)
+//      and T = the k-th best of those, exactly: k groups have a candidate row with scan score >= T. Fewer than k groups: T = -inf.
+//   3. the short list holds EVERY candidate row with scan score >= T - delta_q, not one per group: within delta_q another row of the group
+//      can win the chain re-score, and a row with exactly the same chain score and a lower index must win.
+//      Exactness. SIM_DELTA is twice the bound of |scan - chain| per score. k groups have a row that scans >= T, hence a representative with
+//      chain score >= T - delta_q / 2, so the k-th best representative has a chain score >= T - delta_q / 2 and every representative of the
+//      answer scans >= T - delta_q: it is in the short list (T - delta_q >= tau_q: the k sampled rows behind tau_q are candidates of k
+//      groups). It is the best row of its whole group, so the best of its group's short-listed rows too. A group whose representative is
+//      NOT short-listed has every chain score < T - delta_q / 2: whatever row of it is short-listed ranks behind the k-th representative.
+//   4. chain re-score (16-bit), one sort by (chain score desc, index asc): rank order; first_of_group keeps the first row of every group;
+//      a prefix count over the kept rows gives the output slots; the first k are written, then the (-inf, -1) tail.
+// Group ids are read from global memory by row (grp). Overflow (a stream list, the candidate buffer, the short list): distinct_brute_force.
+template <typename TG, bool RECORDS>
+__global__ void __launch_bounds__(256) sim_final_distinct(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C, int k, long long g_offset,
+                                                          const float* __restrict__ tau, const int* __restrict__ cnt, int nstreams, int cap,
+                                                          const float* __restrict__ rec_s, const int* __restrict__ rec_g, const uint2* __restrict__ lst,
+                                                          const int* __restrict__ grp, float* out_s, long long* out_i, int no_fallback,
+                                                          const int* __restrict__ rlab, const int* __restrict__ qlab, int ne) {
+  extern __shared__ __attribute__((aligned(16))) char fdraw[];
+  float* cs = (float*)fdraw; int* ci = (int*)(cs + FSW);
+  unsigned long long* keys = (unsigned long long*)(ci + FSW);
+  float* sl_s = (float*)(keys + FSW); int* sl_i = (int*)(sl_s + SLW); int* flag = sl_i + SLW;
+  float* qs = (float*)(flag + SLW); int* hist = (int*)(qs + 256);
+  unsigned long long* k2 = (unsigned long long*)fdraw;   // the candidate buffer, dead once the short list is built (SLW * 8 B <= 64 KiB)
+  __shared__ int ovf, total, nsl, sel_bin, k_rem, nheads, wtot[4];
+  __shared__ float qn2[4];
+  constexpr bool F32 = sizeof(TG) == 4;
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) { ovf = 0; total = 0; nsl = 0; nheads = 0; }
+  const float qv = tid < C ? round_to<TG>(Q[(long)q * C + tid]) : 0.f;   // the query as the scan saw it
+  if (tid < C) qs[tid] = qv;
+  const float part = wave_sum(qv * qv);
+  if (lane == 0) qn2[wave] = part;
+  __syncthreads();
+  const float delta = F32 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(qn2[0] + qn2[1] + qn2[2] + qn2[3]));
+  // 1. gather the candidates into LDS (thread <-> stream), as sim_final_wide does
+  const float tq = tau[q];
+  for (int st = tid; st < nstreams; st += 256) {
+    const int c = cnt[(long)q * nstreams + st];
+    if (c > cap) ovf = 1;
+    const int nrec = min(c, cap);
+    const long rec0 = ((long)q * nstreams + st) * cap;
+    for (int j = 0; j < nrec; ++j) {
+      if (RECORDS) {                                   // score [g][i] of lane quarter st & 3 is row g0 + 16 g + 4 (st & 3) + i
+        const f32x4* sj = (const f32x4*)(rec_s + (rec0 + j) * 8);
+        const f32x4 v[2] = {sj[0], sj[1]};
+        const int g0 = rec_g[rec0 + j], r4 = 4 * (st & 3);
+        int np = 0;
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) np += (v[g][i] >= tq && v[g][i] > -INFINITY) ? 1 : 0;
+        if (np == 0) continue;
+        int p = atomicAdd(&total, np);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (v[g][i] >= tq && v[g][i] > -INFINITY) {
+              if (p < FSW) { cs[p] = v[g][i]; ci[p] = g0 + i + 16 * g + r4; }
+              ++p;
+            }
+      } else {
+        const uint2 e = lst[rec0 + j];
+        const int p = atomicAdd(&total, 1);
+        if (p < FSW) { cs[p] = __uint_as_float(e.x); ci[p] = (int)e.y; }
+      }
+    }
+  }
+  __syncthreads();
+  if (total > FSW) ovf = 1;
+  const int n = min(total, FSW);
+  __syncthreads();
+  // 2. T = the k-th best per-group scan score (n <= k candidates: at most k groups, every candidate is in)
+  float T = -INFINITY;
+  if (!ovf && n > k) {
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int i = tid; i < P; i += 256) keys[i] = i < n ? (((unsigned long long)group_key(grp, ci[i]) << 32) | (unsigned)~f2key(cs[i])) : ~0ull;
+    __syncthreads();
+    block_sort_u64(keys, P);
+    auto head = [&](int i) { return i < n && (i == 0 || (keys[i - 1] >> 32) != (keys[i] >> 32)); };
+    int mine = 0;
+    for (int i = tid; i < n; i += 256) mine += head(i) ? 1 : 0;
+    if (mine) atomicAdd(&nheads, mine);
+    __syncthreads();
+    if (nheads >= k) T = key2f_floor(block_kth_key([&](int i) { return head(i) ? ~(unsigned)keys[i] : 0u; }, n, k, hist, &sel_bin, &k_rem));
+  }
+  // 3. short list: every candidate with scan score >= T - delta (fp32: the rows >= T, ties at T included)
+  if (!ovf) {
+    const float cut = T - delta;
+    for (int i = tid; i < n; i += 256) {
+      if (cs[i] >= cut) {
+        const int p = atomicAdd(&nsl, 1);
+        if (p < SLW) { sl_s[p] = cs[i]; sl_i[p] = ci[i]; }
+      }
+    }
+  }
+  __syncthreads();
+  if (nsl > SLW) ovf = 1;
+  __syncthreads();
+  if (ovf) {
+    if (no_fallback) {                                 // tests: expose the raw overflow marker
+      for (int j = tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -2LL; }
+      return;
+    }
+    // scratch: the found-group table in front of the candidate buffer, the page's group keys behind it
+    distinct_brute_force<TG>(G, Ng, C, qs, k, g_offset, grp, sl_s, sl_i, flag, keys, (unsigned long long*)(fdraw + 4096), (unsigned*)fdraw, hist,
+                             out_s + (long)q * k, out_i + (long)q * k, rlab, rlab ? qlab[q] : -1, ne);
+    return;
+  }
+  const int m = nsl;
+  // 4. exact re-scoring (16-bit), rank order, first row of every group, output slots
+  if (!F32)
+    for (int j = tid; j < m; j += 256) sl_s[j] = chain_score_c<TG>(G, sl_i[j], C, qs);
+  __syncthreads();
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int j = tid; j < P; j += 256) keys[j] = j < m ? rank_key(sl_s[j], sl_i[j]) : ~0ull;
+  __syncthreads();
+  block_sort_u64(keys, P);
+  __syncthreads();
+  first_of_group(keys, m, grp, k2, flag);
+  int ng;
+  int slot = block_prefix8(flag, m, wtot, &ng);
+  for (int u = 0; u < 8; ++u) {
+    const int j = 8 * tid + u;
+    if (j < m && flag[j]) {
+      if (slot < k) { out_s[(long)q * k + slot] = rank_key_score(keys[j]); out_i[(long)q * k + slot] = (long long)(unsigned)keys[j] + g_offset; }
+      ++slot;
+    }
+  }
+  for (int j = ng + tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -1LL; }
+}
+constexpr size_t FINAL_DISTINCT_LDS = (size_t)FSW * 16 + SLW * 12 + 256 * 4 + 256 * 4;
+
 // plan of the wide route (host; shared by the launcher and cor_topk_workspace_bytes). scan = the sim_scan form (16-bit, C = 256).
 // filter = the filtered route (any k): four sample values per group; the scan form's slices walk <= 128 super-tiles (their labels fill
 // the 32 KiB behind sim_scan's 4-slot ring).
@@ -2139,8 +2528,10 @@ struct WidePlan {
   int nsplit, tiles_per_split, ntiles, nstreams, cap;                // APPEND
   int s_stride, s_tiles, s_nsplit, s_tiles_per_split, ngroups;       // SAMPLE (ngroups == 0: no sample, tau = -inf)
   size_t off_img, off_sg, off_dq, off_tau, off_flags, off_ovf, off_cnt, off_recs, off_recg, bytes;
+  size_t off_sgrow;                  // group: the rows of the sample values
 };
-inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false) {
+// group = the distinct-group route (any k): the sample keeps NV = 1 (filter: 4) values WITH rows per group, and the capacity plan below.
+inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false) {
   WidePlan p{};
   p.scan = scan;
   const int rows = scan ? 64 : 32;                     // rows per tile of the scan kernel
@@ -2172,8 +2563,24 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false)
     // FSW / 2. Groups: 4 per slice (scan form, up to 256 slices: 1024) or 2 (tile form, up to 512 slices); Ng > 4096 gives >= 260.
     if (scan) p.s_stride = p.ntiles / 16 >= 128 ? 16 : (p.ntiles / 128 > 1 ? p.ntiles / 128 : 1);
     else p.s_stride = p.ntiles / 512 > 1 ? p.ntiles / 512 : 1;
-    const int smax = 2048 / k > 1 ? 2048 / k : 1;
+    // group: tau_q is the k-th largest sampled value AFTER the reduction to one per group id, i.e. sample rank k' = c k, where c = the
+    // sampled values per group among the best. The sampled values are maxima of disjoint row sets (a slice's rows of one lane quarter:
+    // rows 4 rq .. 4 rq + 3 of every 16), so a run of R <= 8 consecutive rows of one image reaches at most 3 of them, and only if its
+    // rows score alike; independent scores give c ~ 1 (a collision needs two of the ~k best sampled rows in one of Ng / 4.5 images).
+    // Planned for c = 2: the scan admits the rows above the sample's 2k-th value, ~1.4 * 2 k * stride of them (the 1.4 of the comment
+    // above), and the stride keeps that below FSW / 2: stride <= 1024 / k, expect = 6 k stride (the same 2x slack). More correlated
+    // galleries overflow into the paging fallback: exact, slower.
+    const int smax = group ? (1024 / k > 1 ? 1024 / k : 1) : (2048 / k > 1 ? 2048 / k : 1);
     if (p.s_stride > smax) p.s_stride = smax;
+    if (group && filter && scan) {
+      // sim_tau_distinct sorts at most TAU_DISTINCT_MAX = 4096 sample values per query in LDS. With a filter the scan form's sample slices
+      // walk <= 128 super-tiles (the label ring), so the slice count, and with it ngroups = 16 per slice, grows with Ng: beyond
+      // 128 * 256 sample super-tiles the stride widens to keep 256 slices. That trades candidates for the bound: ~2.8 k * stride rows pass
+      // tau_q, within FSW while stride <= 2900 / k, i.e. up to ~23M rows at k = 256, ~60M at k = 100 (128 * 256 * 64 rows per unit of
+      // stride); larger shards than that overflow into the paging fallback (exact, slow) rather than into memory they do not own.
+      const int need = cdiv(p.ntiles, 128 * 256);
+      if (p.s_stride < need) p.s_stride = need;
+    }
     p.s_tiles = cdiv(p.ntiles, p.s_stride);
     int sw = scan ? 256 : 512;
     if (sw > p.s_tiles) sw = p.s_tiles;
@@ -2181,7 +2588,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false)
     if (filter && scan && p.s_tiles_per_split > 128) p.s_tiles_per_split = 128;
     p.s_nsplit = cdiv(p.s_tiles, p.s_tiles_per_split);
     p.ngroups = per_tile * p.s_nsplit * (filter ? 4 : 1);
-    const long expect = 3L * k * p.s_stride;           // candidates per query, ~2x slack
+    const long expect = (group ? 6L : 3L) * k * p.s_stride;   // candidates per query, ~2x slack
     // per stream: Poisson with mean ~ expect / nstreams; +10 keeps P(overflow) per search small
     p.cap = (int)(2 * expect / p.nstreams) + 10;
     if (p.cap > stream_max) p.cap = stream_max;
@@ -2199,6 +2606,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false)
   p.off_cnt = take((size_t)Bq * p.nstreams * 4);
   p.off_recs = take((size_t)Bq * p.nstreams * p.cap * (scan ? 32 : 8));   // a record = 8 scores; an entry = (score, row)
   p.off_recg = take(scan ? (size_t)Bq * p.nstreams * p.cap * 4 : 0);
+  p.off_sgrow = take(group ? (size_t)Bq * p.ngroups * 4 + 4 : 0);
   p.bytes = o;
   return p;
 }
@@ -2293,6 +2701,84 @@ int launch_filtered(const float* Q, const TG* G, int Bq, int Ng, int C, int k, l
   return launch_wide_tiles<TG, true>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false, true), flags, s, rlab, qlab, ne);
 }
 
+// the distinct-group route (every k): sample with rows (GROUP), sim_tau_distinct, the wide / filtered APPEND scan as it is, sim_final_distinct.
+// FILTER: rlab / qlab / ne as in launch_filtered; grp: the rows' group ids.
+template <typename TG, int QB, bool FILTER>
+int launch_distinct_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long long g_offset, const int* grp, float* out_s, long long* out_i,
+                         char* w, const WidePlan& p, int flags, hipStream_t s, const int* rlab, const int* qlab, int ne) {
+  constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
+  static DevOnce once_s, once_a, once_f;
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER, true>, (int)lds, once_s);
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER>, (int)lds, once_a);
+  cor_max_dyn_lds((const void*)sim_final_distinct<TG, true>, (int)FINAL_DISTINCT_LDS, once_f);
+  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
+  int* cnt = (int*)(w + p.off_cnt); float* rec_s = (float*)(w + p.off_recs); int* rec_g = (int*)(w + p.off_recg);
+  uint4* qimg = (uint4*)(w + p.off_img);
+  const int Bqp = p.nqg * 256 * QB;
+  hipLaunchKernelGGL((sim_prep<TG>), dim3(p.nqg * 8 * QB), dim3(256), 0, s, Q, Bq, qimg, (int*)(w + p.off_flags), (int*)(w + p.off_ovf), sg, Bqp,
+                     (float*)(w + p.off_dq));
+  COR_CHECK_LAUNCH();
+  ScanArgs a{};
+  a.Bq = Bq; a.Ng = Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups; a.sgrow = (int*)(w + p.off_sgrow);
+  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
+  if (p.ngroups > 0) {
+    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
+    hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER, true>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
+    COR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((sim_tau_distinct<TG>), dim3(Bq), dim3(256), 0, s, Q, 256, sg, a.sgrow, p.ngroups, k, grp, tau);
+  COR_CHECK_LAUNCH();
+  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
+  a.k = k; a.tau = tau; a.cnt = cnt; a.rec_s = rec_s; a.rec_g = rec_g; a.cap = p.cap; a.tau_add = 0.f;
+  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
+  COR_CHECK_LAUNCH();
+  hipLaunchKernelGGL((sim_final_distinct<TG, true>), dim3(Bq), dim3(256), FINAL_DISTINCT_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     rec_s, rec_g, nullptr, grp, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename TG, bool FILTER>
+int launch_distinct_tiles(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* grp, float* out_s, long long* out_i,
+                          char* w, const WidePlan& p, int flags, hipStream_t s, const int* rlab, const int* qlab, int ne) {
+  static DevOnce once_f;
+  cor_max_dyn_lds((const void*)sim_final_distinct<TG, false>, (int)FINAL_DISTINCT_LDS, once_f);
+  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
+  int* cnt = (int*)(w + p.off_cnt); uint2* lst = (uint2*)(w + p.off_recs);
+  WideScanArgs a{};
+  a.Bq = Bq; a.Ng = Ng; a.C = C; a.nqt = p.nqt; a.sg = sg; a.ngroups = p.ngroups; a.sgrow = (int*)(w + p.off_sgrow);
+  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
+  if (p.ngroups > 0) {
+    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
+    hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER, true>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
+    COR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL((sim_tau_distinct<TG>), dim3(Bq), dim3(256), 0, s, Q, C, sg, a.sgrow, p.ngroups, k, grp, tau);
+  COR_CHECK_LAUNCH();
+  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
+  a.tau = tau; a.cnt = cnt; a.lst = lst; a.cap = p.cap;
+  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
+  COR_CHECK_LAUNCH();
+  hipLaunchKernelGGL((sim_final_distinct<TG, false>), dim3(Bq), dim3(256), FINAL_DISTINCT_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
+                     nullptr, nullptr, lst, grp, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename TG, bool FILTER>
+int launch_distinct(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* grp, const int* rlab, const int* qlab,
+                    int ne, float* out_s, long long* out_i, char* w, int flags, hipStream_t s) {
+  if constexpr (sizeof(TG) == 2) {
+    if (C == 256) {
+      const WidePlan p = make_wide(Bq, Ng, k, true, FILTER, true);
+      if (p.qb == 2) return launch_distinct_scan<TG, 2, FILTER>(Q, G, Bq, Ng, k, g_offset, grp, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
+      return launch_distinct_scan<TG, 1, FILTER>(Q, G, Bq, Ng, k, g_offset, grp, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
+    }
+  }
+  return launch_distinct_tiles<TG, FILTER>(Q, G, Bq, Ng, C, k, g_offset, grp, out_s, out_i, w, make_wide(Bq, Ng, k, false, FILTER, true), flags, s,
+                                           rlab, qlab, ne);
+}
+
 template <typename TG>
 int launch_topk(const float* Q, const void* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i,
                 void* workspace, int flags, hipStream_t s) {
@@ -2376,4 +2862,59 @@ extern "C" int cor_similarity_topk_filtered(const float* Q, const void* G, int g
     case COR_F16: return launch_filtered<_Float16>(Q, (const _Float16*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
     default: return COR_ENOSUPPORT;
   }
+}
+
+extern "C" long cor_topk_distinct_workspace_bytes(int Bq, int Ng, int k) {
+  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
+  long m = 0;
+  for (int scan = 0; scan < 2; ++scan)
+    for (int filter = 0; filter < 2; ++filter) {
+      const long b = (long)make_wide(Bq, Ng, k, scan != 0, filter != 0, true).bytes;
+      if (b > m) m = b;
+    }
+  return m;
+}
+
+static int distinct_sample_values(int Bq, int Ng, int k) {
+  int m = 0;
+  for (int scan = 0; scan < 2; ++scan)
+    for (int filter = 0; filter < 2; ++filter) {
+      const int g = make_wide(Bq, Ng, k, scan != 0, filter != 0, true).ngroups;
+      if (g > m) m = g;
+    }
+  return m;
+}
+
+extern "C" int cor_topk_distinct_sample_values(int Bq, int Ng, int k) {
+  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
+  return distinct_sample_values(Bq, Ng, k);
+}
+
+extern "C" int cor_similarity_topk_distinct(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
+                                            const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode,
+                                            float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
+  if (!Q || !G || !row_groups || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
+  if ((row_labels == nullptr) != (query_labels == nullptr)) return COR_EINVAL;
+  const bool filter = row_labels != nullptr;
+  if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
+  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
+  if (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL)) return COR_ENOSUPPORT;     // distinct calls always take the wide route
+  if (distinct_sample_values(Bq, Ng, k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;      // (the plan keeps it: sim_tau_distinct's LDS sort)
+  if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)row_groups & 15) || ((uintptr_t)row_labels & 15) || ((uintptr_t)workspace & 255))
+    return COR_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const int ne = filter && filter_mode == COR_FILTER_NE ? 1 : 0;
+  char* w = (char*)workspace;
+#define COR_DISTINCT(TG_)                                                                                                                       \
+  return filter ? launch_distinct<TG_, true>(Q, (const TG_*)G, Bq, Ng, C, k, g_offset, row_groups, row_labels, query_labels, ne, out_scores,     \
+                                             out_idx, w, flags, s)                                                                             \
+                : launch_distinct<TG_, false>(Q, (const TG_*)G, Bq, Ng, C, k, g_offset, row_groups, nullptr, nullptr, 0, out_scores, out_idx,  \
+                                              w, flags, s)
+  switch (g_dtype) {
+    case COR_F32: COR_DISTINCT(float);
+    case COR_BF16: COR_DISTINCT(bf16_t);
+    case COR_F16: COR_DISTINCT(_Float16);
+    default: return COR_ENOSUPPORT;
+  }
+#undef COR_DISTINCT
 }

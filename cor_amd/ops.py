@@ -460,12 +460,12 @@ def similarity_topk(Q, G, k, g_offset=0, flags=0):
 _FILTER_MODES = {"eq": nat.FILTER_EQ, "ne": nat.FILTER_NE}
 
 
-def _labels(t, n, name, device):
+def _labels(t, n, name, device, who="similarity_topk_filtered"):
     t = torch.as_tensor(t)
     if t.dim() != 1 or t.shape[0] != n:
-        raise ValueError(f"similarity_topk_filtered: {name} must be a vector of {n} labels, got shape {tuple(t.shape)}")
+        raise ValueError(f"{who}: {name} must be a vector of {n} labels, got shape {tuple(t.shape)}")
     if t.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"similarity_topk_filtered: {name} must be int32 (int64 is converted), got {t.dtype}")
+        raise ValueError(f"{who}: {name} must be int32 (int64 is converted), got {t.dtype}")
     t = t.to(device=device, dtype=torch.int32).contiguous()
     if t.data_ptr() % 16:                                     # the kernels read row labels 16 B at a time (a view into a larger tensor)
         t = t.clone()
@@ -499,6 +499,43 @@ def similarity_topk_filtered(Q, G, k, row_labels, query_labels, mode="eq", g_off
     nat.check(lib.cor_similarity_topk_filtered(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), rl.data_ptr(),
                                                qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
                                                int(flags), _s()), "cor_similarity_topk_filtered")
+    return scores, idx
+
+
+def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=None, mode="eq", g_offset=0, flags=0):
+    """Top-k DISTINCT groups: row_groups int32[Ng] gives every gallery row a group id (the source image of a region; a negative id
+    makes the row a group of its own). Per query, each group's representative is its best allowed row by (chain score desc, index
+    asc); the result is the k best representatives in that order: scores f32[Bq,k], idx i64[Bq,k] (global ROW ids, no group twice;
+    fewer than k groups: the (-inf, -1) tail). row_labels / query_labels / mode: the optional filter of similarity_topk_filtered
+    (both or neither; labels and group ids are separate vectors and may be the same tensor), e.g. mode "ne" with the query's own
+    image id. 1 <= k <= 256 for every gallery dtype and C; bit-identical to "chain-rank the allowed rows, keep the first row of each
+    group, keep the first k". No host synchronisation when the vectors already live on the device. flags: nat.TOPK_NO_FALLBACK."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"similarity_topk_distinct: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if mode not in _FILTER_MODES:
+        raise ValueError(f"similarity_topk_distinct: mode must be 'eq' or 'ne', got {mode!r}")
+    if (row_labels is None) != (query_labels is None):
+        raise ValueError("similarity_topk_distinct: row_labels and query_labels go together (both or neither)")
+    _dev(Q, G)
+    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
+    Bq, Cq = Q.shape
+    Ng, Cg = G.shape
+    assert Cq == Cg
+    who = "similarity_topk_distinct"
+    rg = _labels(row_groups, Ng, "row_groups", Q.device, who)
+    rl = _labels(row_labels, Ng, "row_labels", Q.device, who) if row_labels is not None else None
+    qlab = _labels(query_labels, Bq, "query_labels", Q.device, who) if query_labels is not None else None
+    lib = _lib()
+    nbytes = lib.cor_topk_distinct_workspace_bytes(Bq, Ng, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_topk_distinct_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)
+    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
+    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
+    nat.check(lib.cor_similarity_topk_distinct(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), rg.data_ptr(),
+                                               rl.data_ptr() if rl is not None else None, qlab.data_ptr() if qlab is not None else None,
+                                               _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), int(flags), _s()),
+              "cor_similarity_topk_distinct")
     return scores, idx
 
 

@@ -40,6 +40,46 @@ def merge_topk_host(scores_parts, idx_parts, k: int):
     return torch.gather(s, 1, o2), torch.gather(i, 1, o2)
 
 
+def merge_topk_distinct_host(scores_parts, idx_parts, group_parts, k: int):
+    """Host merge of per-shard DISTINCT-group lists: the concatenated entries are ranked by (score desc, index asc), reduced to the
+    best entry per non-negative group id (negative ids and nothing else are never merged; missing entries are dropped) and cut to
+    k; fewer than k groups: the (-inf, -1) tail. parts: lists of CPU tensors [Bq, k_i]; group_parts int32/int64, one id per entry.
+    Exact across shards: a global top-k representative r is its group's best row in its own shard, and fewer than k groups beat
+    it anywhere, so fewer than k beat it there: r is in that shard's list. Every other listed row of r's group ranks behind r,
+    and a group outside the global top-k only lists rows behind its own representative, hence behind the k-th."""
+    s = torch.cat(scores_parts, dim=1)
+    i = torch.cat(idx_parts, dim=1)
+    g = torch.cat([torch.as_tensor(x).to(torch.int64) for x in group_parts], dim=1)
+    B, N = s.shape
+    i_key = torch.where(i < 0, torch.full_like(i, torch.iinfo(torch.int64).max), i)   # missing entries last
+    o1 = torch.sort(i_key, dim=1, stable=True).indices
+    s, i, g = torch.gather(s, 1, o1), torch.gather(i, 1, o1), torch.gather(g, 1, o1)
+    o2 = torch.sort(s, dim=1, descending=True, stable=True).indices
+    s, i, g = torch.gather(s, 1, o2), torch.gather(i, 1, o2), torch.gather(g, 1, o2)   # rank order
+    g_key = torch.where(g >= 0, g, -1 - torch.arange(N, dtype=torch.int64).expand(B, N))   # a negative id: a group of its own
+    o3 = torch.sort(g_key, dim=1, stable=True).indices                               # groups together, rank order inside
+    gs = torch.gather(g_key, 1, o3)
+    head = torch.ones((B, N), dtype=torch.bool)
+    head[:, 1:] = gs[:, 1:] != gs[:, :-1]
+    keep = torch.zeros((B, N), dtype=torch.bool).scatter_(1, o3, head) & (i >= 0)
+    o4 = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices[:, :k]        # the kept entries first, in rank order
+    out_s, out_i = torch.gather(s, 1, o4), torch.gather(i, 1, o4)
+    if out_s.shape[1] < k:
+        out_s = torch.cat([out_s, torch.full((B, k - out_s.shape[1]), float("-inf"))], dim=1)
+        out_i = torch.cat([out_i, torch.full((B, k - out_i.shape[1]), -1, dtype=torch.int64)], dim=1)
+    tail = torch.arange(k).expand(B, k) >= keep.sum(1, keepdim=True)
+    return out_s.masked_fill(tail, float("-inf")), out_i.masked_fill(tail, -1)
+
+
+def groups_of(idx, groups):
+    """Global row ids -> group ids: idx i64[B,k] (as the searches return them; -1 = missing, stays -1), groups: one id per gallery
+    row (the whole gallery, e.g. dataloader.gallery_labels(csv, column="Query_img")). Image-level Recall@K is then
+    recall_at_k(groups_of(idx, groups), positive_image_ids)."""
+    idx = torch.as_tensor(idx).cpu().long()
+    groups = torch.as_tensor(groups).reshape(-1).cpu().long()
+    return torch.where(idx >= 0, groups[idx.clamp(min=0)], torch.full_like(idx, -1))
+
+
 def recall_at_k(idx, positives, ks=(1, 5, 10, 50, 100)) -> dict:
     """Recall@K of ranked lists: the fraction of queries with a positive among their first K entries.
     idx: i64[B, k] global gallery ids (as distributed_search / GalleryShard.search return them; -1 = missing).
@@ -67,9 +107,10 @@ def recall_at_k(idx, positives, ks=(1, 5, 10, 50, 100)) -> dict:
 
 class GalleryShard:
     """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16. labels: optional int32[n], one label
-    per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches."""
+    per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches. groups: optional int32[n],
+    one group id per row (typically the source image id; negative: a group of its own), for distinct searches."""
 
-    def __init__(self, rows: torch.Tensor, offset: int = 0, dtype: torch.dtype | None = None, labels=None):
+    def __init__(self, rows: torch.Tensor, offset: int = 0, dtype: torch.dtype | None = None, labels=None, groups=None):
         if not rows.is_cuda:
             raise RuntimeError("GalleryShard lives in GPU memory (no CPU path)")
         self.rows = rows.to(dtype or rows.dtype).contiguous()
@@ -80,14 +121,24 @@ class GalleryShard:
             if labels.dim() != 1 or labels.shape[0] != self.rows.shape[0]:
                 raise ValueError(f"GalleryShard: {tuple(labels.shape)} labels for {self.rows.shape[0]} rows")
             self.labels = labels.to(self.rows.device, torch.int32).contiguous()
+        self.groups = None
+        if groups is not None:
+            groups = torch.as_tensor(groups)
+            if groups.dim() != 1 or groups.shape[0] != self.rows.shape[0]:
+                raise ValueError(f"GalleryShard: {tuple(groups.shape)} group ids for {self.rows.shape[0]} rows")
+            self.groups = groups.to(self.rows.device, torch.int32).contiguous()
 
     def __len__(self):
         return self.rows.shape[0]
 
-    def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq"):
+    def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq", distinct: bool = False):
         """queries f32[Bq,C] (unit-norm) -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU; 1 <= k <= 256.
         query_labels (int32[Bq], < 0 = unrestricted): only the rows allowed by the shard's labels and `mode` ("eq": same label, "ne":
-        another label) are ranked (ops.similarity_topk_filtered); None: the whole shard."""
+        another label) are ranked (ops.similarity_topk_filtered); None: the whole shard.
+        distinct: one row per group id of the shard's `groups`, the k best groups (ops.similarity_topk_distinct), with or without the
+        filter; idx still names the winning ROW of each group."""
+        if distinct and self.groups is None:
+            raise ValueError("GalleryShard.search: distinct=True but the shard has no group ids")
         q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
         if query_labels is not None:
             if self.labels is None:
@@ -97,6 +148,9 @@ class GalleryShard:
             return (torch.full((q.shape[0], k), float("-inf"), device=q.device),
                     torch.full((q.shape[0], k), -1, dtype=torch.int64, device=q.device))
         with torch.cuda.device(self.rows.device):
+            if distinct:
+                return ops.similarity_topk_distinct(q, self.rows, k, self.groups, None if query_labels is None else self.labels, query_labels,
+                                                    mode=mode, g_offset=self.offset)
             if query_labels is None:
                 return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
             return ops.similarity_topk_filtered(q, self.rows, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
@@ -114,6 +168,18 @@ def _pack_lists(s: torch.Tensor, i: torch.Tensor) -> torch.Tensor:
     out[..., 0] = s.contiguous().view(torch.int32)
     out[..., 1:] = i.contiguous().view(torch.int32).view(i.shape + (2,))
     return out
+
+
+def _entry_groups(shard, i: torch.Tensor) -> torch.Tensor:
+    """Group ids (int32, same shape) of the global row ids i of `shard` (on i's device); a missing entry (-1) gets -1 (the clamps
+    only keep its gather in range). The searches behind this never run with TOPK_NO_FALLBACK, so no -2 marker arrives here. For a
+    GalleryShard the groups already live on that device and the conversion below copies nothing."""
+    local = (i - int(shard.offset)).clamp(min=0)
+    groups = torch.as_tensor(shard.groups).to(i.device)
+    if groups.shape[0] == 0:
+        return torch.full(i.shape, -1, dtype=torch.int32, device=i.device)
+    g = groups[local.clamp(max=groups.shape[0] - 1)].to(torch.int32)
+    return torch.where(i >= 0, g, torch.full_like(g, -1))
 
 
 def _unpack_lists(p: torch.Tensor):
@@ -181,7 +247,7 @@ def _to_host_async(t: torch.Tensor):
 
 def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int, group=None, max_local: int | None = None,
                        dst: int | None = 0, timing: list | None = None, always_collective: bool = False, defer: bool = False,
-                       query_labels=None, filter_mode: str = "eq"):
+                       query_labels=None, filter_mode: str = "eq", distinct: bool = False):
     """All ranks call this with their own queries [B_local, C] and their gallery shard.
 
     Two collectives in all, as BASELINE.json's north_star describes it:
@@ -207,10 +273,19 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     for dst=None); (None, None) on the other ranks. k: 1 .. 256 (recall_at_k turns the lists into Recall@K).
     query_labels: int32[B_local] (< 0 = unrestricted), best on the queries' device: a filtered search (GalleryShard.search with
     filter_mode "eq" / "ne" over each shard's row labels). The labels travel bit-cast in one extra column of the same fixed-size
-    all-gather block, so the call keeps its two collectives; None leaves the payload and the call shard.search(q, k) as they were."""
+    all-gather block, so the call keeps its two collectives; None leaves the payload and the call shard.search(q, k) as they were.
+    distinct: one entry per group id (shard.groups, e.g. the source image), the k best groups over ALL shards although an image's
+    regions may sit in two of them: every rank searches with distinct=True, its packed list carries a fourth int32 per entry, the
+    entry's group id (gathered on the device from shard.groups), and the host merge keeps the best entry per non-negative group id
+    before it cuts to k (merge_topk_distinct_host has the proof). Still two collectives and one device-to-host copy; defer works.
+    Without it the payloads, the [B,k,3] packing and the calls to shard.search are exactly as above."""
     import torch.distributed as dist
+    if distinct and getattr(shard, "groups", None) is None:
+        raise ValueError("distributed_search: distinct=True but the shard has no group ids")
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
-        if query_labels is None:
+        if distinct:
+            s, i = shard.search(local_queries, k, query_labels=query_labels, mode=filter_mode, distinct=True)
+        elif query_labels is None:
             s, i = shard.search(local_queries, k)
         else:
             s, i = shard.search(local_queries, k, query_labels=query_labels, mode=filter_mode)
@@ -245,12 +320,19 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         marks.mark()
     allb = allb.view(world, cap + 1, width)
     slots = allb[:, :cap, :C].reshape(world * cap, C).to(dev)    # every slot is scored; counts stay where they are
-    if query_labels is None:
+    slot_labels = None
+    if query_labels is not None:
+        slot_labels = allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
+    if distinct:
+        s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode, distinct=True)
+    elif query_labels is None:
         s, i = shard.search(slots, k)                            # local shard vs ALL query slots
     else:
-        slot_labels = allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
         s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode)
-    packed = _pack_lists(s, i).to(cdev)
+    packed = _pack_lists(s, i)
+    if distinct:                                                 # [slots,k,4]: + the entry's group id
+        packed = torch.cat([packed, _entry_groups(shard, i).unsqueeze(-1)], dim=-1)
+    packed = packed.to(cdev)
     if marks:
         marks.mark()
     if dst is None:
@@ -276,8 +358,11 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         counts = host[-world:].tolist()
         if any(c < 0 or c > cap for c in counts):
             raise RuntimeError(f"distributed_search: inconsistent per-rank query counts {counts} for max_local={cap}")
-        ps, pi = _unpack_lists(host[:-world].view(pshape))       # [world(shard), world*cap(slot), k]
+        lists = host[:-world].view(pshape)
+        ps, pi = _unpack_lists(lists[..., :3])                   # [world(shard), world*cap(slot), k]
         keep = torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
+        if distinct:
+            return merge_topk_distinct_host(list(ps[:, keep]), list(pi[:, keep]), list(lists[..., 3][:, keep]), k)
         return merge_topk_host(list(ps[:, keep]), list(pi[:, keep]), k)
 
     if defer:
@@ -310,15 +395,20 @@ def build_gallery(model, batches, dtype=torch.float16):
     return torch.cat(rows, dim=0)
 
 
-def save_gallery(path, rows, world=1, labels=None):
+def save_gallery(path, rows, world=1, labels=None, groups=None):
     """On-disk format: <path>.shardNN.pt (rows of shard NN as a tensor) + <path>.manifest.json (row ranges). labels (int32[n], one
-    per row): also <path>.shardNN.labels.pt per shard and "labels": true in the manifest."""
+    per row): also <path>.shardNN.labels.pt per shard and "labels": true in the manifest; groups (int32[n], one group id per row):
+    <path>.shardNN.groups.pt and "groups": true likewise."""
     import json
     n = rows.shape[0]
     if labels is not None:
         labels = torch.as_tensor(labels).reshape(-1).to(torch.int32).cpu()
         if labels.shape[0] != n:
             raise ValueError(f"save_gallery: {labels.shape[0]} labels for {n} rows")
+    if groups is not None:
+        groups = torch.as_tensor(groups).reshape(-1).to(torch.int32).cpu()
+        if groups.shape[0] != n:
+            raise ValueError(f"save_gallery: {groups.shape[0]} group ids for {n} rows")
     shards = []
     for r in range(world):
         lo, hi = shard_bounds(n, world, r)
@@ -327,9 +417,12 @@ def save_gallery(path, rows, world=1, labels=None):
         if labels is not None:
             torch.save(labels[lo:hi].clone(), f"{path}.shard{r:02d}.labels.pt")
             shards[-1]["labels_file"] = f"{path}.shard{r:02d}.labels.pt"
+        if groups is not None:
+            torch.save(groups[lo:hi].clone(), f"{path}.shard{r:02d}.groups.pt")
+            shards[-1]["groups_file"] = f"{path}.shard{r:02d}.groups.pt"
     with open(f"{path}.manifest.json", "w") as f:
-        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels=labels is not None, shards=shards), f,
-                  indent=1)
+        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels=labels is not None,
+                       groups=groups is not None, shards=shards), f, indent=1)
 
 
 def load_gallery_shard(path, rank, device):
@@ -337,4 +430,5 @@ def load_gallery_shard(path, rank, device):
     man = json.load(open(f"{path}.manifest.json"))
     sh = man["shards"][rank]
     labels = torch.load(sh["labels_file"]) if man.get("labels") else None
-    return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"], labels=labels)
+    groups = torch.load(sh["groups_file"]) if man.get("groups") else None
+    return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"], labels=labels, groups=groups)

@@ -312,6 +312,40 @@ int cor_similarity_topk_filtered(const float* Q, const void* G, int g_dtype, int
                                  const int* row_labels, const int* query_labels, int filter_mode, float* out_scores, long long* out_idx,
                                  void* workspace, int flags, void* stream);
 
+/* Distinct-group top-k: every gallery row g has an int32 group id row_groups[g] (shard-local row g; 16-byte aligned; typically the source
+ * image of a region); a negative id makes the row a group of its own. Per query b, among the rows ALLOWED for b, each group's
+ * representative is its best row by (chain score desc, global index asc), and the result is the k best representatives ordered the same
+ * way: out_scores f32[Bq,k], out_idx i64[Bq,k] = the representative ROWS as global ids (g + g_offset), so no group appears twice. Fewer
+ * than k groups with an allowed row: those first, then the (-inf, -1) tail. Allowed = every row when row_labels and query_labels are both
+ * NULL, else the rows the filter of cor_similarity_topk_filtered allows (row_labels / query_labels / filter_mode as there; filter labels
+ * and group ids are separate vectors and may be the same memory). Scores are the fmaf-chain scores of cor_similarity_topk: the result is
+ * bit-identical to "chain-rank the allowed rows, keep the first row of each group, keep the first k", for COR_F32 / COR_BF16 / COR_F16,
+ * every C that cor_similarity_topk accepts and 1 <= k <= COR_TOPK_KMAX. Other arguments and alignment as for cor_similarity_topk;
+ * workspace >= cor_topk_distinct_workspace_bytes(Bq, Ng, k). A null row_groups, exactly one of the two label pointers null, or a
+ * filter_mode that is neither COR_FILTER_EQ nor COR_FILTER_NE (also when unfiltered): COR_EINVAL.
+ * Route: the wide route for every k. The sample pass keeps the ROW of every sampled value, the threshold kernel reduces the sampled values
+ * to one per group id before it takes the k-th (tau_q is valid only if k DISTINCT groups have a row above it), the wide / filtered scan
+ * appends the scores >= tau_q unchanged, and one block per query reduces the candidates to one per group, selects the k-th best group,
+ * re-scores every candidate row within delta_q of it with the chain and keeps the first row of each group in rank order. An overflowed
+ * query (thousands of rows of one group ahead of everything else, fewer than k groups in a large shard) is ranked on the device by paging
+ * through the shard in rank order until k groups are found (exact; no host round trip). Flags: COR_TOPK_NO_FALLBACK keeps its meaning
+ * (index -2 in every slot of an overflowed query); COR_TOPK_FORCE_LISTS and COR_TOPK_WAVE_FINAL return COR_ENOSUPPORT;
+ * COR_TOPK_FORCE_GLOBAL_THRESHOLD has no effect.
+ * Cost of the fallback: it pages through the shard 2048 rows at a time, five chain passes over the whole shard per page, until k groups
+ * are found. A query that finds them in the first pages (thousands of near-identical rows) costs a few passes; a shard with FEWER THAN k
+ * groups allowed for a query is paged to its end: Ng / 2048 pages x 5 Ng row scores = Ng^2 / 410 row scores per query in one block of 256
+ * threads (2.4e7 at 100k rows, 2.4e9 at 1M rows: seconds). Such shards are legal and exact, but keep them small, or search them with
+ * cor_similarity_topk_filtered per group.
+ * cor_topk_distinct_sample_values: the most sample values per query any plan of this call shape hands the threshold kernel, which sorts
+ * at most 4096 of them in LDS; the plan keeps it within that for every Ng (tests assert it; a plan that did not would be refused with
+ * COR_ENOSUPPORT). With a filter, 16-bit C = 256 shards beyond ~23M rows at k = 256 (~60M at k = 100) pay for it with a wider sample
+ * stride than the candidate buffers are planned for: their queries overflow into the fallback above. */
+long cor_topk_distinct_workspace_bytes(int Bq, int Ng, int k);
+int cor_topk_distinct_sample_values(int Bq, int Ng, int k);
+int cor_similarity_topk_distinct(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
+                                 const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
+                                 long long* out_idx, void* workspace, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
