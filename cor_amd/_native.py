@@ -47,6 +47,7 @@ SIGNATURES = {
     "cor_dwconv7x7": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "cor_adapter_pool": [_p, _p, _p, _i, _i, _i, _i, _p],
     "cor_masked_pool": [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p],
+    "cor_region_pool": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "cor_fuse_gate": [_p, _p, _p, _p, _p, _i, _i, _p],
     "cor_fuse_mix": [_p, _p, _p, _i, _i, _p],
     "cor_dense_pe": [_p, _p, _i, _i, _p],

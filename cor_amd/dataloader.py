@@ -173,3 +173,101 @@ def gallery_batches(csv_path, dataset_path, batch_size=8, device="cuda", num_wor
     for samples in DataLoader(_G(), batch_size=batch_size, shuffle=False, num_workers=num_workers, collate_fn=_HostCollate()):
         yield {"query_img": torch.stack([q_img(up(s["q"])) for s in samples]),
                "query_mask": torch.stack([q_mask(up(s["m"])) for s in samples])}
+
+
+def gallery_groups(csv_path):
+    """One int32 group id per gallery row (the rows of read_pairs_csv, in its order, as gallery_labels): ids of the source IMAGE, i.e. of
+    the pair (Dataset, Query_img), by first appearance - two datasets that both hold a `0001.jpg` get two ids. Returns
+    (groups int32[n], keys) with keys[id] = (Dataset, Query_img). The ids GalleryShard(groups=...), save_gallery(groups=...) and
+    search(distinct=True) consume."""
+    df = read_pairs_csv(csv_path)
+    ids, keys, out = {}, [], np.empty(len(df), dtype=np.int32)
+    for i, key in enumerate(zip(df["Dataset"].tolist(), df["Query_img"].tolist())):
+        if key not in ids:
+            ids[key] = len(keys)
+            keys.append(key)
+        out[i] = ids[key]
+    return torch.from_numpy(out), keys
+
+
+def plan_region_batches(groups, images_per_batch, max_regions=None):
+    """Batches for the multi-region gallery builder, from one group (image) id per CSV row: a list of batches, each a list of
+    (image_id, [row indices]). Images come in order of first appearance and an image's rows in CSV order, wherever they stand in the
+    CSV; a batch holds at most `images_per_batch` images and, when `max_regions` is given, at most that many rows. Only an image with
+    more than `max_regions` rows of its own is split, over consecutive batches (it is then encoded once per piece); any other image
+    that does not fit the room left opens the next batch. Every row appears exactly once."""
+    images_per_batch = int(images_per_batch)
+    if images_per_batch < 1 or (max_regions is not None and int(max_regions) < 1):
+        raise ValueError("plan_region_batches: images_per_batch and max_regions must be >= 1")
+    by_image = {}
+    for i, g in enumerate(torch.as_tensor(groups).reshape(-1).tolist()):
+        by_image.setdefault(int(g), []).append(i)
+    pieces = []
+    for g, rows in by_image.items():                            # dicts keep insertion order: first appearance
+        step = len(rows) if max_regions is None else int(max_regions)
+        pieces += [(g, rows[j:j + step]) for j in range(0, len(rows), step)]
+    batches, cur, n = [], [], 0
+    for g, rows in pieces:
+        if cur and (len(cur) == images_per_batch or (max_regions is not None and n + len(rows) > int(max_regions))):
+            batches.append(cur)
+            cur, n = [], 0
+        cur.append((g, rows))
+        n += len(rows)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+class _RegionBatches(Dataset):
+    """Item i: the decoded files of batch i of a plan_region_batches plan (every image of the batch once, every mask once)."""
+
+    def __init__(self, df, dataset_path, plan):
+        self.df, self.dataset_path, self.plan = df, dataset_path, plan
+
+    def __len__(self):
+        return len(self.plan)
+
+    def __getitem__(self, i):
+        out = []
+        for g, rows in self.plan[i]:
+            first = self.df.iloc[rows[0]]
+            root = os.path.join(self.dataset_path, first["Dataset"])
+            masks = []
+            for r in rows:
+                row = self.df.iloc[r]
+                masks.append(VaildingDataset.binary_loader(os.path.join(root, "mask", str(row["Target"]), row["Query_mask"])))
+            out.append({"id": g, "rows": rows, "q": VaildingDataset.rgb_loader(os.path.join(root, "image", first["Query_img"])), "m": masks})
+        return out
+
+
+def _identity(x):
+    return x
+
+
+def gallery_region_batches(csv_path, dataset_path, batch_size=8, device="cuda", num_workers=0, max_regions=None, grid=64):
+    """Input of cor_amd.retrieval.build_gallery_regions from the CSV schema of gallery_batches: every distinct image (Dataset, Query_img)
+    is decoded and resized ONCE, each of its masks once; yields {"query_img" f32[B,3,1024,1024], "region_masks" f32[R,1,grid,grid],
+    "region_offsets" int32[B+1], "image_ids" (gallery_groups' ids), "row_index" (the CSV row of each region)} with B <= batch_size images
+    (and R <= max_regions regions when given: plan_region_batches). With row_index the builder returns its rows in CSV order, the
+    layout of build_gallery(model, gallery_batches(...)) and of gallery_labels / gallery_groups. Every mask is reduced to the encoder's
+    token grid (`grid` = image size / patch size = 64 for SAM; ops.bilinear, per plane what the batched call gives) as soon as it is
+    resized, so device memory for masks does not grow with 1024^2 x regions."""
+    from . import ops
+    df = read_pairs_csv(csv_path)
+    groups, _ = gallery_groups(csv_path)
+    plan = plan_region_batches(groups, batch_size, max_regions)
+    dev = torch.device(device)
+    q_img, q_mask = P.ImageTransform(1024), P.MaskTransform(1024)
+    up = lambda a: torch.from_numpy(np.array(a, copy=True)).to(dev)                   # noqa: E731
+    for items in DataLoader(_RegionBatches(df, dataset_path, plan), batch_size=None, shuffle=False, num_workers=num_workers, collate_fn=_identity):
+        imgs, planes, offsets, ids, index = [], [], [0], [], []
+        for it in items:
+            imgs.append(q_img(up(it["q"])))
+            for m in it["m"]:
+                planes.append(ops.bilinear(q_mask(up(m)).reshape(1, 1, 1024, 1024).contiguous(), grid, grid)[0])
+            offsets.append(offsets[-1] + len(it["m"]))
+            ids.append(it["id"])
+            index += list(it["rows"])
+        yield {"query_img": torch.stack(imgs), "region_masks": torch.stack(planes),
+               "region_offsets": torch.tensor(offsets, dtype=torch.int32), "image_ids": torch.tensor(ids, dtype=torch.int32),
+               "row_index": torch.tensor(index, dtype=torch.int64)}

@@ -362,6 +362,24 @@ def masked_pool(feat, mask, B, P, D, feat_nchw=False, clamp01=False, l2norm=Fals
     return out
 
 
+def region_pool(tokens, masks, region_offsets, B, P, D, out_dtype=torch.float32, clamp01=False, l2norm=False):
+    """R masks pooled against the tokens of B images, every image's tokens read once per tile of regions (cor_region_pool).
+    tokens f32 [B,P,D] channels-last, masks f32 [R,P], region_offsets int32 [B+1] on the device (CSR: regions [off[b], off[b+1]) belong
+    to image b) -> [R,D] in out_dtype (float32 / bfloat16 / float16). An f32 row has the bits masked_pool gives for that mask alone."""
+    _dev(tokens, masks, region_offsets)
+    assert tokens.dtype == torch.float32 and tokens.is_contiguous() and tokens.numel() == B * P * D
+    assert masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() % P == 0
+    assert region_offsets.dtype == torch.int32 and region_offsets.is_contiguous() and region_offsets.numel() == B + 1
+    assert out_dtype in _DT, f"region_pool: out_dtype {out_dtype}"
+    R = masks.numel() // P
+    out = torch.empty((R, D), dtype=out_dtype, device=tokens.device)
+    if R == 0 or B == 0:
+        return out
+    nat.check(_lib().cor_region_pool(tokens.data_ptr(), masks.data_ptr(), region_offsets.data_ptr(), out.data_ptr(), _DT[out_dtype],
+                                     B, R, P, D, int(clamp01), int(l2norm), _s()), "cor_region_pool")
+    return out
+
+
 def fuse_gate(img, txt, aI, aT):
     _dev(img, txt, aI, aT)
     N, D = img.shape

@@ -395,6 +395,66 @@ def build_gallery(model, batches, dtype=torch.float16):
     return torch.cat(rows, dim=0)
 
 
+@torch.no_grad()
+def build_gallery_regions(model, batches, dtype=torch.float16):
+    """Multi-region gallery builder: every image goes through the SAM image encoder ONCE, all of its region masks are pooled against
+    its tokens in one launch (ops.region_pool) -> (rows [sum R, 256] unit-norm in `dtype`, groups int32[sum R]: the image id of each
+    row), ready for GalleryShard(rows, groups=groups) / save_gallery(path, rows, world, groups=groups) / search(distinct=True).
+    `batches` yields dicts with "query_img" f32[B,3,1024,1024], "region_masks" f32[R,1,h,w] and "region_offsets" int[B+1] (host or
+    device; CSR: regions [off[b], off[b+1]) belong to image b, an image may have none), optionally "image_ids" int[B] (global ids of
+    the batch's images; default: a running count of the images seen) and "row_index" int[R] (the position of each region's row in the
+    finished gallery; default: arrival order). A row_index that is not a permutation of 0 .. sum R - 1 raises ValueError.
+    dataloader.gallery_region_batches yields such batches from the reference's CSV, with row_index = the CSV row. A row has the
+    arithmetic of build_gallery's (the pooling is bit-identical given the same tokens)."""
+    from . import engine
+    T = model._resolve_dtype()
+    W = model.packed(T)
+    cfg = model.image_encoder.cfg
+    g = cfg["img"] // cfg["patch"]
+    rows, groups, index, seen, indexed = [], [], [], 0, None
+    for b in batches:
+        img = b["query_img"].to(model.device, torch.float32).contiguous()
+        B = img.shape[0]
+        off = torch.as_tensor(b["region_offsets"]).reshape(-1)
+        off_host = off.cpu().to(torch.int64)
+        m = b["region_masks"].to(model.device, torch.float32).contiguous()
+        R = m.shape[0]
+        if off_host.shape[0] != B + 1 or int(off_host[0]) != 0 or int(off_host[-1]) != R or bool((off_host[1:] < off_host[:-1]).any()):
+            raise ValueError(f"build_gallery_regions: region_offsets {off_host.tolist()} do not describe {R} regions of {B} images")
+        ids = torch.as_tensor(b["image_ids"]).reshape(-1).cpu().to(torch.int64) if b.get("image_ids") is not None \
+            else torch.arange(seen, seen + B, dtype=torch.int64)
+        if ids.shape[0] != B:
+            raise ValueError(f"build_gallery_regions: {ids.shape[0]} image ids for {B} images")
+        seen += B
+        has_index = b.get("row_index") is not None
+        if indexed is not None and has_index != indexed:
+            raise ValueError("build_gallery_regions: row_index must be given by every batch or by none")
+        indexed = has_index
+        if indexed:
+            ri = torch.as_tensor(b["row_index"]).reshape(-1).cpu().to(torch.int64)
+            if ri.shape[0] != R:
+                raise ValueError(f"build_gallery_regions: {ri.shape[0]} row indices for {R} regions")
+            index.append(ri)
+        groups.append(torch.repeat_interleave(ids, off_host[1:] - off_host[:-1]).to(torch.int32))
+        tok = engine.sam_encoder(W, img, cfg, T)                                       # [B*g*g, 256] fp32 tokens, once per image
+        if R and tuple(m.shape[-2:]) != (g, g):
+            m = ops.bilinear(m, g, g)
+        rows.append(ops.region_pool(tok, m.reshape(R, g * g), off.to(model.device, torch.int32).contiguous(), B, g * g, cfg["out"],
+                                    out_dtype=dtype, clamp01=True, l2norm=True))
+    if not rows:
+        return torch.empty((0, cfg["out"]), dtype=dtype, device=model.device), torch.empty((0,), dtype=torch.int32)
+    rows, groups = torch.cat(rows, dim=0), torch.cat(groups)
+    if indexed:
+        index = torch.cat(index)
+        n = rows.shape[0]
+        if index.shape[0] != n or not torch.equal(torch.sort(index).values, torch.arange(n, dtype=torch.int64)):
+            raise ValueError(f"build_gallery_regions: row_index is not a permutation of 0..{n - 1}")
+        inv = torch.empty(n, dtype=torch.int64)
+        inv[index] = torch.arange(n, dtype=torch.int64)        # finished[index[j]] = arrival[j]
+        rows, groups = rows[inv.to(rows.device)], groups[inv]
+    return rows, groups
+
+
 def save_gallery(path, rows, world=1, labels=None, groups=None):
     """On-disk format: <path>.shardNN.pt (rows of shard NN as a tensor) + <path>.manifest.json (row ranges). labels (int32[n], one
     per row): also <path>.shardNN.labels.pt per shard and "labels": true in the manifest; groups (int32[n], one group id per row):

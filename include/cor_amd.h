@@ -189,6 +189,21 @@ int cor_adapter_pool(const float* maps, const float* feat, float* out, int B, in
 int cor_masked_pool(const float* feat, int feat_nchw, const float* mask, float* out, int B, int P, int D,
                     int clamp01, int l2norm, void* stream);
 
+/* Region pooling for a multi-region gallery: R masks pooled against the tokens of B images, every image's tokens read once per
+ * tile of 8 regions instead of once per region. tokens f32 [B,P,D] channels-last (the SAM encoder's output: P = grid^2, D = 256);
+ * masks f32 [R,P], one plane per region at grid resolution; region_offsets int32 [B+1] in DEVICE memory, CSR layout: regions
+ * [off[b], off[b+1]) belong to image b (non-decreasing, off[0] = 0, off[B] = R; an image may have none). out [R,D] in out_dtype
+ * (COR_F32, COR_BF16 or COR_F16; 16-bit outputs are the f32 result rounded to nearest-even).
+ *   out[r,:] = sum_p tokens[b,p,:]*m[r,p] / (sum_p m[r,p] + 1e-8), m clamped to [0,1] if clamp01, L2-normalised if l2norm
+ * with the summation orders of cor_masked_pool: a COR_F32 row is bit-identical to cor_masked_pool(tokens + b*P*D, 0, masks + r*P,
+ * B = 1, ...), so a gallery row does not depend on how many regions share its image, on their order or on the tiling.
+ * The host cannot see the offsets: the kernel clamps them into [0, R] and never reads or writes outside the three arrays (rows that
+ * inconsistent offsets leave uncovered are not written). R == 0 or B == 0: returns 0 without a launch. D <= 1024 (the tile's pooled
+ * rows wait in LDS for the norm), larger: COR_ENOSUPPORT; a bad out_dtype: COR_EINVAL.
+ * ref: utils/loss_func.py:35-56 (region embedding) applied to every region of an image. */
+int cor_region_pool(const float* tokens, const float* masks, const int* region_offsets, void* out, int out_dtype, int B, int R,
+                    int P, int D, int clamp01, int l2norm, void* stream);
+
 /* i' = aI*i ; t' = aT*t  (gates already sigmoid-ed), written into cat [N,2D]; and the final
  * out = normalize(dyn*i' + (1-dyn)*t'). ref: cir_feature_fuse.py:51-58. */
 int cor_fuse_gate(const float* img, const float* txt, const float* aI, const float* aT, float* cat, int N, int D, void* stream);
