@@ -557,6 +557,41 @@ def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=
     return scores, idx
 
 
+def merge_topk(scores, idx, k, groups=None):
+    """Merge P top-k lists per query on the device (cor_merge_topk): scores f32 [P,B,kin], idx i64 [P,B,kin] (global row ids; < 0 =
+    missing, ranked after every present entry), as P searches return them, stacked -> (scores f32[B,k], idx i64[B,k]) ordered by
+    (score desc, index asc) with the (-inf, -1) tail. groups i32 [P,B,kin] (one id per entry): the distinct merge, the best entry
+    per non-negative group id, and a third result, the survivors' group ids i32[B,k] (-1 in the tail), so that a merged list can be
+    merged again. Bitwise equal to retrieval.merge_topk_host / merge_topk_distinct_host on the same lists. 1 <= k <= 256;
+    P * kin <= nat.MERGE_NMAX (4096) entries per query in one launch, beyond that NativeError (retrieval.merge_topk_device merges
+    in rounds). No host synchronisation."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"merge_topk: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if scores.dim() != 3 or scores.shape[0] < 1 or scores.shape[2] < 1:
+        raise ValueError(f"merge_topk: scores must be [P, B, kin] with P, kin >= 1, got {tuple(scores.shape)}")
+    for name, t, dt in (("idx", idx, torch.int64), ("groups", groups, torch.int32)):
+        if t is not None and (t.shape != scores.shape or t.dtype != dt):
+            raise ValueError(f"merge_topk: {name} must be {dt} of shape {tuple(scores.shape)}, got {t.dtype} {tuple(t.shape)}")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"merge_topk: scores must be float32, got {scores.dtype}")
+    _dev(scores, idx, groups)
+    scores, idx = scores.contiguous(), idx.contiguous()
+    groups = groups.contiguous() if groups is not None else None
+    P, B, kin = scores.shape
+    lib = _lib()
+    nbytes = lib.cor_merge_topk_workspace_bytes(P, B, kin, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_merge_topk_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device) if nbytes else None
+    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
+    out_i = torch.empty((B, k), dtype=torch.int64, device=scores.device)
+    out_g = torch.empty((B, k), dtype=torch.int32, device=scores.device) if groups is not None else None
+    if B:                                                     # (no queries: empty tensors have no address to pass)
+        nat.check(lib.cor_merge_topk(scores.data_ptr(), idx.data_ptr(), _p(groups) or None, P, B, kin, k, out_s.data_ptr(), out_i.data_ptr(),
+                                     _p(out_g) or None, _p(ws) or None, _s()), "cor_merge_topk")
+    return (out_s, out_i) if groups is None else (out_s, out_i, out_g)
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

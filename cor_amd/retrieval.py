@@ -71,6 +71,50 @@ def merge_topk_distinct_host(scores_parts, idx_parts, group_parts, k: int):
     return out_s.masked_fill(tail, float("-inf")), out_i.masked_fill(tail, -1)
 
 
+def _merge_stacked(s, i, g, k: int):
+    """Rounds of ops.merge_topk over stacked lists s, i[, g] of shape [P, B, kin] on one GPU -> (scores, idx, groups or None), [B, k]."""
+    while s.shape[0] * s.shape[2] > ops.nat.MERGE_NMAX:
+        per = max(1, ops.nat.MERGE_NMAX // s.shape[2])          # lists per launch; the outputs are lists of k <= 256, so a round shrinks
+        outs = [ops.merge_topk(s[j:j + per], i[j:j + per], k, None if g is None else g[j:j + per]) for j in range(0, s.shape[0], per)]
+        s, i = torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
+        g = None if g is None else torch.stack([o[2] for o in outs])
+    out = ops.merge_topk(s, i, k, g)
+    return (out[0], out[1], None) if g is None else out
+
+
+def merge_topk_device(scores_parts, idx_parts, k: int, group_parts=None):
+    """merge_topk_host / merge_topk_distinct_host on the GPU (ops.merge_topk, cor_merge_topk): parts are lists of device tensors
+    [B, k_i] as the searches return them (missing entries (-inf, -1)); the result is bitwise what the host functions give on CPU
+    copies of the same lists and stays on the device: (scores f32[B,k], idx i64[B,k]), with group_parts (int32 / int64 ids, one per
+    entry: the distinct merge) a third tensor, the surviving entries' group ids i32[B,k] (-1 in the tail).
+    Lists of unequal k_i are padded to the longest with missing entries; a list longer than one launch ranks (4096 entries) is cut
+    into several. When all lists together exceed 4096 entries per query they are merged in ROUNDS: as many lists as fit go to one
+    list of k, and those lists are merged again, the group ids travelling between rounds in the kernel's out_groups. The rounds are
+    exact for both modes: a merged list is the (distinct) top-k of the union of its inputs, so it stands in for a shard in the proof
+    in merge_topk_distinct_host's docstring (plain: the top-k of a union lies in the union of the parts' top-k)."""
+    if len(scores_parts) == 0 or len(scores_parts) != len(idx_parts) or (group_parts is not None and len(group_parts) != len(idx_parts)):
+        raise ValueError("merge_topk_device: need one or more lists, and as many index (and group) lists as score lists")
+    nmax = ops.nat.MERGE_NMAX
+    ss = [x for t in scores_parts for x in t.split(nmax, dim=1)]
+    ii = [x for t in idx_parts for x in t.split(nmax, dim=1)]
+    gg = None if group_parts is None else [x for t in group_parts for x in t.to(torch.int32).split(nmax, dim=1)]
+    kin = max(t.shape[1] for t in ss)
+
+    def stacked(parts, fill, dtype):
+        out = torch.full((len(parts), parts[0].shape[0], kin), fill, dtype=dtype, device=parts[0].device)
+        for p, t in enumerate(parts):
+            out[p, :, :t.shape[1]] = t
+        return out
+
+    if all(t.shape[1] == kin for t in ss):
+        s, i, g = torch.stack(ss), torch.stack(ii), None if gg is None else torch.stack(gg)
+    else:
+        s, i = stacked(ss, float("-inf"), torch.float32), stacked(ii, -1, torch.int64)
+        g = None if gg is None else stacked(gg, -1, torch.int32)
+    out_s, out_i, out_g = _merge_stacked(s, i, g, k)
+    return (out_s, out_i) if group_parts is None else (out_s, out_i, out_g)
+
+
 def groups_of(idx, groups):
     """Global row ids -> group ids: idx i64[B,k] (as the searches return them; -1 = missing, stays -1), groups: one id per gallery
     row (the whole gallery, e.g. dataloader.gallery_labels(csv, column="Query_img")). Image-level Recall@K is then
@@ -154,6 +198,97 @@ class GalleryShard:
             if query_labels is None:
                 return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
             return ops.similarity_topk_filtered(q, self.rows, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
+
+
+class GallerySet:
+    """Several GalleryShard segments on ONE device, searched as one gallery: a gallery that grows (index today's images as a new
+    segment: add(); retire a segment: drop()) without concatenating the resident rows. The segments own pairwise disjoint global row
+    ranges [offset, offset + len), share the embedding width and either all carry labels (groups) or none does; their row dtypes may
+    differ. A search runs every non-empty segment and merges the lists on the device (merge_topk_device): the result stays there.
+    For segments of one dtype it equals bitwise the search of a single GalleryShard over the concatenated rows, because a row's
+    chain score does not depend on which rows share its shard. A set can stand in for a shard in distributed_search (a rank that
+    owns several segments)."""
+
+    def __init__(self, shards=()):
+        self._segments = []
+        for sh in shards:
+            self.add(sh)
+
+    def add(self, shard):
+        lo, hi = int(shard.offset), int(shard.offset) + len(shard)
+        for other in self._segments:
+            if shard.rows.device != other.rows.device:
+                raise ValueError(f"GallerySet: segment on {shard.rows.device}, the set lives on {other.rows.device}")
+            if shard.rows.shape[1] != other.rows.shape[1]:
+                raise ValueError(f"GallerySet: segment of width {shard.rows.shape[1]}, the set has width {other.rows.shape[1]}")
+            if (shard.labels is None) != (other.labels is None) or (shard.groups is None) != (other.groups is None):
+                raise ValueError("GallerySet: labels (and likewise groups) must be present on all segments or on none")
+            olo, ohi = int(other.offset), int(other.offset) + len(other)
+            if lo < ohi and olo < hi:
+                raise ValueError(f"GallerySet: rows [{lo}, {hi}) overlap the segment [{olo}, {ohi})")
+            if lo == olo:
+                raise ValueError(f"GallerySet: a segment already starts at offset {lo}")   # (an empty one: drop() names segments by offset)
+        self._segments.append(shard)
+        self._segments.sort(key=lambda sh: int(sh.offset))
+
+    def drop(self, offset: int):
+        """Remove and return the segment that starts at `offset`; KeyError if none does."""
+        for n, sh in enumerate(self._segments):
+            if int(sh.offset) == int(offset):
+                return self._segments.pop(n)
+        raise KeyError(offset)
+
+    def __len__(self):
+        return sum(len(sh) for sh in self._segments)
+
+    @property
+    def segments(self):
+        return list(self._segments)
+
+    @property
+    def rows(self):
+        """A zero-row view [0, C] of the first segment: the set has no single row matrix; this carries its device and width."""
+        if not self._segments:
+            raise ValueError("GallerySet: an empty set has no device yet")
+        return self._segments[0].rows[:0]
+
+    @property
+    def labels(self):
+        return [sh.labels for sh in self._segments] if self._segments and self._segments[0].labels is not None else None
+
+    @property
+    def groups(self):
+        return [sh.groups for sh in self._segments] if self._segments and self._segments[0].groups is not None else None
+
+    def entry_groups(self, idx: torch.Tensor) -> torch.Tensor:
+        """Group ids (int32, same shape, on idx's device) of global row ids out of any segment; -1 for missing entries."""
+        g = torch.full(idx.shape, -1, dtype=torch.int32, device=idx.device)
+        for sh in self._segments:
+            if len(sh):
+                inside = (idx >= int(sh.offset)) & (idx < int(sh.offset) + len(sh))
+                g = torch.where(inside, _entry_groups(sh, torch.where(inside, idx, torch.full_like(idx, -1))), g)
+        return g
+
+    def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq", distinct: bool = False):
+        """GalleryShard.search over all segments: (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU. One search per non-empty segment
+        and one device merge; a single non-empty segment's result is returned as it is; no segment with rows: the all-missing lists.
+        distinct: the segments' entry group ids are gathered on the device and the merge keeps the best entry per group."""
+        live = [sh for sh in self._segments if len(sh)]
+        if distinct and self._segments and self.groups is None:
+            raise ValueError("GallerySet.search: distinct=True but the segments have no group ids")
+        if query_labels is not None and self._segments and self.labels is None:
+            raise ValueError("GallerySet.search: query_labels given but the segments have no row labels")
+        if not live:
+            q = queries.reshape(-1, queries.shape[-1])
+            dev = self._segments[0].rows.device if self._segments else q.device
+            return (torch.full((q.shape[0], k), float("-inf"), device=dev), torch.full((q.shape[0], k), -1, dtype=torch.int64, device=dev))
+        res = [sh.search(queries, k, query_labels=query_labels, mode=mode, distinct=distinct) for sh in live]
+        if len(live) == 1:
+            return res[0]
+        with torch.cuda.device(live[0].rows.device):
+            if distinct:
+                return merge_topk_device([r[0] for r in res], [r[1] for r in res], k, [_entry_groups(sh, r[1]) for sh, r in zip(live, res)])[:2]
+            return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):
@@ -247,7 +382,7 @@ def _to_host_async(t: torch.Tensor):
 
 def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int, group=None, max_local: int | None = None,
                        dst: int | None = 0, timing: list | None = None, always_collective: bool = False, defer: bool = False,
-                       query_labels=None, filter_mode: str = "eq", distinct: bool = False):
+                       query_labels=None, filter_mode: str = "eq", distinct: bool = False, merge: str = "host"):
     """All ranks call this with their own queries [B_local, C] and their gallery shard.
 
     Two collectives in all, as BASELINE.json's north_star describes it:
@@ -278,8 +413,17 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     regions may sit in two of them: every rank searches with distinct=True, its packed list carries a fourth int32 per entry, the
     entry's group id (gathered on the device from shard.groups), and the host merge keeps the best entry per non-negative group id
     before it cuts to k (merge_topk_distinct_host has the proof). Still two collectives and one device-to-host copy; defer works.
-    Without it the payloads, the [B,k,3] packing and the calls to shard.search are exactly as above."""
+    Without it the payloads, the [B,k,3] packing and the calls to shard.search are exactly as above.
+    merge: "host" (default) is the path described above. "device" (RCCL groups only; under gloo the lists are host copies: ValueError
+    on every rank before any collective): the merging rank(s) unpack the gathered lists and merge ALL world * max_local slots on the GPU
+    (merge_topk_device's kernel; plain or distinct), so the one device-to-host copy carries [slots, k] scores and indices plus the
+    per-rank counts instead of `world` lists per slot, and the host only drops the slots beyond each rank's count. Same results,
+    bitwise; defer, dst=None, query_labels and distinct work as before; the single-rank shortcut's lists are final either way.
+    shard: a GalleryShard, or a GallerySet for a rank that owns several segments (anything with .search, .rows.device, .groups and
+    either .offset or an entry_groups(idx) method)."""
     import torch.distributed as dist
+    if merge not in ("host", "device"):
+        raise ValueError(f"distributed_search: merge must be 'host' or 'device', got {merge!r}")
     if distinct and getattr(shard, "groups", None) is None:
         raise ValueError("distributed_search: distinct=True but the shard has no group ids")
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
@@ -301,6 +445,8 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         raise ValueError(f"distributed_search: {b_local} local queries exceed max_local={cap}")
     dev = shard.rows.device
     host_coll = dist.get_backend(group) == "gloo"               # CPU rehearsal backend: collectives on host copies
+    if host_coll and merge == "device":                          # (the same on every rank: nobody is left waiting in a collective)
+        raise ValueError("distributed_search: merge='device' needs a device backend (nccl / RCCL); under gloo the gathered lists are host copies")
     cdev = torch.device("cpu") if host_coll else dev
     width = C if query_labels is None else C + 1                  # filtered: column C carries each query's label (int32 bits)
     block = torch.zeros((cap + 1, width), dtype=torch.float32, device=cdev)
@@ -331,7 +477,8 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode)
     packed = _pack_lists(s, i)
     if distinct:                                                 # [slots,k,4]: + the entry's group id
-        packed = torch.cat([packed, _entry_groups(shard, i).unsqueeze(-1)], dim=-1)
+        eg = shard.entry_groups(i) if hasattr(shard, "entry_groups") else _entry_groups(shard, i)    # (a GallerySet looks up its segments)
+        packed = torch.cat([packed, eg.unsqueeze(-1)], dim=-1)
     packed = packed.to(cdev)
     if marks:
         marks.mark()
@@ -351,6 +498,8 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         parts = torch.stack(glist, dim=0)
     # the ONE device-to-host copy: lists of all shards + the per-rank counts (as int32) in one buffer
     counts_i = allb[:, cap, 0].to(torch.int32)
+    if merge == "device":
+        return _finish_device_merge(parts, counts_i, k, cap, distinct, defer)
     flat = torch.cat([parts.reshape(-1), counts_i.to(parts.device)])
     pshape = tuple(parts.shape)
 
@@ -364,6 +513,28 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         if distinct:
             return merge_topk_distinct_host(list(ps[:, keep]), list(pi[:, keep]), list(lists[..., 3][:, keep]), k)
         return merge_topk_host(list(ps[:, keep]), list(pi[:, keep]), k)
+
+    if defer:
+        host, ev = _to_host_async(flat)
+        return PendingSearch(lambda: finish(host), ev)
+    return finish(flat.cpu())
+
+
+def _finish_device_merge(parts, counts_i, k, cap, distinct, defer):
+    """distributed_search(merge="device") on a merging rank: parts int32 [world, slots, k, 3|4] (the gathered packed lists, on the GPU) are
+    merged there for every slot; ONE copy takes [slots, k] indices and scores and the per-rank counts (all as int32) to the host."""
+    world, n = parts.shape[0], parts.shape[1] * k
+    ps, pi = _unpack_lists(parts[..., :3])
+    with torch.cuda.device(parts.device):
+        ms, mi, _ = _merge_stacked(ps, pi, parts[..., 3].contiguous() if distinct else None, k)
+    flat = torch.cat([mi.view(torch.int32).reshape(-1), ms.view(torch.int32).reshape(-1), counts_i.to(parts.device)])   # (the 8-byte indices first: aligned)
+
+    def finish(host):
+        counts = host[-world:].tolist()
+        if any(c < 0 or c > cap for c in counts):
+            raise RuntimeError(f"distributed_search: inconsistent per-rank query counts {counts} for max_local={cap}")
+        keep = torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
+        return host[2 * n:3 * n].view(torch.float32).view(-1, k)[keep], host[:2 * n].view(torch.int64).view(-1, k)[keep]
 
     if defer:
         host, ev = _to_host_async(flat)

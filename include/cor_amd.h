@@ -34,6 +34,7 @@ extern "C" {
 #define COR_TOPK_FORCE_GLOBAL_THRESHOLD 8 /* ... : never the two-launch local-threshold path of small shards (A/B partner, tests) */
 #define COR_TOPK_WAVE_FINAL 16 /* ... : global-threshold pipeline with the one-wave-per-query selection kernel fed from the records (slower A/B partner, tests) */
 #define COR_TOPK_KMAX 256     /* largest k cor_similarity_topk accepts (k > 32: the wide route, see below) */
+#define COR_MERGE_NMAX 4096   /* most entries per query (P * kin) one cor_merge_topk launch ranks */
 #define COR_FILTER_EQ 0       /* cor_similarity_topk_filtered: a row is allowed if its label equals the query's */
 #define COR_FILTER_NE 1       /* ... : a row is allowed if its label differs from the query's */
 
@@ -360,6 +361,31 @@ int cor_topk_distinct_sample_values(int Bq, int Ng, int k);
 int cor_similarity_topk_distinct(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                                  const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
                                  long long* out_idx, void* workspace, int flags, void* stream);
+
+/* Merge of top-k lists on the device: per query b, P lists of kin entries (what P calls of cor_similarity_topk[_filtered|_distinct] over P
+ * shards return, stacked) -> the k best entries of their union. scores f32 [P,Bq,kin], idx i64 [P,Bq,kin] (global row ids), groups NULL or
+ * i32 [P,Bq,kin] (one group id per entry), all contiguous; out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_groups NULL or i32 [Bq,k].
+ * Plain merge (groups == NULL): the P*kin entries of a query are ordered by (score desc, index asc). An entry with idx < 0 is MISSING: it
+ * ranks after every present entry whatever its score, while a present entry whose score is -inf still ranks ahead of the missing ones.
+ * The first k go out; positions past the number of present entries hold (-inf, -1). out_groups, if given, is filled with -1.
+ * Scores compare as floats (-0.0 and +0.0 tie and the index decides) and their bits are copied through unchanged; indices compare as full
+ * 64-bit values (g_offset is a long long: ids above 2^32 are legal). Preconditions: scores are finite or -inf; no row id occurs twice among
+ * one query's present entries (two equal (score, index) pairs keep the order of their positions in the stacked lists).
+ * Distinct merge (groups != NULL): after the same ranking an entry is dropped if an earlier-ranked present entry of the same query has the
+ * same NON-NEGATIVE group id (negative ids are never merged) and missing entries are dropped; the first k survivors go out, then the
+ * (-inf, -1) tail. out_groups receives the survivors' group ids (-1 in the tail), so a merged list can itself be merged again: a merged
+ * list is the (distinct) top-k of the union of its inputs.
+ * Both modes agree bitwise, scores and indices, with merge_topk_host / merge_topk_distinct_host of cor_amd/retrieval.py on lists as the
+ * searches return them (missing entries carry (-inf, -1)). Nothing is indexed with a missing entry's index or group value, which may be
+ * arbitrary. One launch, one block per query: a bitonic sort in LDS of 8-byte keys (order-preserving score key | position; the index is
+ * read through the position on ties), for distinct a second sort by (group id, rank) with head flags and a block scan.
+ * 1 <= k <= COR_TOPK_KMAX, kin >= 1, P >= 1, Bq >= 0 and non-null scores / idx / out_scores / out_idx, else COR_EINVAL; Bq == 0 is a
+ * successful no-op; P*kin > COR_MERGE_NMAX: COR_ENOSUPPORT (merge in rounds: retrieval.merge_topk_device). cor_merge_topk_workspace_bytes
+ * reports the same errors as negative values, as cor_topk_workspace_bytes does; the kernel needs no scratch memory today, so it returns 0
+ * for every supported shape and `workspace` may then be NULL. */
+long cor_merge_topk_workspace_bytes(int P, int Bq, int kin, int k);
+int cor_merge_topk(const float* scores, const long long* idx, const int* groups, int P, int Bq, int kin, int k, float* out_scores,
+                   long long* out_idx, int* out_groups, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
