@@ -71,9 +71,11 @@ SIGNATURES = {
     "cor_similarity_topk_distinct": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p, _p, _p, _i, _p],
     "cor_merge_topk_workspace_bytes": [_i, _i, _i, _i],
     "cor_merge_topk": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "cor_rescore_workspace_bytes": [_i, _i, _i],
+    "cor_rescore_topk": [_p, _p, _i, _i, _i, _i, _ll, _p, _i, _i, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
-            "cor_merge_topk_workspace_bytes": _l}
+            "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}
 
 _lib = None
 

@@ -592,6 +592,41 @@ def merge_topk(scores, idx, k, groups=None):
     return (out_s, out_i) if groups is None else (out_s, out_i, out_g)
 
 
+def rescore_topk(Q, G, cand, k, g_offset=0, return_pos=False):
+    """Re-score candidate lists on the device (cor_rescore_topk), the second stage of a two-stage search: Q f32 [Bq,C], G [Ng,C]
+    fp32/bf16/fp16 (the rows with global ids [g_offset, g_offset + Ng)), cand i64 [Bq,kin] global row ids -> (scores f32[Bq,k],
+    idx i64[Bq,k]) ordered by (score desc, id asc), and with return_pos a third tensor pos i32[Bq,k], each entry's position in its
+    input list (of a repeated id: the first occurrence). An id outside the shard (negative, another shard's, any 64-bit value) or
+    seen earlier in the same list is dropped; fewer than k left: the (-inf, -1, -1) tail. Scores are the fmaf-chain scores of
+    similarity_topk (16-bit galleries: the query rounded to the gallery dtype), so the list a search returned comes back bitwise.
+    1 <= k <= 256, 1 <= kin <= nat.MERGE_NMAX (4096; beyond that NativeError), C <= 256 and C % 16 == 0. No host synchronisation."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"rescore_topk: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if Q.dim() != 2 or G.dim() != 2 or Q.shape[1] != G.shape[1]:
+        raise ValueError(f"rescore_topk: Q must be [Bq, C] and G [Ng, C], got {tuple(Q.shape)} and {tuple(G.shape)}")
+    if Q.dtype != torch.float32 or G.dtype not in _DT:
+        raise ValueError(f"rescore_topk: Q must be float32 and G float32 / bfloat16 / float16, got {Q.dtype} and {G.dtype}")
+    if cand.dim() != 2 or cand.shape[0] != Q.shape[0] or cand.shape[1] < 1 or cand.dtype != torch.int64:
+        raise ValueError(f"rescore_topk: cand must be int64 [{Q.shape[0]}, kin] with kin >= 1, got {cand.dtype} {tuple(cand.shape)}")
+    _dev(Q, G, cand)
+    Q, G, cand = Q.contiguous(), G.contiguous(), cand.contiguous()
+    (Bq, C), Ng, kin = Q.shape, G.shape[0], cand.shape[1]
+    lib = _lib()
+    nbytes = lib.cor_rescore_workspace_bytes(Bq, kin, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_rescore_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device) if nbytes else None
+    out_s = torch.full((Bq, k), float("-inf"), dtype=torch.float32, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
+    out_i = torch.full((Bq, k), -1, dtype=torch.int64, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
+    out_p = None
+    if return_pos:
+        out_p = torch.full((Bq, k), -1, dtype=torch.int32, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.int32, device=Q.device)
+    if Bq and Ng:                                             # (no queries / no rows: empty tensors have no address to pass)
+        nat.check(lib.cor_rescore_topk(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, int(g_offset), cand.data_ptr(), kin, k, out_s.data_ptr(),
+                                       out_i.data_ptr(), _p(out_p) or None, _p(ws) or None, _s()), "cor_rescore_topk")
+    return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

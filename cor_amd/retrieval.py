@@ -13,6 +13,8 @@ lists go to one rank in ONE gather and are merged once on the host by (score des
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import ops
@@ -199,6 +201,19 @@ class GalleryShard:
                 return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
             return ops.similarity_topk_filtered(q, self.rows, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
 
+    def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int | None = None, return_pos: bool = False):
+        """The second stage of a two-stage search: queries f32[Bq,C], cand i64[Bq,kin] global row ids (a coarse search's idx, a union
+        of lists, the ids of known rows; at most 4096 per query) -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]) on the GPU: the
+        chain scores of the candidates this shard holds, ranked by (score desc, id asc), every id once (ops.rescore_topk). Ids outside
+        [offset, offset + len) are dropped; fewer than k left: the (-inf, -1[, -1]) tail. k defaults to min(kin, 256). pos: each
+        entry's position in its input list, to carry group ids or coarse scores along."""
+        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        if cand.dim() != 2:
+            raise ValueError(f"GalleryShard.rescore: cand must be [Bq, kin], got {tuple(cand.shape)}")
+        k = min(cand.shape[1], ops.nat.TOPK_KMAX) if k is None else k
+        with torch.cuda.device(self.rows.device) if self.rows.is_cuda else contextlib.nullcontext():
+            return ops.rescore_topk(q, self.rows, cand, k, g_offset=self.offset, return_pos=return_pos)
+
 
 class GallerySet:
     """Several GalleryShard segments on ONE device, searched as one gallery: a gallery that grows (index today's images as a new
@@ -289,6 +304,40 @@ class GallerySet:
             if distinct:
                 return merge_topk_device([r[0] for r in res], [r[1] for r in res], k, [_entry_groups(sh, r[1]) for sh, r in zip(live, res)])[:2]
             return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
+
+    def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int):
+        """GalleryShard.rescore over all segments: (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU. Every non-empty segment
+        re-scores the same cand; an id outside a segment is missing for it and the segments' ranges are disjoint, so every id is
+        scored exactly once, and the lists are merged on the device (merge_topk_device). A single non-empty segment's result is
+        returned as it is; no segment with rows: the all-missing lists. For segments of one dtype the result equals bitwise that of
+        a single GalleryShard over the concatenated rows."""
+        live = [sh for sh in self._segments if len(sh)]
+        if not live:
+            if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
+                raise ValueError(f"GallerySet.rescore: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
+            dev = self._segments[0].rows.device if self._segments else cand.device
+            return (torch.full((cand.shape[0], k), float("-inf"), device=dev), torch.full((cand.shape[0], k), -1, dtype=torch.int64, device=dev))
+        res = [sh.rescore(queries, cand, k) for sh in live]
+        if len(live) == 1:
+            return res[0]
+        with torch.cuda.device(live[0].rows.device):
+            return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
+
+
+def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int, fine_queries: torch.Tensor | None = None, **search_kwargs):
+    """Two-stage search on one device: coarse.search(queries, k_coarse, **search_kwargs) finds the candidates, fine.rescore(fine_queries
+    if given else queries, idx, k) orders them again and keeps k -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU, the scores being
+    `fine`'s chain scores. coarse and fine are each a GalleryShard or a GallerySet over the SAME global id space: typically a bf16 /
+    fp16 copy that is scanned on the matrix cores and the fp32 master rows, which give the final order at fp32 precision (the 16-bit
+    stage rounds the query to the gallery dtype too; the second stage takes it unrounded). fine_queries: another embedding of the same
+    requests for the second stage (e.g. the exact-query mode's fp32 feat). A candidate row that `fine` does not hold drops out; fewer
+    than k left: the (-inf, -1) tail. k <= k_coarse <= 256, else ValueError. search_kwargs go to the coarse search (query_labels, mode,
+    distinct). With distinct=True the COARSE stage fixes each group's representative row and the k_coarse groups; the second stage
+    re-orders those rows and does not look for a better row of a group. Nothing leaves the device and the host is not waited for."""
+    if not 1 <= int(k) <= int(k_coarse) <= ops.nat.TOPK_KMAX:
+        raise ValueError(f"two_stage_search: need 1 <= k <= k_coarse <= {ops.nat.TOPK_KMAX}, got k={k}, k_coarse={k_coarse}")
+    _, idx = coarse.search(queries, int(k_coarse), **search_kwargs)
+    return fine.rescore(queries if fine_queries is None else fine_queries, idx, int(k))
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):

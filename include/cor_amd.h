@@ -387,6 +387,34 @@ long cor_merge_topk_workspace_bytes(int P, int Bq, int kin, int k);
 int cor_merge_topk(const float* scores, const long long* idx, const int* groups, int P, int Bq, int kin, int k, float* out_scores,
                    long long* out_idx, int* out_groups, void* workspace, void* stream);
 
+/* Re-scoring of candidate lists (the second stage of a two-stage search): per query b a list of kin global row ids -> the chain score of
+ * every listed row this shard holds, ranked, every id once, the first k. Q f32 [Bq,C]; G [Ng,C] in g_dtype (COR_F32 / COR_BF16 / COR_F16),
+ * the shard's rows, global ids [g_offset, g_offset + Ng); cand i64 [Bq,kin], contiguous; out_scores f32 [Bq,k], out_idx i64 [Bq,k] (global
+ * ids), out_pos NULL or i32 [Bq,k].
+ * Entry j of query b is PRESENT if g_offset <= cand[b,j] < g_offset + Ng and no earlier position j' < j of the same query holds the same
+ * id; every other entry (negative ids, ids of other shards, repeats) is MISSING: it is dropped, and no address is ever derived from an id
+ * that has not passed the range test, so the ids may be arbitrary 64-bit values. The score of a present entry is the fmaf-chain score of
+ * cor_similarity_topk (oracle/c/sim_chain.c): the row's stored values widened exactly to fp32, for a 16-bit gallery the query rounded
+ * (nearest even) to the gallery dtype and widened back, acc = fmaf(row, query, acc) from 0 over k = 8c+i then 8c+4+i, c = 0 .. C/8-1,
+ * i = 0 .. 3. Every entry is scored with plain fmaf in that order; there is no approximate pass. Present entries are ordered by (score
+ * desc, global id asc); scores compare as floats (-0.0 and +0.0 tie and the id decides) and the first k go out with the score bits as
+ * computed. out_pos, if given, receives the entry's position j in the input list (of a repeated id: its first occurrence), so that a
+ * caller can carry group ids or coarse scores along. Positions past the number of present entries hold (-inf, -1, -1).
+ * Hence re-scoring the list a search returned against the gallery it searched gives that list back bitwise, whatever the order of the
+ * candidates; and the lists of several shards over disjoint id ranges, each re-scoring the same cand, merge (cor_merge_topk) into the
+ * list of one shard over all the rows.
+ * One launch, one block per query: the query in LDS, thread-per-candidate row gathers with 16-byte loads (four chains interleaved per
+ * thread), then the ranking of cor_merge_topk (bitonic sort in LDS of 8-byte keys, the id read through the position on ties), a keep flag
+ * where the rank before holds another id, and a block scan that places the first k survivors.
+ * 1 <= k <= COR_TOPK_KMAX, kin >= 1, Ng >= 0, Bq >= 0 and non-null Q / cand / out_scores / out_idx (G too unless Ng == 0), else
+ * COR_EINVAL; Bq == 0 is a successful no-op; kin > COR_MERGE_NMAX, C > 256 or C % 16 != 0, an unknown g_dtype: COR_ENOSUPPORT. All of
+ * these are decided before any HIP call. Q and G 16-byte aligned as for the searches. cor_rescore_workspace_bytes reports the errors it can
+ * see as negative values; the kernel needs no scratch memory today, so it returns 0 for every supported shape and `workspace` may then be
+ * NULL. No host synchronisation, no allocation; everything runs on `stream`. */
+long cor_rescore_workspace_bytes(int Bq, int kin, int k);
+int cor_rescore_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, long long g_offset, const long long* cand, int kin,
+                     int k, float* out_scores, long long* out_idx, int* out_pos, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
