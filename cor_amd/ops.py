@@ -627,6 +627,68 @@ def rescore_topk(Q, G, cand, k, g_offset=0, return_pos=False):
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
+def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, normalize=True, out_dtype=torch.float32, out=None):
+    """Query expansion on the device (cor_expand_queries; AQE / alpha-QE, and with query_weight = 0 over gallery rows: DBA).
+    Q f32 [Bq,C] (None is allowed when query_weight == 0), segments a list of (rows, offset): rows [n,C] fp32 / bf16 / fp16 holding the
+    global ids [offset, offset + n), at most nat.EXPAND_SEGMAX (16) of them, pairwise disjoint, dtypes free to differ; scores f32
+    [Bq,kin] and idx i64 [Bq,kin] as a search, the merge or the re-scoring return them -> [Bq,C] in out_dtype:
+    v = query_weight * Q; for j < m in list order, if idx[b,j] lies in a segment: v += max(scores[b,j], +0)^alpha * row; then
+    v / max(|v|, 1e-12) if normalize. Every step is one separately rounded fp32 operation in a fixed order (include/cor_amd.h has the
+    definition to the bit), so the result does not depend on how the rows are cut into segments. An id of no segment (-1, another
+    shard's, any 64-bit value) contributes nothing and its score is not read. 1 <= m <= min(kin, 256), 0 <= alpha <= 8, C <= 256 and
+    C % 16 == 0. out: an optional contiguous [Bq,C] tensor of out_dtype to write into. No host synchronisation; capturable in a graph."""
+    segments = [(r, int(o)) for r, o in segments]
+    if len(segments) > nat.EXPAND_SEGMAX:
+        raise ValueError(f"expand_queries: {len(segments)} segments, one call reads at most {nat.EXPAND_SEGMAX}")
+    if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:
+        raise ValueError(f"expand_queries: scores must be float32 [Bq, kin] with kin >= 1, got {scores.dtype} {tuple(scores.shape)}")
+    if idx.shape != scores.shape or idx.dtype != torch.int64:
+        raise ValueError(f"expand_queries: idx must be int64 {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
+    Bq, kin = scores.shape
+    if not 1 <= int(m) <= min(kin, nat.TOPK_KMAX):
+        raise ValueError(f"expand_queries: m must be in [1, min(kin, {nat.TOPK_KMAX})] (kin = {kin}), got {m}")
+    if int(alpha) != alpha or not 0 <= int(alpha) <= 8:
+        raise ValueError(f"expand_queries: alpha must be an integer in [0, 8], got {alpha}")
+    query_weight = float(query_weight)
+    if Q is None and query_weight != 0.0:
+        raise ValueError("expand_queries: Q may only be None with query_weight == 0")
+    if Q is None and not segments:
+        raise ValueError("expand_queries: neither queries nor segments: the width is unknown")
+    C = Q.shape[-1] if Q is not None else segments[0][0].shape[-1]
+    if Q is not None and (Q.dim() != 2 or Q.shape[0] != Bq or Q.dtype != torch.float32):
+        raise ValueError(f"expand_queries: Q must be float32 [{Bq}, C], got {Q.dtype} {tuple(Q.shape)}")
+    if C < 16 or C > 256 or C % 16 != 0:
+        raise ValueError(f"expand_queries: the width must be a multiple of 16 up to 256, got {C}")
+    if out_dtype not in _DT:
+        raise ValueError(f"expand_queries: out_dtype must be float32 / bfloat16 / float16, got {out_dtype}")
+    for r, o in segments:
+        if r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
+            raise ValueError(f"expand_queries: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+    spans = sorted((o, o + r.shape[0]) for r, o in segments if r.shape[0])
+    for (_, hi), (lo, _) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise ValueError("expand_queries: the segments' id ranges overlap")
+    if out is not None and (out.shape != (Bq, C) or out.dtype != out_dtype or not out.is_contiguous()):
+        raise ValueError(f"expand_queries: out must be a contiguous {out_dtype} [{Bq}, {C}] tensor")
+    dev = _dev(Q, scores, idx, out, *[r for r, _ in segments])
+    Q = Q.contiguous() if Q is not None else None
+    scores, idx = scores.contiguous(), idx.contiguous()
+    rows = [r.contiguous() for r, _ in segments]
+    if out is None:
+        out = torch.empty((Bq, C), dtype=out_dtype, device=dev)
+    n = len(segments)
+    c = nat.C
+    seg_rows = (c.c_void_p * max(n, 1))(*[r.data_ptr() or None for r in rows])
+    seg_off = (c.c_longlong * max(n, 1))(*[o for _, o in segments])
+    seg_n = (c.c_int * max(n, 1))(*[r.shape[0] for r in rows])
+    seg_dt = (c.c_int * max(n, 1))(*[_dt(r) for r in rows])
+    if Bq:                                                    # (no queries: empty tensors have no address to pass)
+        nat.check(_lib().cor_expand_queries(_p(Q) or None, query_weight, seg_rows, seg_off, seg_n, seg_dt, n, scores.data_ptr(), idx.data_ptr(),
+                                            Bq, kin, int(m), C, int(alpha), int(bool(normalize)), out.data_ptr(), _DT[out_dtype], _s()),
+                  "cor_expand_queries")
+    return out
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

@@ -214,6 +214,30 @@ class GalleryShard:
         with torch.cuda.device(self.rows.device) if self.rows.is_cuda else contextlib.nullcontext():
             return ops.rescore_topk(q, self.rows, cand, k, g_offset=self.offset, return_pos=return_pos)
 
+    def expand(self, queries, scores: torch.Tensor, idx: torch.Tensor, m: int, alpha: int = 3, query_weight: float = 1.0,
+               normalize: bool = True, out_dtype: torch.dtype = torch.float32, out=None):
+        """Query expansion over this shard's rows (ops.expand_queries): queries f32[Bq,C] (None with query_weight = 0), scores / idx
+        [Bq,kin] a list as search / rescore return it -> [Bq,C] in out_dtype on the GPU: query_weight * query + the sum over the first m
+        entries of max(score, 0)^alpha * row, L2-normalised if `normalize`. Entries this shard does not hold (-1, other shards' ids)
+        contribute nothing."""
+        q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        with torch.cuda.device(self.rows.device) if self.rows.is_cuda else contextlib.nullcontext():
+            return ops.expand_queries(q, [(self.rows, self.offset)], scores, idx, m, alpha=alpha, query_weight=query_weight,
+                                      normalize=normalize, out_dtype=out_dtype, out=out)
+
+    def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None, neighbours=None):
+        """Database-side augmentation: a NEW GalleryShard (same offset, labels and groups; rows in `dtype`, default this shard's) whose
+        every row is the expansion, with query_weight = 0, of the row's own top-m list over `neighbours` (a GalleryShard or GallerySet;
+        default: this shard, where a unit-norm row finds itself with score 1), normalised. `batch` rows are searched and expanded at a
+        time. This shard is left untouched."""
+        _check_expansion("GalleryShard.augmented", m=m, batch=batch)
+        nb = self if neighbours is None else neighbours
+        out = torch.empty(self.rows.shape, dtype=dtype or self.rows.dtype, device=self.rows.device)
+        for lo in range(0, len(self), int(batch)):
+            s, i = nb.search(self.rows[lo:lo + int(batch)], int(m))
+            nb.expand(None, s, i, int(m), alpha=alpha, query_weight=0.0, out_dtype=out.dtype, out=out[lo:lo + int(batch)])
+        return GalleryShard(out, offset=self.offset, labels=self.labels, groups=self.groups)
+
 
 class GallerySet:
     """Several GalleryShard segments on ONE device, searched as one gallery: a gallery that grows (index today's images as a new
@@ -323,6 +347,23 @@ class GallerySet:
         with torch.cuda.device(live[0].rows.device):
             return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
 
+    def expand(self, queries, scores: torch.Tensor, idx: torch.Tensor, m: int, alpha: int = 3, query_weight: float = 1.0,
+               normalize: bool = True, out_dtype: torch.dtype = torch.float32, out=None):
+        """GalleryShard.expand over all segments in ONE launch: the kernel looks every listed id up in the table of the live segments
+        (at most 16; their dtypes may differ), so nothing is concatenated and no per-segment partial sums exist. The result equals
+        bitwise that of a single GalleryShard over the concatenated rows."""
+        live = [sh for sh in self._segments if len(sh)]
+        dev = live[0].rows.device if live else scores.device
+        q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(dev, torch.float32).contiguous()
+        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+            return ops.expand_queries(q, [(sh.rows, sh.offset) for sh in live], scores, idx, m, alpha=alpha, query_weight=query_weight,
+                                      normalize=normalize, out_dtype=out_dtype, out=out)
+
+    def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
+        """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new
+        GallerySet of new segments; this set and its segments are left untouched."""
+        return GallerySet([sh.augmented(m, alpha=alpha, batch=batch, dtype=dtype, neighbours=self) for sh in self._segments])
+
 
 def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int, fine_queries: torch.Tensor | None = None, **search_kwargs):
     """Two-stage search on one device: coarse.search(queries, k_coarse, **search_kwargs) finds the candidates, fine.rescore(fine_queries
@@ -338,6 +379,30 @@ def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int,
         raise ValueError(f"two_stage_search: need 1 <= k <= k_coarse <= {ops.nat.TOPK_KMAX}, got k={k}, k_coarse={k_coarse}")
     _, idx = coarse.search(queries, int(k_coarse), **search_kwargs)
     return fine.rescore(queries if fine_queries is None else fine_queries, idx, int(k))
+
+
+def _check_expansion(who, m=1, k=1, rounds=1, batch=1):
+    if not 1 <= int(m) <= ops.nat.TOPK_KMAX or not 1 <= int(k) <= ops.nat.TOPK_KMAX:
+        raise ValueError(f"{who}: m and k must be in [1, {ops.nat.TOPK_KMAX}], got m={m}, k={k}")
+    if int(rounds) < 1 or int(batch) < 1:
+        raise ValueError(f"{who}: rounds and batch must be at least 1, got rounds={rounds}, batch={batch}")
+
+
+def expanded_search(queries: torch.Tensor, gallery, k: int, m: int, alpha: int = 3, query_weight: float = 1.0, rounds: int = 1, **search_kwargs):
+    """Search with query expansion on one device: `rounds` times q <- gallery.expand(q, *gallery.search(q, m, **search_kwargs), m)
+    (q starts as `queries`; each round expands the query of the round before), then gallery.search(q, k, **search_kwargs)
+    -> (scores f32[Bq,k], idx i64[Bq,k], expanded queries f32[Bq,C]) on the GPU. gallery: a GalleryShard or a GallerySet. alpha and
+    query_weight as in ops.expand_queries (alpha = 0, query_weight = 1: plain AQE); the expanded query is L2-normalised. 1 <= m <= 256,
+    1 <= k <= 256, rounds >= 1, else ValueError. search_kwargs (query_labels, mode, distinct) apply to EVERY search, so a filtered
+    expansion only sums rows the filter allows. Nothing leaves the device and the host is not waited for. distributed_search has no
+    such option: the rows to sum live on other ranks."""
+    _check_expansion("expanded_search", m=m, k=k, rounds=rounds)
+    q = queries
+    for _ in range(int(rounds)):
+        s, i = gallery.search(q, int(m), **search_kwargs)
+        q = gallery.expand(q, s, i, int(m), alpha=alpha, query_weight=query_weight)
+    s, i = gallery.search(q, int(k), **search_kwargs)
+    return s, i, q
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):

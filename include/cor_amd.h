@@ -415,6 +415,41 @@ long cor_rescore_workspace_bytes(int Bq, int kin, int k);
 int cor_rescore_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, long long g_offset, const long long* cand, int kin,
                      int k, float* out_scores, long long* out_idx, int* out_pos, void* workspace, void* stream);
 
+/* Query expansion (AQE, its weighted form alpha-QE) and, applied to gallery rows with query_weight = 0, database-side augmentation (DBA):
+ * per query b the weighted sum of the first m rows its list names plus the weighted query, optionally L2-normalised.
+ * Q f32 [Bq,C], may be NULL when query_weight == 0. seg_rows / seg_offset / seg_n / seg_dtype are HOST arrays of nseg entries: segment s
+ * holds the rows with global ids [seg_offset[s], seg_offset[s] + seg_n[s]) at the DEVICE pointer seg_rows[s], contiguous [seg_n[s], C] in
+ * seg_dtype[s] (COR_F32 / COR_BF16 / COR_F16; dtypes may differ between segments); the id ranges must be pairwise disjoint (the segments of
+ * a GallerySet, or the one of a GalleryShard). The launcher copies the table into a by-value kernel argument: no device allocation, no
+ * host-to-device copy, no host synchronisation; everything runs on `stream` and the call can be captured in a graph. scores f32 [Bq,kin]
+ * and idx i64 [Bq,kin], contiguous, are lists as the searches, the merge and the re-scoring return them; only the first m entries of each
+ * are used (1 <= m <= kin, m <= COR_TOPK_KMAX). out [Bq,C] in out_dtype (COR_F32 / COR_BF16 / COR_F16; the 16-bit forms are the f32 result
+ * rounded to nearest-even). Rows and Q 16-byte aligned as for the searches.
+ * Definition, fixed to the bit: every operation below is ONE IEEE fp32 operation, separately rounded, never contracted to an fma.
+ *   1. v[c] = query_weight * Q[b,c]; with query_weight == 0: v[c] = +0 and Q is not read.
+ *   2. for j = 0 .. m-1 IN THAT ORDER: id = idx[b,j] is PRESENT if some segment s has seg_offset[s] <= id < seg_offset[s] + seg_n[s] (the
+ *      difference is taken in unsigned arithmetic behind the test id >= seg_offset[s]; no address is formed from an id that failed, so ids
+ *      may be arbitrary 64-bit values). A missing entry contributes nothing and its score is never used. A present one:
+ *      t = scores[b,j] > 0 ? scores[b,j] : +0 (NaN, -0.0 and negative scores give +0); w = 1, then alpha times w = w * t (alpha == 0:
+ *      w = 1); x[c] = the stored row value widened exactly to fp32; v[c] = v[c] + (w * x[c]). The addition is performed even when
+ *      w == 0, and an id that occurs twice is added twice.
+ *   3. normalize != 0: s[c] = v[c] * v[c] for c < C and +0 for C <= c < 256; for h = 128, 64, .., 1: s[c] = s[c] + s[c+h] for all c < h;
+ *      d = sqrt(s[0]), raised to 1e-12f if smaller; out[c] = v[c] / d. A query with nothing to sum gives a zero row.
+ *   4. normalize == 0: out[c] = v[c].
+ * The order is by list position and the tree is over the channel index, so the result does not depend on how many segments hold the rows,
+ * on their order, on the dtype of rows that store the same values, or on the launch geometry: several segments give the bits of one
+ * segment over the concatenated rows.
+ * One launch, one wave per query and four queries per block; each lane owns four consecutive channels, so a row is one coalesced wave
+ * load; the loads of up to 8 list entries are issued before the first add; no LDS, no scratch, no global workspace.
+ * COR_EINVAL: a null scores / idx / out, a null segment array with nseg > 0, Bq < 0, kin < 1, m < 1, m > kin, alpha < 0, alpha > 8, nseg < 0,
+ * C < 1, a negative seg_n, a null seg_rows[s] with seg_n[s] > 0, a bad out_dtype, Q == NULL with a non-zero weight. COR_ENOSUPPORT:
+ * m > COR_TOPK_KMAX, nseg > COR_EXPAND_SEGMAX, C > 256 or C % 16 != 0, an unknown seg_dtype. All of these are decided before any HIP call.
+ * Bq == 0 is a successful no-op; nseg == 0 is legal (every entry is missing). */
+#define COR_EXPAND_SEGMAX 16
+int cor_expand_queries(const float* Q, float query_weight, const void* const* seg_rows, const long long* seg_offset, const int* seg_n,
+                       const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int m, int C, int alpha,
+                       int normalize, void* out, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
