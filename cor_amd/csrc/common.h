@@ -25,6 +25,12 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
   return __builtin_bit_cast(uint16_t, b);
 }
 
+// x rounded to the gallery element type TG and widened back: a query as a kernel that scans a TG gallery sees it
+template <typename TG> __device__ __forceinline__ float round_to(float x);
+template <> __device__ __forceinline__ float round_to<bf16_t>(float x) { return bf2f(f2bf(x)); }
+template <> __device__ __forceinline__ float round_to<_Float16>(float x) { return (float)(_Float16)x; }
+template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
+
 template <typename T> __device__ __forceinline__ float ld(const T* p);
 template <> __device__ __forceinline__ float ld<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float ld<bf16_t>(const bf16_t* p) { return bf2f(*p); }

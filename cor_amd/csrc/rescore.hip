@@ -43,11 +43,6 @@ __device__ __forceinline__ unsigned rs_key_score(u64 key) {
   return (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
 }
 
-template <typename TG> __device__ __forceinline__ float rs_round_to(float x);
-template <> __device__ __forceinline__ float rs_round_to<float>(float x) { return x; }
-template <> __device__ __forceinline__ float rs_round_to<bf16_t>(float x) { return bf2f(f2bf(x)); }
-template <> __device__ __forceinline__ float rs_round_to<_Float16>(float x) { return (float)(_Float16)x; }
-
 // elements [16 s, 16 s + 16) of a gallery row, widened exactly to fp32 (16-byte loads; rows are 16-byte aligned, C % 16 == 0)
 template <typename TG> __device__ __forceinline__ void rs_load16(const TG* __restrict__ row, int s, float (&g)[16]) {
   if constexpr (sizeof(TG) == 4) {
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(1024) void rescore_topk_kernel(const float* __restr
   const long long out0 = (long long)blockIdx.x * k;
   const RsList L{cand + (long long)blockIdx.x * kin};
 
-  for (int c = tid; c < C; c += T) qs[c] = rs_round_to<TG>(Q[(long long)blockIdx.x * C + c]);
+  for (int c = tid; c < C; c += T) qs[c] = round_to<TG>(Q[(long long)blockIdx.x * C + c]);
   if (tid == 0) s_present = 0;
   __syncthreads();
 

@@ -18,6 +18,7 @@
 // bf16 / fp16 gallery: v_mfma_f32_32x32x16_{bf16,f16}; Q is rounded to the gallery dtype in registers.
 // Everything up to the "WIDE k" section serves k <= 32; 33 <= k <= 256 takes the route of that section (launch_topk dispatches on k first).
 #include <limits.h>
+#include <algorithm>
 
 #include "common.h"
 
@@ -738,11 +739,6 @@ __global__ void __launch_bounds__(256) sim_prep(const float* __restrict__ Q, int
     dq[qblk * 32 + tid] = SIM_DELTA * fmaxf(1.f, sqrtf(n2));
   }
 }
-
-template <typename TG> __device__ __forceinline__ float round_to(float x);
-template <> __device__ __forceinline__ float round_to<bf16_t>(float x) { return bf2f(f2bf(x)); }
-template <> __device__ __forceinline__ float round_to<_Float16>(float x) { return (float)(_Float16)x; }
-template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
 
 // chain score of gallery row `idx` against the query in LDS (oracle/c/sim_chain.c order: chunk c of 8: k = 8c+i then 8c+4+i)
 template <typename TG>
@@ -2611,209 +2607,189 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   return p;
 }
 
-// FILTER: the filtered route (rlab / qlab / ne: cor_similarity_topk_filtered's labels and mode)
-template <typename TG, int QB, bool FILTER = false>
-int launch_wide_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long long g_offset, float* out_s, long long* out_i, char* w,
-                     const WidePlan& p, int flags, hipStream_t s, const int* rlab = nullptr, const int* qlab = nullptr, int ne = 0) {
+// One call of the wide family, as the entry points hand it to the launchers. grp: the distinct route's group ids (GROUP); rlab / qlab / ne:
+// the row labels, query labels and COR_FILTER_NE of the filtered route (FILTER); null / 0 where the route has none.
+struct WideCall {
+  const float* Q; int Bq, Ng, C, k; long long g_offset;
+  const int* grp; const int* rlab; const int* qlab; int ne;
+  float* out_s; long long* out_i; char* w; int flags; hipStream_t s;
+};
+
+// tau_q from the sample values. GROUP: reduced to one value per group first (sim_tau_distinct, with the rows behind the values).
+template <typename TG, bool GROUP>
+int launch_wide_tau(const WideCall& c, const WidePlan& p) {
+  const unsigned* sg = (const unsigned*)(c.w + p.off_sg); float* tau = (float*)(c.w + p.off_tau);
+  if constexpr (GROUP)
+    hipLaunchKernelGGL((sim_tau_distinct<TG>), dim3(c.Bq), dim3(256), 0, c.s, c.Q, c.C, sg, (const int*)(c.w + p.off_sgrow), p.ngroups, c.k, c.grp, tau);
+  else
+    hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(c.Bq), dim3(256), 0, c.s, c.Q, c.C, sg, p.ngroups, c.k, tau);
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+// the selection over the APPEND pass's streams: records (scan form) or entry lists (tile form). GROUP: one row per group (sim_final_distinct).
+template <typename TG, bool RECORDS, bool FILTER, bool GROUP>
+int launch_wide_final(const TG* G, const WideCall& c, const WidePlan& p) {
+  static DevOnce once;
+  const float* tau = (const float*)(c.w + p.off_tau); const int* cnt = (const int*)(c.w + p.off_cnt);
+  const float* rec_s = RECORDS ? (const float*)(c.w + p.off_recs) : nullptr; const int* rec_g = RECORDS ? (const int*)(c.w + p.off_recg) : nullptr;
+  const uint2* lst = RECORDS ? nullptr : (const uint2*)(c.w + p.off_recs);
+  const int no_fallback = (c.flags & COR_TOPK_NO_FALLBACK) ? 1 : 0;
+  if constexpr (GROUP) {
+    cor_max_dyn_lds((const void*)sim_final_distinct<TG, RECORDS>, (int)FINAL_DISTINCT_LDS, once);
+    hipLaunchKernelGGL((sim_final_distinct<TG, RECORDS>), dim3(c.Bq), dim3(256), FINAL_DISTINCT_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, tau, cnt,
+                       p.nstreams, p.cap, rec_s, rec_g, lst, c.grp, c.out_s, c.out_i, no_fallback, c.rlab, c.qlab, c.ne);
+  } else {
+    cor_max_dyn_lds((const void*)sim_final_wide<TG, RECORDS, FILTER>, (int)FINAL_WIDE_LDS, once);
+    hipLaunchKernelGGL((sim_final_wide<TG, RECORDS, FILTER>), dim3(c.Bq), dim3(256), FINAL_WIDE_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, tau, cnt,
+                       p.nstreams, p.cap, rec_s, rec_g, lst, c.out_s, c.out_i, no_fallback, c.rlab, c.qlab, c.ne);
+  }
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+// The scan form (16-bit, C = 256): sim_prep, SAMPLE, tau, APPEND, selection. GROUP changes the sample (it keeps the rows, sgrow), the
+// threshold and the selection; the APPEND scan is the wide / filtered instantiation unchanged (it appends scores >= tau_q whatever the
+// groups are).
+template <typename TG, int QB, bool FILTER, bool GROUP>
+int launch_wide_scan(const TG* G, const WideCall& c, const WidePlan& p) {
   constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
-  static DevOnce once_s, once_a, once_f;
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER>, (int)lds, once_s);
+  static DevOnce once_s, once_a;
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER, GROUP>, (int)lds, once_s);
   cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER>, (int)lds, once_a);
-  cor_max_dyn_lds((const void*)sim_final_wide<TG, true, FILTER>, (int)FINAL_WIDE_LDS, once_f);
-  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
-  int* cnt = (int*)(w + p.off_cnt); float* rec_s = (float*)(w + p.off_recs); int* rec_g = (int*)(w + p.off_recg);
-  uint4* qimg = (uint4*)(w + p.off_img);
+  unsigned* sg = (unsigned*)(c.w + p.off_sg);
+  uint4* qimg = (uint4*)(c.w + p.off_img);
   const int Bqp = p.nqg * 256 * QB;
-  hipLaunchKernelGGL((sim_prep<TG>), dim3(p.nqg * 8 * QB), dim3(256), 0, s, Q, Bq, qimg, (int*)(w + p.off_flags), (int*)(w + p.off_ovf), sg, Bqp,
-                     (float*)(w + p.off_dq));
+  hipLaunchKernelGGL((sim_prep<TG>), dim3(p.nqg * 8 * QB), dim3(256), 0, c.s, c.Q, c.Bq, qimg, (int*)(c.w + p.off_flags), (int*)(c.w + p.off_ovf), sg,
+                     Bqp, (float*)(c.w + p.off_dq));
   COR_CHECK_LAUNCH();
   ScanArgs a{};
-  a.Bq = Bq; a.Ng = Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups;
-  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
+  a.Bq = c.Bq; a.Ng = c.Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups;
+  if constexpr (GROUP) a.sgrow = (int*)(c.w + p.off_sgrow);
+  a.rlab = c.rlab; a.qlab = c.qlab; a.ne = c.ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
+    hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER, GROUP>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, c.s, G, a);
     COR_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, 256, sg, p.ngroups, k, tau);
-  COR_CHECK_LAUNCH();
+  if (const int e = launch_wide_tau<TG, GROUP>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
-  a.k = k; a.tau = tau; a.cnt = cnt; a.rec_s = rec_s; a.rec_g = rec_g; a.cap = p.cap; a.tau_add = 0.f;
-  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
+  a.k = c.k; a.tau = (float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.rec_s = (float*)(c.w + p.off_recs);
+  a.rec_g = (int*)(c.w + p.off_recg); a.cap = p.cap; a.tau_add = 0.f;
+  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, c.s, G, a);
   COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_wide<TG, true, FILTER>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     rec_s, rec_g, nullptr, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
-  COR_CHECK_LAUNCH();
-  return 0;
+  return launch_wide_final<TG, true, FILTER, GROUP>(G, c, p);
 }
 
-template <typename TG, bool FILTER = false>
-int launch_wide_tiles(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i, char* w,
-                      const WidePlan& p, int flags, hipStream_t s, const int* rlab = nullptr, const int* qlab = nullptr, int ne = 0) {
-  static DevOnce once_f;
-  cor_max_dyn_lds((const void*)sim_final_wide<TG, false, FILTER>, (int)FINAL_WIDE_LDS, once_f);
-  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
-  int* cnt = (int*)(w + p.off_cnt); uint2* lst = (uint2*)(w + p.off_recs);
+// the tile form (fp32, or C != 256): the same steps on sim_wide_scan and its entry lists, without a query image
+template <typename TG, bool FILTER, bool GROUP>
+int launch_wide_tiles(const TG* G, const WideCall& c, const WidePlan& p) {
   WideScanArgs a{};
-  a.Bq = Bq; a.Ng = Ng; a.C = C; a.nqt = p.nqt; a.sg = sg; a.ngroups = p.ngroups;
-  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
+  a.Bq = c.Bq; a.Ng = c.Ng; a.C = c.C; a.nqt = p.nqt; a.sg = (unsigned*)(c.w + p.off_sg); a.ngroups = p.ngroups;
+  if constexpr (GROUP) a.sgrow = (int*)(c.w + p.off_sgrow);
+  a.rlab = c.rlab; a.qlab = c.qlab; a.ne = c.ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
+    hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER, GROUP>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, c.s, c.Q, G, a);
     COR_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(Bq), dim3(256), 0, s, Q, C, sg, p.ngroups, k, tau);
-  COR_CHECK_LAUNCH();
+  if (const int e = launch_wide_tau<TG, GROUP>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
-  a.tau = tau; a.cnt = cnt; a.lst = lst; a.cap = p.cap;
-  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
+  a.tau = (float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.lst = (uint2*)(c.w + p.off_recs); a.cap = p.cap;
+  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, c.s, c.Q, G, a);
   COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_wide<TG, false, FILTER>), dim3(Bq), dim3(256), FINAL_WIDE_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     nullptr, nullptr, lst, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
-  COR_CHECK_LAUNCH();
-  return 0;
+  return launch_wide_final<TG, false, FILTER, GROUP>(G, c, p);
+}
+
+// The three routes of the wide family: wide (33 <= k <= COR_TOPK_KMAX), filtered (FILTER, every k) and distinct groups (GROUP, every k,
+// with or without a filter). 16-bit galleries with C = 256 take the scan form, everything else the tile form.
+template <bool FILTER, bool GROUP, typename TG>
+int launch_wide(const TG* G, const WideCall& c) {
+  if constexpr (sizeof(TG) == 2) {
+    if (c.C == 256) {
+      const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, FILTER, GROUP);
+      if (p.qb == 2) return launch_wide_scan<TG, 2, FILTER, GROUP>(G, c, p);
+      return launch_wide_scan<TG, 1, FILTER, GROUP>(G, c, p);
+    }
+  }
+  return launch_wide_tiles<TG, FILTER, GROUP>(G, c, make_wide(c.Bq, c.Ng, c.k, false, FILTER, GROUP));
 }
 
 template <typename TG>
-int launch_wide(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i, char* w,
-                int flags, hipStream_t s) {
-  if constexpr (sizeof(TG) == 2) {
-    if (C == 256) {
-      const WidePlan p = make_wide(Bq, Ng, k, true);
-      if (p.qb == 2) return launch_wide_scan<TG, 2>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s);
-      return launch_wide_scan<TG, 1>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s);
-    }
-  }
-  return launch_wide_tiles<TG>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false), flags, s);
-}
-
-// the filtered route: every k (1 .. COR_TOPK_KMAX) on the wide route's kernels with FILTER set
-template <typename TG>
-int launch_filtered(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* rlab, const int* qlab, int ne,
-                    float* out_s, long long* out_i, char* w, int flags, hipStream_t s) {
-  if constexpr (sizeof(TG) == 2) {
-    if (C == 256) {
-      const WidePlan p = make_wide(Bq, Ng, k, true, true);
-      if (p.qb == 2) return launch_wide_scan<TG, 2, true>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
-      return launch_wide_scan<TG, 1, true>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
-    }
-  }
-  return launch_wide_tiles<TG, true>(Q, G, Bq, Ng, C, k, g_offset, out_s, out_i, w, make_wide(Bq, Ng, k, false, true), flags, s, rlab, qlab, ne);
-}
-
-// the distinct-group route (every k): sample with rows (GROUP), sim_tau_distinct, the wide / filtered APPEND scan as it is, sim_final_distinct.
-// FILTER: rlab / qlab / ne as in launch_filtered; grp: the rows' group ids.
-template <typename TG, int QB, bool FILTER>
-int launch_distinct_scan(const float* Q, const TG* G, int Bq, int Ng, int k, long long g_offset, const int* grp, float* out_s, long long* out_i,
-                         char* w, const WidePlan& p, int flags, hipStream_t s, const int* rlab, const int* qlab, int ne) {
-  constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
-  static DevOnce once_s, once_a, once_f;
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER, true>, (int)lds, once_s);
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER>, (int)lds, once_a);
-  cor_max_dyn_lds((const void*)sim_final_distinct<TG, true>, (int)FINAL_DISTINCT_LDS, once_f);
-  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
-  int* cnt = (int*)(w + p.off_cnt); float* rec_s = (float*)(w + p.off_recs); int* rec_g = (int*)(w + p.off_recg);
-  uint4* qimg = (uint4*)(w + p.off_img);
-  const int Bqp = p.nqg * 256 * QB;
-  hipLaunchKernelGGL((sim_prep<TG>), dim3(p.nqg * 8 * QB), dim3(256), 0, s, Q, Bq, qimg, (int*)(w + p.off_flags), (int*)(w + p.off_ovf), sg, Bqp,
-                     (float*)(w + p.off_dq));
-  COR_CHECK_LAUNCH();
-  ScanArgs a{};
-  a.Bq = Bq; a.Ng = Ng; a.nqg = p.nqg; a.qimg = qimg; a.sg = sg; a.Bqp = p.ngroups; a.sgrow = (int*)(w + p.off_sgrow);
-  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
-  if (p.ngroups > 0) {
-    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER, true>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, s, G, a);
-    COR_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL((sim_tau_distinct<TG>), dim3(Bq), dim3(256), 0, s, Q, 256, sg, a.sgrow, p.ngroups, k, grp, tau);
-  COR_CHECK_LAUNCH();
-  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
-  a.k = k; a.tau = tau; a.cnt = cnt; a.rec_s = rec_s; a.rec_g = rec_g; a.cap = p.cap; a.tau_add = 0.f;
-  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, s, G, a);
-  COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_distinct<TG, true>), dim3(Bq), dim3(256), FINAL_DISTINCT_LDS, s, Q, G, Ng, 256, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     rec_s, rec_g, nullptr, grp, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
-  COR_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename TG, bool FILTER>
-int launch_distinct_tiles(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* grp, float* out_s, long long* out_i,
-                          char* w, const WidePlan& p, int flags, hipStream_t s, const int* rlab, const int* qlab, int ne) {
-  static DevOnce once_f;
-  cor_max_dyn_lds((const void*)sim_final_distinct<TG, false>, (int)FINAL_DISTINCT_LDS, once_f);
-  unsigned* sg = (unsigned*)(w + p.off_sg); float* tau = (float*)(w + p.off_tau);
-  int* cnt = (int*)(w + p.off_cnt); uint2* lst = (uint2*)(w + p.off_recs);
-  WideScanArgs a{};
-  a.Bq = Bq; a.Ng = Ng; a.C = C; a.nqt = p.nqt; a.sg = sg; a.ngroups = p.ngroups; a.sgrow = (int*)(w + p.off_sgrow);
-  a.rlab = rlab; a.qlab = qlab; a.ne = ne;
-  if (p.ngroups > 0) {
-    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER, true>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, s, Q, G, a);
-    COR_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL((sim_tau_distinct<TG>), dim3(Bq), dim3(256), 0, s, Q, C, sg, a.sgrow, p.ngroups, k, grp, tau);
-  COR_CHECK_LAUNCH();
-  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
-  a.tau = tau; a.cnt = cnt; a.lst = lst; a.cap = p.cap;
-  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, s, Q, G, a);
-  COR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((sim_final_distinct<TG, false>), dim3(Bq), dim3(256), FINAL_DISTINCT_LDS, s, Q, G, Ng, C, k, g_offset, tau, cnt, p.nstreams, p.cap,
-                     nullptr, nullptr, lst, grp, out_s, out_i, (flags & COR_TOPK_NO_FALLBACK) ? 1 : 0, rlab, qlab, ne);
-  COR_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename TG, bool FILTER>
-int launch_distinct(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, const int* grp, const int* rlab, const int* qlab,
-                    int ne, float* out_s, long long* out_i, char* w, int flags, hipStream_t s) {
-  if constexpr (sizeof(TG) == 2) {
-    if (C == 256) {
-      const WidePlan p = make_wide(Bq, Ng, k, true, FILTER, true);
-      if (p.qb == 2) return launch_distinct_scan<TG, 2, FILTER>(Q, G, Bq, Ng, k, g_offset, grp, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
-      return launch_distinct_scan<TG, 1, FILTER>(Q, G, Bq, Ng, k, g_offset, grp, out_s, out_i, w, p, flags, s, rlab, qlab, ne);
-    }
-  }
-  return launch_distinct_tiles<TG, FILTER>(Q, G, Bq, Ng, C, k, g_offset, grp, out_s, out_i, w, make_wide(Bq, Ng, k, false, FILTER, true), flags, s,
-                                           rlab, qlab, ne);
-}
-
-template <typename TG>
-int launch_topk(const float* Q, const void* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i,
+int launch_topk(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long long g_offset, float* out_s, long long* out_i,
                 void* workspace, int flags, hipStream_t s) {
-  if (k > 32) return launch_wide<TG>(Q, (const TG*)G, Bq, Ng, C, k, g_offset, out_s, out_i, (char*)workspace, flags, s);   // 33 <= k <= COR_TOPK_KMAX
+  if (k > 32)                                          // 33 <= k <= COR_TOPK_KMAX
+    return launch_wide<false, false>(G, WideCall{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_s, out_i, (char*)workspace, flags, s});
   float* ws_s = (float*)workspace;
   const bool force_lists = (flags & COR_TOPK_FORCE_LISTS) != 0;
   if constexpr (sizeof(TG) == 2) {
     if (C == 256 && !force_lists && !(flags & COR_TOPK_FORCE_GLOBAL_THRESHOLD)) {   // small shards: two launches, local thresholds
       const SmallPlan sp = make_small(Bq, Ng, k);
-      if (sp.ok) return launch_small<TG>(Q, (const TG*)G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, sp, flags, s);
+      if (sp.ok) return launch_small<TG>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, sp, flags, s);
     }
     if (C == 256 && !force_lists) {                     // threshold-and-append + exact re-scoring
       const V3Plan p = make_v3(Bq, Ng, k);
-      if (p.qb == 2) return launch_v3<TG, 2>(Q, (const TG*)G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, p, flags, s);
-      return launch_v3<TG, 1>(Q, (const TG*)G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, p, flags, s);
+      if (p.qb == 2) return launch_v3<TG, 2>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, p, flags, s);
+      return launch_v3<TG, 1>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, (char*)workspace, p, flags, s);
     }
-    if (C == 256) return launch_lists_v2<TG>(Q, (const TG*)G, Bq, Ng, k, g_offset, out_s, out_i, ws_s, nullptr, nullptr, s);
+    if (C == 256) return launch_lists_v2<TG>(Q, G, Bq, Ng, k, g_offset, out_s, out_i, ws_s, nullptr, nullptr, s);
   }
   const TopkPlan p = make_plan(Bq, Ng, k);
   int* ws_i = (int*)(ws_s + (long)Bq * p.nparts * p.kmax);
   const int nwaves = p.nqt * p.nsplit;
-  if (p.kmax == 8) hipLaunchKernelGGL((sim_topk_partial<TG, 8>), dim3(cdiv(nwaves, 4)), dim3(256), 0, s, Q, (const TG*)G, Bq, Ng, C, p, ws_s, ws_i);
-  else hipLaunchKernelGGL((sim_topk_partial<TG, 32>), dim3(cdiv(nwaves, 4)), dim3(256), 0, s, Q, (const TG*)G, Bq, Ng, C, p, ws_s, ws_i);
+  if (p.kmax == 8) hipLaunchKernelGGL((sim_topk_partial<TG, 8>), dim3(cdiv(nwaves, 4)), dim3(256), 0, s, Q, G, Bq, Ng, C, p, ws_s, ws_i);
+  else hipLaunchKernelGGL((sim_topk_partial<TG, 32>), dim3(cdiv(nwaves, 4)), dim3(256), 0, s, Q, G, Bq, Ng, C, p, ws_s, ws_i);
   COR_CHECK_LAUNCH();
   return launch_merge(ws_s, ws_i, Bq, p.nparts * p.kmax, k, g_offset, out_s, out_i, nullptr, s);
 }
 
+// the largest value of a plan field over the two forms of a route (the gallery's dtype and C choose the form at call time)
+template <typename T>
+long wide_max(int Bq, int Ng, int k, bool filter, bool group, T WidePlan::*field) {
+  const long a = (long)(make_wide(Bq, Ng, k, true, filter, group).*field), b = (long)(make_wide(Bq, Ng, k, false, filter, group).*field);
+  return a > b ? a : b;
+}
+inline long wide_bytes(int Bq, int Ng, int k, bool filter, bool group) { return wide_max(Bq, Ng, k, filter, group, &WidePlan::bytes); }
+// the most sample values per query any plan of a distinct call hands sim_tau_distinct
+inline int distinct_sample_values(int Bq, int Ng, int k) {
+  return (int)std::max(wide_max(Bq, Ng, k, false, true, &WidePlan::ngroups), wide_max(Bq, Ng, k, true, true, &WidePlan::ngroups));
+}
+inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
+
+constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT };
+
+// The argument checks of the three search entry points, in the order (and with the codes) of the ABI. What differs by route: the
+// pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither), the A/B flags it refuses
+// (the plain call only at k > 32) and the distinct route's sample bound.
+int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
+  const bool own_ptrs = route == ROUTE_TOPK       ? true
+                        : route == ROUTE_FILTERED ? c.rlab && c.qlab
+                                                  : c.grp && (c.rlab == nullptr) == (c.qlab == nullptr);
+  if (!c.Q || !G || !own_ptrs || !c.out_s || !c.out_i || !c.w || c.Bq <= 0 || c.Ng <= 0 || c.k <= 0) return COR_EINVAL;
+  if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
+  if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
+  if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
+  if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
+  if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
+  return 0;
+}
+
+// f(typed gallery pointer) for the gallery's dtype
+template <typename F>
+int by_dtype(int g_dtype, const void* G, F f) {
+  switch (g_dtype) {
+    case COR_F32: return f((const float*)G);
+    case COR_BF16: return f((const bf16_t*)G);
+    case COR_F16: return f((const _Float16*)G);
+    default: return COR_ENOSUPPORT;
+  }
+}
 }  // namespace
 
 extern "C" long cor_topk_workspace_bytes(int Bq, int Ng, int k) {
-  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  if (k > 32) {                                        // the wide route: whichever form the gallery's dtype and C select
-    const long a = (long)make_wide(Bq, Ng, k, true).bytes, b = (long)make_wide(Bq, Ng, k, false).bytes;
-    return a > b ? a : b;
-  }
+  if (!topk_shape_ok(Bq, Ng, k)) return COR_EINVAL;
+  if (k > 32) return wide_bytes(Bq, Ng, k, false, false);   // the wide route: whichever form the gallery's dtype and C select
   const TopkPlan p = make_plan(Bq, Ng, k);
   const TopkPlan2 p2 = make_plan2(Bq, Ng, k, device_cus());
   const long a = (long)Bq * p.nparts * p.kmax * 8, b = (long)Bq * p2.nparts * p2.kmax * 8;
@@ -2826,95 +2802,40 @@ extern "C" long cor_topk_workspace_bytes(int Bq, int Ng, int k) {
 
 extern "C" int cor_similarity_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                                    float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
-  if (!Q || !G || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
-  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
-  if (k > 32 && (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL))) return COR_ENOSUPPORT;   // register-list / one-wave kernels: k <= 32
-  if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)workspace & 255)) return COR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  switch (g_dtype) {
-    case COR_F32: return launch_topk<float>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
-    case COR_BF16: return launch_topk<bf16_t>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
-    case COR_F16: return launch_topk<_Float16>(Q, G, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, s);
-    default: return COR_ENOSUPPORT;
-  }
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream};
+  if (const int e = check_topk_call(ROUTE_TOPK, c, G, COR_FILTER_EQ)) return e;
+  return by_dtype(g_dtype, G, [&](auto* g) { return launch_topk(Q, g, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, c.s); });
 }
 
 extern "C" long cor_topk_filtered_workspace_bytes(int Bq, int Ng, int k) {
-  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  const long a = (long)make_wide(Bq, Ng, k, true, true).bytes, b = (long)make_wide(Bq, Ng, k, false, true).bytes;
-  return a > b ? a : b;
+  return topk_shape_ok(Bq, Ng, k) ? wide_bytes(Bq, Ng, k, true, false) : COR_EINVAL;
 }
 
+// filtered calls always take the wide route (every k)
 extern "C" int cor_similarity_topk_filtered(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                                             const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
                                             long long* out_idx, void* workspace, int flags, void* stream) {
-  if (!Q || !G || !row_labels || !query_labels || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
-  if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
-  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
-  if (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL)) return COR_ENOSUPPORT;     // filtered calls always take the wide route
-  if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)row_labels & 15) || ((uintptr_t)workspace & 255)) return COR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int ne = filter_mode == COR_FILTER_NE ? 1 : 0;
-  char* w = (char*)workspace;
-  switch (g_dtype) {
-    case COR_F32: return launch_filtered<float>(Q, (const float*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
-    case COR_BF16: return launch_filtered<bf16_t>(Q, (const bf16_t*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
-    case COR_F16: return launch_filtered<_Float16>(Q, (const _Float16*)G, Bq, Ng, C, k, g_offset, row_labels, query_labels, ne, out_scores, out_idx, w, flags, s);
-    default: return COR_ENOSUPPORT;
-  }
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, row_labels, query_labels, filter_mode == COR_FILTER_NE ? 1 : 0, out_scores, out_idx,
+                   (char*)workspace, flags, (hipStream_t)stream};
+  if (const int e = check_topk_call(ROUTE_FILTERED, c, G, filter_mode)) return e;
+  return by_dtype(g_dtype, G, [&](auto* g) { return launch_wide<true, false>(g, c); });
 }
 
 extern "C" long cor_topk_distinct_workspace_bytes(int Bq, int Ng, int k) {
-  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  long m = 0;
-  for (int scan = 0; scan < 2; ++scan)
-    for (int filter = 0; filter < 2; ++filter) {
-      const long b = (long)make_wide(Bq, Ng, k, scan != 0, filter != 0, true).bytes;
-      if (b > m) m = b;
-    }
-  return m;
-}
-
-static int distinct_sample_values(int Bq, int Ng, int k) {
-  int m = 0;
-  for (int scan = 0; scan < 2; ++scan)
-    for (int filter = 0; filter < 2; ++filter) {
-      const int g = make_wide(Bq, Ng, k, scan != 0, filter != 0, true).ngroups;
-      if (g > m) m = g;
-    }
-  return m;
+  return topk_shape_ok(Bq, Ng, k) ? std::max(wide_bytes(Bq, Ng, k, false, true), wide_bytes(Bq, Ng, k, true, true)) : COR_EINVAL;
 }
 
 extern "C" int cor_topk_distinct_sample_values(int Bq, int Ng, int k) {
-  if (Bq <= 0 || Ng <= 0 || k <= 0 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  return distinct_sample_values(Bq, Ng, k);
+  return topk_shape_ok(Bq, Ng, k) ? distinct_sample_values(Bq, Ng, k) : COR_EINVAL;
 }
 
+// distinct calls always take the wide route (every k); the labels are optional: both or neither
 extern "C" int cor_similarity_topk_distinct(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, int k, long long g_offset,
                                             const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode,
                                             float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
-  if (!Q || !G || !row_groups || !out_scores || !out_idx || !workspace || Bq <= 0 || Ng <= 0 || k <= 0) return COR_EINVAL;
-  if ((row_labels == nullptr) != (query_labels == nullptr)) return COR_EINVAL;
   const bool filter = row_labels != nullptr;
-  if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
-  if (k > COR_TOPK_KMAX || C > 256 || (C & 15)) return COR_ENOSUPPORT;
-  if (flags & (COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL)) return COR_ENOSUPPORT;     // distinct calls always take the wide route
-  if (distinct_sample_values(Bq, Ng, k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;      // (the plan keeps it: sim_tau_distinct's LDS sort)
-  if (((uintptr_t)Q & 15) || ((uintptr_t)G & 15) || ((uintptr_t)row_groups & 15) || ((uintptr_t)row_labels & 15) || ((uintptr_t)workspace & 255))
-    return COR_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int ne = filter && filter_mode == COR_FILTER_NE ? 1 : 0;
-  char* w = (char*)workspace;
-#define COR_DISTINCT(TG_)                                                                                                                       \
-  return filter ? launch_distinct<TG_, true>(Q, (const TG_*)G, Bq, Ng, C, k, g_offset, row_groups, row_labels, query_labels, ne, out_scores,     \
-                                             out_idx, w, flags, s)                                                                             \
-                : launch_distinct<TG_, false>(Q, (const TG_*)G, Bq, Ng, C, k, g_offset, row_groups, nullptr, nullptr, 0, out_scores, out_idx,  \
-                                              w, flags, s)
-  switch (g_dtype) {
-    case COR_F32: COR_DISTINCT(float);
-    case COR_BF16: COR_DISTINCT(bf16_t);
-    case COR_F16: COR_DISTINCT(_Float16);
-    default: return COR_ENOSUPPORT;
-  }
-#undef COR_DISTINCT
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, row_groups, row_labels, query_labels, filter && filter_mode == COR_FILTER_NE ? 1 : 0, out_scores,
+                   out_idx, (char*)workspace, flags, (hipStream_t)stream};
+  if (const int e = check_topk_call(ROUTE_DISTINCT, c, G, filter_mode)) return e;
+  return by_dtype(g_dtype, G, [&](auto* g) { return filter ? launch_wide<true, true>(g, c) : launch_wide<false, true>(g, c); });
 }

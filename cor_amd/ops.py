@@ -448,6 +448,37 @@ def iou_select(iou, hyper, k_off, Ksel):
     return best, sel
 
 
+_FILTER_MODES = {"eq": nat.FILTER_EQ, "ne": nat.FILTER_NE}
+
+
+def _topk_front(who, Q, G, k, mode="eq", labels=None):
+    """The argument checks the similarity_topk* wrappers share, before anything touches the device: k, the filter mode, the label pair
+    (both or neither), then device, dtype and shapes. Returns (Bq, Ng, C)."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if mode not in _FILTER_MODES:
+        raise ValueError(f"{who}: mode must be 'eq' or 'ne', got {mode!r}")
+    if labels is not None and (labels[0] is None) != (labels[1] is None):
+        raise ValueError(f"{who}: row_labels and query_labels go together (both or neither)")
+    _dev(Q, G)
+    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
+    Bq, Cq = Q.shape
+    Ng, Cg = G.shape
+    assert Cq == Cg
+    return Bq, Ng, Cq
+
+
+def _topk_buffers(bytes_fn, Q, Bq, Ng, k):
+    """(workspace, scores f32[Bq,k], idx i64[Bq,k]) of one search; bytes_fn names the route's cor_topk*_workspace_bytes."""
+    nbytes = getattr(_lib(), bytes_fn)(Bq, Ng, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), bytes_fn)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)          # torch's allocator returns >= 256-B aligned blocks
+    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
+    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
+    return ws, scores, idx
+
+
 def similarity_topk(Q, G, k, g_offset=0, flags=0):
     """Top-k gallery rows per query by dot product; (score desc, index asc). Q fp32 [Bq,C]; G [Ng,C] fp32/bf16/fp16;
     1 <= k <= nat.TOPK_KMAX (256); Ng < k: the tail is (-inf, -1).
@@ -456,26 +487,11 @@ def similarity_topk(Q, G, k, g_offset=0, flags=0):
     gallery dtype and every C is bit-identical to that oracle. A candidate overflow (pathological score distributions) is
     repaired ON THE DEVICE: no host synchronisation here. flags: nat.TOPK_FORCE_LISTS | nat.TOPK_NO_FALLBACK (tests);
     TOPK_FORCE_LISTS and TOPK_WAVE_FINAL need k <= 32."""
-    if not 1 <= int(k) <= nat.TOPK_KMAX:
-        raise ValueError(f"similarity_topk: k must be in [1, {nat.TOPK_KMAX}], got {k}")
-    _dev(Q, G)
-    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
-    Bq, Cq = Q.shape
-    Ng, Cg = G.shape
-    assert Cq == Cg
-    lib = _lib()
-    nbytes = lib.cor_topk_workspace_bytes(Bq, Ng, k)
-    if nbytes < 0:
-        nat.check(int(nbytes), "cor_topk_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)          # torch's allocator returns >= 256-B aligned blocks
-    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
-    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
-    nat.check(lib.cor_similarity_topk(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), scores.data_ptr(),
-                                      idx.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_topk")
+    Bq, Ng, C = _topk_front("similarity_topk", Q, G, k)
+    ws, scores, idx = _topk_buffers("cor_topk_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, k, int(g_offset), scores.data_ptr(),
+                                         idx.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_topk")
     return scores, idx
-
-
-_FILTER_MODES = {"eq": nat.FILTER_EQ, "ne": nat.FILTER_NE}
 
 
 def _labels(t, n, name, device, who="similarity_topk_filtered"):
@@ -496,27 +512,13 @@ def similarity_topk_filtered(Q, G, k, row_labels, query_labels, mode="eq", g_off
     (exclude a source, e.g. the query's own image). row_labels int32[Ng], query_labels int32[Bq] (int64 is converted). 1 <= k <= 256
     for every gallery dtype and C; bit-identical to the chain oracle on the allowed rows; fewer than k allowed rows: the tail is
     (-inf, -1). No host synchronisation when the labels already live on the device. flags: nat.TOPK_NO_FALLBACK (tests)."""
-    if not 1 <= int(k) <= nat.TOPK_KMAX:
-        raise ValueError(f"similarity_topk_filtered: k must be in [1, {nat.TOPK_KMAX}], got {k}")
-    if mode not in _FILTER_MODES:
-        raise ValueError(f"similarity_topk_filtered: mode must be 'eq' or 'ne', got {mode!r}")
-    _dev(Q, G)
-    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
-    Bq, Cq = Q.shape
-    Ng, Cg = G.shape
-    assert Cq == Cg
+    Bq, Ng, C = _topk_front("similarity_topk_filtered", Q, G, k, mode)
     rl = _labels(row_labels, Ng, "row_labels", Q.device)
     qlab = _labels(query_labels, Bq, "query_labels", Q.device)
-    lib = _lib()
-    nbytes = lib.cor_topk_filtered_workspace_bytes(Bq, Ng, k)
-    if nbytes < 0:
-        nat.check(int(nbytes), "cor_topk_filtered_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)
-    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
-    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
-    nat.check(lib.cor_similarity_topk_filtered(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), rl.data_ptr(),
-                                               qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                                               int(flags), _s()), "cor_similarity_topk_filtered")
+    ws, scores, idx = _topk_buffers("cor_topk_filtered_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk_filtered(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, k, int(g_offset), rl.data_ptr(),
+                                                  qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                                  int(flags), _s()), "cor_similarity_topk_filtered")
     return scores, idx
 
 
@@ -528,31 +530,15 @@ def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=
     (both or neither; labels and group ids are separate vectors and may be the same tensor), e.g. mode "ne" with the query's own
     image id. 1 <= k <= 256 for every gallery dtype and C; bit-identical to "chain-rank the allowed rows, keep the first row of each
     group, keep the first k". No host synchronisation when the vectors already live on the device. flags: nat.TOPK_NO_FALLBACK."""
-    if not 1 <= int(k) <= nat.TOPK_KMAX:
-        raise ValueError(f"similarity_topk_distinct: k must be in [1, {nat.TOPK_KMAX}], got {k}")
-    if mode not in _FILTER_MODES:
-        raise ValueError(f"similarity_topk_distinct: mode must be 'eq' or 'ne', got {mode!r}")
-    if (row_labels is None) != (query_labels is None):
-        raise ValueError("similarity_topk_distinct: row_labels and query_labels go together (both or neither)")
-    _dev(Q, G)
-    assert Q.dtype == torch.float32 and Q.is_contiguous() and G.is_contiguous() and Q.dim() == 2 and G.dim() == 2
-    Bq, Cq = Q.shape
-    Ng, Cg = G.shape
-    assert Cq == Cg
     who = "similarity_topk_distinct"
+    Bq, Ng, C = _topk_front(who, Q, G, k, mode, (row_labels, query_labels))
     rg = _labels(row_groups, Ng, "row_groups", Q.device, who)
     rl = _labels(row_labels, Ng, "row_labels", Q.device, who) if row_labels is not None else None
     qlab = _labels(query_labels, Bq, "query_labels", Q.device, who) if query_labels is not None else None
-    lib = _lib()
-    nbytes = lib.cor_topk_distinct_workspace_bytes(Bq, Ng, k)
-    if nbytes < 0:
-        nat.check(int(nbytes), "cor_topk_distinct_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device)
-    scores = torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
-    idx = torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
-    nat.check(lib.cor_similarity_topk_distinct(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, Cq, k, int(g_offset), rg.data_ptr(),
-                                               rl.data_ptr() if rl is not None else None, qlab.data_ptr() if qlab is not None else None,
-                                               _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), int(flags), _s()),
+    ws, scores, idx = _topk_buffers("cor_topk_distinct_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk_distinct(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, k, int(g_offset), rg.data_ptr(),
+                                                  rl.data_ptr() if rl is not None else None, qlab.data_ptr() if qlab is not None else None,
+                                                  _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), int(flags), _s()),
               "cor_similarity_topk_distinct")
     return scores, idx
 

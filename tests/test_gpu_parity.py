@@ -1185,8 +1185,9 @@ def test_similarity_small_shard_path_overflow_falls_back_on_the_device():
 
 
 def test_similarity_topk_lists_fallback_kernels():
-    """The per-lane sorted-list kernels (COR_TOPK_FORCE_LISTS; what the device-side fallback runs after an overflow) rank by
-    the 16-bit MFMA score: indices equal the chain oracle's except inside fp32-summation-order ties (counted)."""
+    """The per-lane sorted-list kernels (COR_TOPK_FORCE_LISTS; an A/B path only: an overflow is repaired by the brute force inside the
+    selection kernel, not by these) rank by the 16-bit MFMA score: indices equal the chain oracle's except inside fp32-summation-order
+    ties (counted)."""
     ops, _ = _ops()
     from cor_amd import _native as nat
     rng = np.random.default_rng(99)

@@ -166,24 +166,29 @@ def test_filtered_topk_planted_excluded_copies(gdt, mode):
     assert int((raw == -2).any(dim=1).sum()) == 0
 
 
-def test_filtered_topk_overflow_falls_back_over_the_allowed_rows():
+# (gdt, C, queries, rows): the record (scan-form) selection kernel, then the entry-list (tile-form) one for fp32 and for C != 256
+OVERFLOW_CASES = [(BF16, 256, 40, 60000), (F32, 256, 16, 20000), (F16, 128, 16, 20000)]
+
+
+@pytest.mark.parametrize("gdt,C,nq,Ng", OVERFLOW_CASES, ids=["bf16-256", "f32-256", "f16-128"])
+def test_filtered_topk_overflow_falls_back_over_the_allowed_rows(gdt, C, nq, Ng):
     """6000 identical rows close to query 0, alternating classes 0 / 1; query 0 keeps class 0: 3000 tied allowed rows overflow the short
     list at k = 100, the in-kernel brute force ranks the ALLOWED rows only (the first 100 class-0 copies in index order)."""
     _, nat = _ops()
     k = 100
     rng = np.random.default_rng(5)
-    Q = _unit(rng, 40, 256)
-    row = _unit(rng, 1, 256)
-    G = _unit(rng, 60000, 256)
+    Q = _unit(rng, nq, C)
+    row = _unit(rng, 1, C)
+    G = _unit(rng, Ng, C)
     G[10000:16000] = torch.nn.functional.normalize(Q[0:1] + 0.05 * row, dim=-1)
-    G = G.to(BF16)
-    rl = torch.from_numpy(rng.integers(0, 4, 60000).astype(np.int32))
+    G = G.to(gdt)
+    rl = torch.from_numpy(rng.integers(0, 4, Ng).astype(np.int32))
     rl[10000:16000] = torch.arange(6000, dtype=torch.int32) % 2
-    ql = torch.from_numpy(rng.integers(0, 4, 40).astype(np.int32)); ql[0] = 0; ql[1::5] = -1
+    ql = torch.from_numpy(rng.integers(0, 4, nq).astype(np.int32)); ql[0] = 0; ql[1::5] = -1
     s, i = _run(Q, G, k, rl, ql, "eq")
     _, raw = _run(Q, G, k, rl, ql, "eq", flags=nat.TOPK_NO_FALLBACK)
     flagged = (raw == -2).all(dim=1).cpu()
-    assert bool(flagged[0]) and int(flagged.sum()) < 40
+    assert bool(flagged[0]) and int(flagged.sum()) < nq
     assert torch.equal(i[0].cpu(), torch.arange(10000, 16000, 2)[:k])
     keep = ~flagged.to(DEV)
     assert torch.equal(raw[keep], i[keep])

@@ -97,31 +97,36 @@ def test_wide_topk_prefix_equals_the_k32_call(C, gdt, Bq, Ng):
         assert torch.equal(s[:, :32].view(torch.int32), s32.view(torch.int32)), k
 
 
-def test_wide_topk_overflow_falls_back_on_the_device():
+# (gdt, C, queries, rows): the record (scan-form) selection kernel, then the entry-list (tile-form) one for fp32 and for C != 256
+OVERFLOW_CASES = [(BF16, 256, 40, 60000), (F32, 256, 16, 20000), (F16, 128, 16, 20000)]
+
+
+@pytest.mark.parametrize("gdt,C,nq,Ng", OVERFLOW_CASES, ids=["bf16-256", "f32-256", "f16-128"])
+def test_wide_topk_overflow_falls_back_on_the_device(gdt, C, nq, Ng):
     """A slice of 3000 identical rows close to query 0 ties far more rows than the short list holds at k = 100: the query overflows,
     is flagged (COR_TOPK_NO_FALLBACK: -2 in every slot) and, by default, ranked exactly inside the selection kernel (radix select over
     the chain scores of the whole shard, the first k tied rows in index order). The other queries are exact either way."""
     ops, nat = _ops()
     k = 100
     rng = np.random.default_rng(5)
-    Q = _unit(rng, 40, 256)
-    row = _unit(rng, 1, 256)
-    G = _unit(rng, 60000, 256)
+    Q = _unit(rng, nq, C)
+    row = _unit(rng, 1, C)
+    G = _unit(rng, Ng, C)
     G[10000:13000] = torch.nn.functional.normalize(Q[0:1] + 0.05 * row, dim=-1)
-    G = G.to(BF16)
+    G = G.to(gdt)
     s, i = ops.similarity_topk(Q.to(DEV), G.to(DEV), k)
     _, raw = ops.similarity_topk(Q.to(DEV), G.to(DEV), k, flags=nat.TOPK_NO_FALLBACK)
     flagged = (raw == -2).all(dim=1).cpu()
-    assert bool(flagged[0]) and int(flagged.sum()) < 40, flagged
+    assert bool(flagged[0]) and int(flagged.sum()) < nq, flagged
     assert bool(((raw == -2).any(dim=1).cpu() == flagged).all())
     assert torch.equal(i[0].cpu(), torch.arange(10000, 10000 + k))
     assert torch.equal(raw[~flagged.to(DEV)], i[~flagged.to(DEV)])
     rs, ri = _oracle(Q, G, k, margin=1e-3)
     _assert_bitwise(s, i, rs, ri, 0, k, G.shape[0])
     # every row identical: every query overflows; the answer is the first k rows, all with the same score
-    G1 = row.repeat(20000, 1).to(BF16)
+    G1 = row.repeat(20000, 1).to(gdt)
     s1, i1 = ops.similarity_topk(Q.to(DEV), G1.to(DEV), k)
-    assert torch.equal(i1.cpu(), torch.arange(k).repeat(40, 1))
+    assert torch.equal(i1.cpu(), torch.arange(k).repeat(nq, 1))
     _, raw1 = ops.similarity_topk(Q.to(DEV), G1.to(DEV), k, flags=nat.TOPK_NO_FALLBACK)
     assert (raw1 == -2).all()
     rs1, _ = _oracle(Q, G1, k, margin=1e-3)
