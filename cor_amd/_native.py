@@ -19,6 +19,7 @@ TOPK_KMAX = 256    # largest k of cor_similarity_topk (COR_TOPK_KMAX)
 FILTER_EQ, FILTER_NE = 0, 1    # cor_similarity_topk_filtered modes (COR_FILTER_EQ / COR_FILTER_NE)
 MERGE_NMAX = 4096    # most entries per query (P * kin) one cor_merge_topk launch ranks (COR_MERGE_NMAX)
 EXPAND_SEGMAX = 16    # most gallery segments one cor_expand_queries launch reads (COR_EXPAND_SEGMAX)
+RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_reciprocal launch reads (COR_RERANK_SEGMAX)
 ORDER_REVERSE = 1 << 30    # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
 KERNEL_ROWLANE, KERNEL_FEWQ, KERNEL_FLASH_MFMA, KERNEL_FLASH_PIPELINED, KERNEL_WINDOW_BLOCK = 1, 2, 3, 4, 5
 import numpy as _np
@@ -75,6 +76,8 @@ SIGNATURES = {
     "cor_rescore_workspace_bytes": [_i, _i, _i],
     "cor_rescore_topk": [_p, _p, _i, _i, _i, _i, _ll, _p, _i, _i, _p, _p, _p, _p, _p],
     "cor_expand_queries": [_p, _f, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p],
+    "cor_knn_reciprocal": [_p, _p, _p, _i, _i, _i, _p, _p],
+    "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}

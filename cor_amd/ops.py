@@ -675,6 +675,100 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
     return out
 
 
+def _graph_spans(who, segments):
+    """Shared check of a graph's segment list [(…, offset)] whose first tensor has one row per gallery row: count and disjoint ranges."""
+    if len(segments) > nat.RERANK_SEGMAX:
+        raise ValueError(f"{who}: {len(segments)} segments, one call reads at most {nat.RERANK_SEGMAX}")
+    spans = sorted((seg[-1], seg[-1] + seg[0].shape[0]) for seg in segments if seg[0].shape[0])
+    for (_, hi), (lo, _) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise ValueError(f"{who}: the segments' id ranges overlap")
+
+
+def knn_reciprocal(segments, seg, out=None):
+    """Reciprocal pruning of one segment of a neighbour graph on the device (cor_knn_reciprocal). segments: a list of (nbr, offset), nbr
+    i64 [n, k1] the global ids of the k1 nearest rows of each of the rows [offset, offset + n), as a search returns them (-1 = none); at
+    most nat.RERANK_SEGMAX (16) segments, pairwise disjoint, one width k1 <= 256. -> i64 [n, k1] for segment number `seg`: the id h where
+    h lies in some segment and h's own list names the row, else -1. Written to a new tensor (or `out`, which must not be an input): never
+    in place. Ids are range-tested before they index anything. No host synchronisation."""
+    segments = [(t, int(o)) for t, o in segments]
+    if not segments or not 0 <= int(seg) < len(segments):
+        raise ValueError(f"knn_reciprocal: segment number {seg} of {len(segments)} segments")
+    k1 = segments[0][0].shape[-1]
+    for t, _ in segments:
+        if t.dim() != 2 or t.dtype != torch.int64 or t.shape[1] != k1 or t.shape[0] >= 2 ** 31:
+            raise ValueError(f"knn_reciprocal: a segment's lists must be int64 [n < 2^31, {k1}], got {t.dtype} {tuple(t.shape)}")
+    if not 1 <= k1 <= nat.TOPK_KMAX:
+        raise ValueError(f"knn_reciprocal: the lists' width must be in [1, {nat.TOPK_KMAX}], got {k1}")
+    _graph_spans("knn_reciprocal", segments)
+    mine = segments[int(seg)][0]
+    if out is not None and (out.shape != mine.shape or out.dtype != torch.int64 or not out.is_contiguous()
+                            or any(out.data_ptr() == t.data_ptr() for t, _ in segments if t.numel())):
+        raise ValueError(f"knn_reciprocal: out must be a contiguous int64 {tuple(mine.shape)} tensor that is none of the inputs")
+    dev = _dev(out, *[t for t, _ in segments])
+    lists = [t.contiguous() for t, _ in segments]
+    if out is None:
+        out = torch.empty(mine.shape, dtype=torch.int64, device=dev)
+    n = len(segments)
+    c = nat.C
+    seg_nbr = (c.c_void_p * n)(*[t.data_ptr() or None for t in lists])
+    seg_off = (c.c_longlong * n)(*[o for _, o in segments])
+    seg_n = (c.c_int * n)(*[t.shape[0] for t in lists])
+    if mine.shape[0]:                                         # (no rows: empty tensors have no address to pass)
+        nat.check(_lib().cor_knn_reciprocal(seg_nbr, seg_off, seg_n, n, k1, int(seg), out.data_ptr(), _s()), "cor_knn_reciprocal")
+    return out
+
+
+def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
+    """k-reciprocal re-ranking of lists on the device, set form (cor_rerank_reciprocal). scores f32 [Bq,kin] and idx i64 [Bq,kin] as a
+    search, the merge or the re-scoring return them; segments: a list of (rnbr, kth, offset), the graph of the rows [offset, offset + n):
+    rnbr i64 [n,kg] the reciprocal neighbour lists (knn_reciprocal), kth f32 [n] the score of each row's k1-th neighbour; at most
+    nat.RERANK_SEGMAX (16), pairwise disjoint, one width kg <= 256. -> (scores f32[Bq,k], idx i64[Bq,k]) and with return_pos pos i32[Bq,k]:
+    A = the ids of the first k1 entries with score >= kth[id]; every entry whose id lies in a segment gets
+    f = lam * score + (1 - lam) * |A n B| / |A u B|, B its row's non-negative rnbr ids, and the entries are ranked by (f desc, id asc);
+    an id of no segment (-1, another shard's, any 64-bit value) is dropped and its score is not read; fewer than k left: the
+    (-inf, -1, -1) tail. include/cor_amd.h has the definition to the bit. 1 <= k1 <= min(kin, 256), 1 <= k <= 256, kin <= nat.MERGE_NMAX
+    (4096; beyond that NativeError), lam finite. No host synchronisation; capturable in a graph."""
+    segments = [(r, t, int(o)) for r, t, o in segments]
+    if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:
+        raise ValueError(f"rerank_reciprocal: scores must be float32 [Bq, kin] with kin >= 1, got {scores.dtype} {tuple(scores.shape)}")
+    if idx.shape != scores.shape or idx.dtype != torch.int64:
+        raise ValueError(f"rerank_reciprocal: idx must be int64 {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
+    Bq, kin = scores.shape
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"rerank_reciprocal: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if not 1 <= int(k1) <= min(kin, nat.TOPK_KMAX):
+        raise ValueError(f"rerank_reciprocal: k1 must be in [1, min(kin, {nat.TOPK_KMAX})] (kin = {kin}), got {k1}")
+    lam = float(lam)
+    if lam != lam or lam in (float("inf"), float("-inf")):
+        raise ValueError(f"rerank_reciprocal: lam must be finite, got {lam}")
+    kg = segments[0][0].shape[-1] if segments else 1
+    for r, t, _ in segments:
+        if r.dim() != 2 or r.dtype != torch.int64 or r.shape[1] != kg or r.shape[0] >= 2 ** 31:
+            raise ValueError(f"rerank_reciprocal: a segment's lists must be int64 [n < 2^31, {kg}], got {r.dtype} {tuple(r.shape)}")
+        if t.dim() != 1 or t.dtype != torch.float32 or t.shape[0] != r.shape[0]:
+            raise ValueError(f"rerank_reciprocal: a segment's kth must be float32 [{r.shape[0]}], got {t.dtype} {tuple(t.shape)}")
+    if not 1 <= kg <= nat.TOPK_KMAX:
+        raise ValueError(f"rerank_reciprocal: the graph's width must be in [1, {nat.TOPK_KMAX}], got {kg}")
+    _graph_spans("rerank_reciprocal", segments)
+    dev = _dev(scores, idx, *[x for r, t, _ in segments for x in (r, t)])
+    scores, idx = scores.contiguous(), idx.contiguous()
+    lists, kths = [r.contiguous() for r, _, _ in segments], [t.contiguous() for _, t, _ in segments]
+    out_s = torch.empty((Bq, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((Bq, k), dtype=torch.int64, device=dev)
+    out_p = torch.empty((Bq, k), dtype=torch.int32, device=dev) if return_pos else None
+    n = len(segments)
+    c = nat.C
+    seg_rnbr = (c.c_void_p * max(n, 1))(*[r.data_ptr() or None for r in lists])
+    seg_kth = (c.c_void_p * max(n, 1))(*[t.data_ptr() or None for t in kths])
+    seg_off = (c.c_longlong * max(n, 1))(*[o for _, _, o in segments])
+    seg_n = (c.c_int * max(n, 1))(*[r.shape[0] for r in lists])
+    if Bq:                                                    # (no queries: empty tensors have no address to pass)
+        nat.check(_lib().cor_rerank_reciprocal(scores.data_ptr(), idx.data_ptr(), seg_rnbr, seg_kth, seg_off, seg_n, n, Bq, kin, kg, int(k1), lam,
+                                               int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _s()), "cor_rerank_reciprocal")
+    return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

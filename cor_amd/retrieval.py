@@ -151,6 +151,69 @@ def recall_at_k(idx, positives, ks=(1, 5, 10, 50, 100)) -> dict:
     return {K: int((first < K).sum()) / B if B else 0.0 for K in ks}
 
 
+class NeighbourGraph:
+    """The k-reciprocal neighbour graph of a gallery (GalleryShard.neighbour_graph / GallerySet.neighbour_graph), on the gallery's
+    device. Per non-empty segment it was built from: rnbr i64[n, width], row g's k1 nearest rows as global ids, pruned to the reciprocal
+    ones (-1 where the neighbour does not list g back, lies in no segment, or does not exist), and kth f32[n], the score of row g's
+    k1-th neighbour (-inf when fewer than k1 rows exist). `offsets` / `lengths` name those segments: a graph is valid only for them;
+    GallerySet.add / drop do not update it, and rerank raises ValueError for a gallery whose live segments differ."""
+
+    def __init__(self, width: int, offsets, lengths, rnbr, kth):
+        self.width = int(width)
+        self.offsets, self.lengths = tuple(int(o) for o in offsets), tuple(int(n) for n in lengths)
+        self.rnbr, self.kth = list(rnbr), list(kth)
+
+    @property
+    def segments(self):
+        """[(rnbr, kth, offset)] as ops.rerank_reciprocal takes it."""
+        return list(zip(self.rnbr, self.kth, self.offsets))
+
+    def check(self, who, live):
+        """ValueError unless `live` (the gallery's non-empty segments) are the segments this graph was built from."""
+        spans = (tuple(int(sh.offset) for sh in live), tuple(len(sh) for sh in live))
+        if spans != (self.offsets, self.lengths):
+            raise ValueError(f"{who}: the graph was built from segments at offsets {self.offsets} of lengths {self.lengths}, the gallery "
+                             f"now has {spans[0]} of lengths {spans[1]}: build a new graph (neighbour_graph)")
+
+
+def _check_graph_args(who, k1, batch):
+    if not 1 <= int(k1) <= ops.nat.TOPK_KMAX or int(batch) < 1:
+        raise ValueError(f"{who}: k1 must be in [1, {ops.nat.TOPK_KMAX}] and batch at least 1, got k1={k1}, batch={batch}")
+
+
+def _knn_lists(shard, k1, batch, nb):
+    """(nbr i64[n,k1], kth f32[n]) of `shard`'s rows searched, unfiltered, in `nb`, `batch` rows at a time."""
+    n, dev = len(shard), shard.rows.device
+    nbr = torch.empty((n, k1), dtype=torch.int64, device=dev)
+    kth = torch.empty((n,), dtype=torch.float32, device=dev)
+    for lo in range(0, n, int(batch)):
+        s, i = nb.search(shard.rows[lo:lo + int(batch)], k1)
+        nbr[lo:lo + int(batch)] = i
+        kth[lo:lo + int(batch)] = s[:, k1 - 1]
+    return nbr, kth
+
+
+def _pruned_graph(live, k1, lists):
+    """NeighbourGraph of the non-empty segments `live` from their (nbr, kth) lists: one ops.knn_reciprocal launch per segment."""
+    table = [(nbr, int(sh.offset)) for sh, (nbr, _) in zip(live, lists)]
+    rnbr = []
+    for n, sh in enumerate(live):
+        with torch.cuda.device(sh.rows.device) if sh.rows.is_cuda else contextlib.nullcontext():
+            rnbr.append(ops.knn_reciprocal(table, n))
+    return NeighbourGraph(k1, [sh.offset for sh in live], [len(sh) for sh in live], rnbr, [kth for _, kth in lists])
+
+
+def _rerank(who, live, scores, idx, graph, k1, lam, k):
+    graph.check(who, live)
+    if idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be [Bq, kin], got {tuple(idx.shape)}")
+    k1 = graph.width if k1 is None else k1
+    k = min(idx.shape[1], ops.nat.TOPK_KMAX) if k is None else k
+    dev = live[0].rows.device if live else scores.device
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        return ops.rerank_reciprocal(scores, idx, graph.segments, k1, lam, k)
+
+
 class GalleryShard:
     """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16. labels: optional int32[n], one label
     per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches. groups: optional int32[n],
@@ -237,6 +300,24 @@ class GalleryShard:
             s, i = nb.search(self.rows[lo:lo + int(batch)], int(m))
             nb.expand(None, s, i, int(m), alpha=alpha, query_weight=0.0, out_dtype=out.dtype, out=out[lo:lo + int(batch)])
         return GalleryShard(out, offset=self.offset, labels=self.labels, groups=self.groups)
+
+    def neighbour_graph(self, k1: int, batch: int = 4096, neighbours=None):
+        """The k-reciprocal neighbour graph of this shard's rows (a NeighbourGraph of width k1, for rerank): every row's top-k1 list over
+        `neighbours` (a GalleryShard or GallerySet over the same id space, e.g. a 16-bit copy; default: this shard, where a unit-norm row
+        finds itself, so it stays in its own reciprocal list), unfiltered, `batch` rows at a time, then pruned on the device
+        (ops.knn_reciprocal) to the neighbours that lie in this shard and list the row back. 1 <= k1 <= 256, batch >= 1, else
+        ValueError."""
+        _check_graph_args("GalleryShard.neighbour_graph", k1, batch)
+        live = [self] if len(self) else []
+        return _pruned_graph(live, int(k1), [_knn_lists(sh, int(k1), batch, self if neighbours is None else neighbours) for sh in live])
+
+    def rerank(self, scores: torch.Tensor, idx: torch.Tensor, graph, k1: int | None = None, lam: float = 0.3, k: int | None = None):
+        """k-reciprocal re-ranking (set form) of lists over this shard (ops.rerank_reciprocal): scores / idx [Bq,kin] as search, rescore,
+        two_stage_search or expanded_search return them, graph = self.neighbour_graph(..) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU,
+        ranked by lam * score + (1 - lam) * Jaccard(the query's k-reciprocal set among its first k1 entries, the entry's reciprocal
+        neighbours). k1 defaults to the graph's width, k to min(kin, 256). Entries this shard does not hold are dropped. ValueError if the
+        graph was built from other segments."""
+        return _rerank("GalleryShard.rerank", [self] if len(self) else [], scores, idx, graph, k1, lam, k)
 
 
 class GallerySet:
@@ -364,6 +445,21 @@ class GallerySet:
         GallerySet of new segments; this set and its segments are left untouched."""
         return GallerySet([sh.augmented(m, alpha=alpha, batch=batch, dtype=dtype, neighbours=self) for sh in self._segments])
 
+    def neighbour_graph(self, k1: int, batch: int = 4096):
+        """GalleryShard.neighbour_graph over all segments: every row's top-k1 list over the WHOLE set, pruned against the lists of all
+        segments (at most 16 non-empty ones). The graph is valid for the segments the set has now; add / drop do not update it."""
+        _check_graph_args("GallerySet.neighbour_graph", k1, batch)
+        live = [sh for sh in self._segments if len(sh)]
+        if len(live) > ops.nat.RERANK_SEGMAX:
+            raise ValueError(f"GallerySet.neighbour_graph: {len(live)} non-empty segments, a graph spans at most {ops.nat.RERANK_SEGMAX}")
+        return _pruned_graph(live, int(k1), [_knn_lists(sh, int(k1), batch, self) for sh in live])
+
+    def rerank(self, scores: torch.Tensor, idx: torch.Tensor, graph, k1: int | None = None, lam: float = 0.3, k: int | None = None):
+        """GalleryShard.rerank over all segments in ONE launch: the kernel looks every id up in the graph's segment table. The result
+        equals bitwise that of a single GalleryShard over the concatenated rows with the same lists. ValueError if the set's non-empty
+        segments are not the ones the graph was built from."""
+        return _rerank("GallerySet.rerank", [sh for sh in self._segments if len(sh)], scores, idx, graph, k1, lam, k)
+
 
 def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int, fine_queries: torch.Tensor | None = None, **search_kwargs):
     """Two-stage search on one device: coarse.search(queries, k_coarse, **search_kwargs) finds the candidates, fine.rescore(fine_queries
@@ -403,6 +499,19 @@ def expanded_search(queries: torch.Tensor, gallery, k: int, m: int, alpha: int =
         q = gallery.expand(q, s, i, int(m), alpha=alpha, query_weight=query_weight)
     s, i = gallery.search(q, int(k), **search_kwargs)
     return s, i, q
+
+
+def reranked_search(queries: torch.Tensor, gallery, graph, k: int, k_coarse: int, k1: int | None = None, lam: float = 0.3, **search_kwargs):
+    """Search with k-reciprocal re-ranking on one device: gallery.search(queries, k_coarse, **search_kwargs) followed by
+    gallery.rerank(scores, idx, graph, k1=k1, lam=lam, k=k) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU. gallery: a GalleryShard or a
+    GallerySet, graph: its neighbour_graph. 1 <= k <= k_coarse <= 256, else ValueError; k1 defaults to the graph's width and must not
+    exceed k_coarse. search_kwargs (query_labels, mode, distinct) go to the search; with distinct=True the candidates are the
+    representatives' rows and their graph rows are used as they are. Nothing leaves the device and the host is not waited for.
+    distributed_search has no such option: a candidate's graph row lives on the rank that owns the row."""
+    if not 1 <= int(k) <= int(k_coarse) <= ops.nat.TOPK_KMAX:
+        raise ValueError(f"reranked_search: need 1 <= k <= k_coarse <= {ops.nat.TOPK_KMAX}, got k={k}, k_coarse={k_coarse}")
+    s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
+    return gallery.rerank(s, i, graph, k1=k1, lam=lam, k=int(k))
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):

@@ -450,6 +450,56 @@ int cor_expand_queries(const float* Q, float query_weight, const void* const* se
                        const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int m, int C, int alpha,
                        int normalize, void* out, int out_dtype, void* stream);
 
+/* k-reciprocal re-ranking (Zhong et al., CVPR 2017), SET FORM: uniform weights and the Jaccard index of k-reciprocal neighbour sets, mixed
+ * with the original score by lam. Not implemented: the paper's Gaussian weights, the 2/3-overlap set expansion, the local query expansion
+ * over k2. Two entry points: the reciprocal pruning of a gallery's neighbour graph (once per gallery) and the re-ranking of lists.
+ *
+ * cor_knn_reciprocal. A neighbour graph is, per segment s of a gallery (global ids [seg_offset[s], seg_offset[s] + seg_n[s]), pairwise
+ * disjoint, at most COR_RERANK_SEGMAX segments), a DEVICE array seg_nbr[s] i64 [seg_n[s], k1], contiguous: row g holds the global ids of
+ * the k1 nearest rows of row g, as a search returns them (-1 where fewer exist). The segment arrays are HOST arrays of nseg entries and
+ * travel by value in the kernel arguments. The call prunes segment `seg`: out i64 [seg_n[seg], k1], a buffer of its own (never one of the
+ * inputs), receives out[g, j] = h = seg_nbr[seg][g, j] if h lies in some segment's id range AND the global id of row g,
+ * seg_offset[seg] + g, occurs among the k1 ids of h's row; otherwise -1. The range test comes before any address is formed from h
+ * (unsigned difference behind h >= seg_offset[s]), so the ids may be arbitrary 64-bit values. One thread per (g, j). A row that lists
+ * itself keeps itself. COR_EINVAL: a null segment array, nseg < 1, k1 < 1, seg outside [0, nseg), a negative seg_n, a null seg_nbr[s] with
+ * seg_n[s] > 0, a null out with seg_n[seg] > 0. COR_ENOSUPPORT: k1 > COR_TOPK_KMAX, nseg > COR_RERANK_SEGMAX. seg_n[seg] == 0 is a
+ * successful no-op.
+ *
+ * cor_rerank_reciprocal. scores f32 [Bq,kin] and idx i64 [Bq,kin], contiguous: lists as the searches, the merge or the re-scoring return
+ * them. Segment s of the graph: seg_rnbr[s] i64 [seg_n[s], kg] (the pruned lists above, kg the graph's width), seg_kth[s] f32 [seg_n[s]]
+ * (the score of each row's k1-th neighbour; -inf where fewer than k1 rows exist), seg_offset[s], seg_n[s]; HOST arrays of nseg DEVICE
+ * pointers, copied into a by-value kernel argument. out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_pos NULL or i32 [Bq,k].
+ * Definition, per query b, fixed to the bit:
+ *   Entry j is PRESENT if idx[b,j] lies in some segment's [seg_offset[s], seg_offset[s] + seg_n[s]); the range test runs before any
+ *   address is formed (unsigned difference behind id >= seg_offset[s]), so ids may be arbitrary 64-bit values. Every other entry is
+ *   MISSING: it is dropped and its score is never read.
+ *   Preconditions: the present entries of one query have pairwise different ids and finite scores; lam is finite. (If they do not hold
+ *   the result is unspecified, but every access stays in bounds.)
+ *   A = { idx[b,j] : j < k1, present, scores[b,j] >= kth[idx[b,j]] }: the query's k-reciprocal set. A gallery row counts the query among
+ *   its k1 nearest if the query scores at least as high as the row's k1-th neighbour.
+ *   For every present entry j (all kin positions): B_j = the non-negative ids among rnbr[idx[b,j], 0 .. kg) (counted by position: a
+ *   graph built by a search names every id once, so these are set sizes); I = |A n B_j|; U = |A| + |B_j| - I;
+ *   J = U > 0 ? float(I) / float(U) : +0;  f = (lam * scores[b,j]) + ((1.0f - lam) * J).
+ *   Each of the five fp32 operations (two conversions aside, which are exact) is ONE separately rounded IEEE operation, never an fma.
+ *   The present entries are ranked by (f desc, id asc) with cor_merge_topk's rules: -0.0 and +0.0 tie and the id decides; ids compare
+ *   as 64-bit values. The first k go out with f's bits as computed; out_pos is the entry's position j; positions past the number of
+ *   present entries hold (-inf, -1, -1). lam == 1 therefore returns the present entries ordered by (score desc, id asc), which for a
+ *   list as a search returns it is the input order, with scores * 1 + 0 * J as scores.
+ * One launch, one block per query: A is built and sorted in LDS; thread-per-candidate, each candidate's rnbr row is read from global
+ * memory (16-byte loads for even kg) and every id is binary-searched in A; then cor_merge_topk's ranking (bitonic sort in LDS of 8-byte
+ * keys [f key | position], the id read through the position on ties). No scratch, no allocation, no host synchronisation; everything
+ * runs on `stream` and the call can be captured in a graph.
+ * COR_EINVAL: a null scores / idx / out_scores / out_idx, Bq < 0, kin / kg / k1 / k < 1, k1 > kin, nseg < 0, a null segment array with
+ * nseg > 0, a negative seg_n, a null seg_rnbr[s] or seg_kth[s] with seg_n[s] > 0. COR_ENOSUPPORT: kin > COR_MERGE_NMAX; k, k1 or
+ * kg > COR_TOPK_KMAX; nseg > COR_RERANK_SEGMAX. All of these are decided before any HIP call. Bq == 0 is a successful no-op; nseg == 0 is
+ * legal (every entry is missing). */
+#define COR_RERANK_SEGMAX 16
+int cor_knn_reciprocal(const long long* const* seg_nbr, const long long* seg_offset, const int* seg_n, int nseg, int k1, int seg,
+                       long long* out, void* stream);
+int cor_rerank_reciprocal(const float* scores, const long long* idx, const long long* const* seg_rnbr, const float* const* seg_kth,
+                          const long long* seg_offset, const int* seg_n, int nseg, int Bq, int kin, int kg, int k1, float lam, int k,
+                          float* out_scores, long long* out_idx, int* out_pos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
