@@ -175,6 +175,14 @@ __device__ __forceinline__ void glds16_so_pair4k(const void* sbase, unsigned vof
 }
 
 __host__ __device__ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// the smallest power of two >= max(n, 2): the padded length of an LDS bitonic sort
+static inline int next_pow2(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+// an entry of a by-value segment table: a negative row count, or rows without an address (`ptrs_ok`: none of the entry's pointers is null)
+static inline bool seg_entry_bad(int n, bool ptrs_ok) { return n < 0 || (!ptrs_ok && n > 0); }
 
 // ---- per-DEVICE one-time host state -----------------------------------------------------------------------------------
 // The > 64 KiB dynamic-LDS attribute of a kernel and the CU count belong to a device, not to the process: a second GPU in

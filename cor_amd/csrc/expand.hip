@@ -4,8 +4,8 @@
 // One wave per query, EX_QPB = 4 queries per 256-thread block; there is no block-level cooperation, hence no barrier and no LDS.
 //   Lane l owns channels [4l, 4l + 4): a row is ONE coalesced wave load, 16 B per lane for fp32 rows and 8 B for 16-bit rows (C = 256: all
 //   64 lanes; smaller C: the lanes past C / 4 re-read channels 0..3, stay out of the tree and store nothing, so no load or store is masked).
-//   1. List. 64 entries at a time, lane j takes entry j: its id is tested against every segment's [offset, offset + n) and only a test that
-//      passed forms the row address (unsigned difference behind the test, as rescore.hip); the entry's weight w = max(score, +0)^alpha
+//   1. List. 64 entries at a time, lane j takes entry j: its id is looked up in the segment table (ranklist.h's seg_lookup: the range test
+//      comes first) and only a hit forms the row address; the entry's weight w = max(score, +0)^alpha
 //      is computed there too (alpha dependent multiplies). The segment table is a by-value kernel argument, read with scalar loads.
 //   2. Rows. A ballot gives the present entries of the 64; they are walked in list order, lowest set bit first, 8 at a time (then 4, 2,
 //      1 for what is left): the entry's row address, weight and dtype come out of lane j by v_readlane, the loads of the whole group are
@@ -16,7 +16,7 @@
 // file: HIP's __fmul_rn / __fadd_rn are plain * and + (contractible under the default -ffp-contract=fast) and its __fsqrt_rn is the
 // APPROXIMATE native square root, so none of them is used here; a / b and __builtin_sqrtf are correctly rounded in a build without
 // fast-math flags (-fhip-fp32-correctly-rounded-divide-sqrt is the default), and the Makefile adds no such flag for this file.
-#include "common.h"
+#include "ranklist.h"
 
 #pragma clang fp contract(off)
 
@@ -27,7 +27,6 @@ constexpr int EX_QPB = 4;        // queries (waves) per block
 constexpr int EX_CMAX = 256;     // 64 lanes x 4 channels
 constexpr int EX_ALPHA_MAX = 8;
 
-typedef unsigned long long u64;
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // the segment table, passed BY VALUE in the kernel argument block (384 B): no device allocation, no copy, nothing to keep alive
@@ -124,18 +123,10 @@ __global__ __launch_bounds__(64 * EX_QPB) void expand_kernel(const float* __rest
     int dt = COR_F32;
     bool present = false;
     if (j < m) {
-      const long long id = ids[j];
-      for (int s = 0; s < nseg; ++s) {
-        const long long so = segs.off[s];
-        if (!present && id >= so) {
-          const u64 local = (u64)id - (u64)so;                           // exact: id >= so
-          if (local < (u64)segs.n[s]) {                                  // the only place a row address is formed
-            present = true;
-            dt = segs.dt[s];
-            row = (u64)segs.rows[s] + local * (u64)(C * (dt == COR_F32 ? 4 : 2));
-          }
-        }
-      }
+      present = seg_lookup(segs, nseg, ids[j], [&](int s, u64 local) {   // the only place a row address is formed
+        dt = segs.dt[s];
+        row = (u64)segs.rows[s] + local * (u64)(C * (dt == COR_F32 ? 4 : 2));
+      });
       if (present) {                                                     // a missing entry's score is never read
         const float t0 = sc[j];
         const float t = t0 > 0.f ? t0 : 0.f;                             // NaN, -0.0 and negatives: +0
@@ -201,7 +192,7 @@ extern "C" int cor_expand_queries(const float* Q, float query_weight, const void
   if (!Q && query_weight != 0.f) return COR_EINVAL;
   if (nseg > EX_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
   for (int s = 0; s < nseg; ++s)
-    if (seg_n[s] < 0 || (!seg_rows[s] && seg_n[s] > 0)) return COR_EINVAL;
+    if (seg_entry_bad(seg_n[s], seg_rows[s])) return COR_EINVAL;
   if (m > COR_TOPK_KMAX || C > EX_CMAX || C % 16 != 0) return COR_ENOSUPPORT;
   ExSegs segs = {};
   int sizes = 0;                                                         // bit 0: a segment of 16-bit rows, bit 1: one of fp32 rows

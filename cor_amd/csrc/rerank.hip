@@ -3,7 +3,7 @@
 // candidate's reciprocal neighbours). Contract and the definition, fixed to the bit: include/cor_amd.h.
 //
 // cor_knn_reciprocal: one thread per edge (g, j) of one segment. h = nbr[g, j] is tested against every segment's [offset, offset + n)
-//   and only a test that passed forms the address of h's list (unsigned difference behind the test, as expand.hip); the thread walks
+//   by ranklist.h's seg_lookup, and only a hit forms the address of h's list; the thread walks
 //   h's k1 ids until it meets g's global id. Output to a buffer of its own.
 // cor_rerank_reciprocal: one block per query, T = npad threads (64 .. 1024; npad = kin rounded up to a power of two), three phases.
 //   1. A. Thread j < k1 tests entry j's id against the segment table and, if it is present and scores[j] >= kth[id], puts the id into
@@ -12,12 +12,10 @@
 //      from global memory, 8 ids at a time with 16-byte loads when the rows are 16-byte aligned (kg even), and every non-negative id
 //      is looked up in the sorted A by binary search (at most 8 steps). I and |B| are counted in integers; J and f are five separately
 //      rounded fp32 operations (`#pragma clang fp contract(off)` for the file, plain `/`, no fast-math flag in the Makefile).
-//   3. Rank. merge.hip's scheme with helpers of this file's own: every position becomes a 64-bit key in LDS, [order-preserving key of
-//      f, descending | -0.0 flag | position]; a missing entry and the padding carry the largest key. The bitonic network reads the 64-bit
-//      id through the position when two present entries tie. The present entries' ids are pairwise different (precondition), so
-//      rank r goes to output slot r without a scan; f's bits come back out of the key.
+//   3. Rank. ranklist.h's keys (of f, with the -0.0 flag), network and tie rule. The present entries' ids are pairwise different
+//      (precondition), so rank r goes to output slot r without a scan; f's bits come back out of the key.
 // LDS: 8 B per key + 2 KiB for A + 2 counters = 34 KiB at kin = 4096, all in the dynamic region; no scratch memory in global.
-#include "common.h"
+#include "ranklist.h"
 
 #pragma clang fp contract(off)
 
@@ -25,15 +23,9 @@ namespace {
 
 constexpr int RR_SEGMAX = COR_RERANK_SEGMAX;
 constexpr int RR_KMAX = COR_TOPK_KMAX;         // k, k1 and the graph width kg
-constexpr int RR_NMAX = COR_MERGE_NMAX;        // candidates per query: 4096 = 12 position bits in the key
-static_assert(RR_NMAX == 4096 && RR_KMAX == 256, "the sort keys carry 12 position bits, bit 12 is the -0.0 flag, A holds 256 ids");
-constexpr unsigned RR_POS_MASK = RR_NMAX - 1;
-constexpr unsigned RR_NEGZERO = RR_NMAX;       // bit 12 of the key's low word: f is -0.0 (its key is that of +0.0)
-constexpr unsigned RR_MISSING = 0xffffffffu;   // key of missing entries and padding: above every non-NaN value's key
-constexpr unsigned RR_NEG_INF = 0xff800000u;
+static_assert(RR_KMAX == 256, "A holds 256 ids");
 constexpr long long RR_ID_MAX = 0x7fffffffffffffffLL;
 
-typedef unsigned long long u64;
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
 
 // the segment tables, passed BY VALUE in the kernel argument block: no device allocation, no copy, nothing to keep alive
@@ -58,13 +50,7 @@ __global__ __launch_bounds__(256) void knn_reciprocal_kernel(const KrSegs segs, 
   const long long gid = g_offset + (long long)((u64)e / (unsigned)k1);
   const long long h = nbr[e];
   const long long* list = nullptr;
-  for (int s = 0; s < nseg; ++s) {
-    const long long so = segs.off[s];
-    if (!list && h >= so) {
-      const u64 local = (u64)h - (u64)so;                                // exact: h >= so
-      if (local < (u64)segs.n[s]) list = segs.nbr[s] + local * (u64)k1;  // the only place the address of a list is formed
-    }
-  }
+  seg_lookup(segs, nseg, h, [&](int s, u64 local) { list = segs.nbr[s] + local * (u64)k1; });   // the only place a list's address is formed
   bool found = false;
   if (list)
     for (int t = 0; t < k1 && !found; ++t) found = list[t] == gid;
@@ -73,72 +59,18 @@ __global__ __launch_bounds__(256) void knn_reciprocal_kernel(const KrSegs segs, 
 
 // ------------------------------------------------------------------------------------------------------------------- re-ranking
 
-// float bits -> key that ascends as the value DEscends; -0.0 keys as +0.0
-__device__ __forceinline__ unsigned rr_score_key(unsigned u) {
-  if (u == 0x80000000u) u = 0u;
-  const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-// and back: the bits of a present entry's f
-__device__ __forceinline__ unsigned rr_key_score(u64 key) {
-  if ((unsigned)key & RR_NEGZERO) return 0x80000000u;
-  const unsigned asc = ~(unsigned)(key >> 32);
-  return (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-}
-
-__device__ __forceinline__ bool rr_before(u64 a, u64 b, const long long* __restrict__ ids) {
-  const unsigned ha = (unsigned)(a >> 32), hb = (unsigned)(b >> 32);
-  if (ha == hb && ha != RR_MISSING) {            // a tie between two PRESENT entries: positions < kin
-    const long long ia = ids[(unsigned)a & RR_POS_MASK], ib = ids[(unsigned)b & RR_POS_MASK];
-    if (ia != ib) return ia < ib;
-  }
-  return a < b;
-}
-
-// ascending bitonic sort of key[0, npad) (npad a power of two >= 2); ends with a barrier
-__device__ void rr_sort_keys(u64* key, int npad, const long long* __restrict__ ids) {
-  const int half = npad >> 1;
-  for (int size = 2; size <= npad; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < half; t += blockDim.x) {
-        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-        const u64 a = key[i], b = key[j];
-        if (rr_before(b, a, ids) == ((i & size) == 0)) { key[i] = b; key[j] = a; }
-      }
-      __syncthreads();
-    }
-}
-
-// the same network over signed 64-bit ids
-__device__ void rr_sort_ids(long long* a, int apad) {
-  const int half = apad >> 1;
-  for (int size = 2; size <= apad; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < half; t += blockDim.x) {
-        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-        const long long x = a[i], y = a[j];
-        if ((y < x) == ((i & size) == 0)) { a[i] = y; a[j] = x; }
-      }
-      __syncthreads();
-    }
-}
-
-// id -> the entry's rnbr row and kth value, or false: the range test comes first and only a test that passed forms an address
+// id -> the entry's rnbr row and kth value, or false
 __device__ __forceinline__ bool rr_lookup(const RrSegs& segs, int nseg, int kg, long long id, const long long*& row, const float*& kth) {
-  bool present = false;
-  for (int s = 0; s < nseg; ++s) {
-    const long long so = segs.off[s];
-    if (!present && id >= so) {
-      const u64 local = (u64)id - (u64)so;                               // exact: id >= so
-      if (local < (u64)segs.n[s]) {
-        present = true;
-        row = segs.rnbr[s] + local * (u64)kg;
-        kth = segs.kth[s] + local;
-      }
-    }
-  }
-  return present;
+  return seg_lookup(segs, nseg, id, [&](int s, u64 local) {
+    row = segs.rnbr[s] + local * (u64)kg;
+    kth = segs.kth[s] + local;
+  });
 }
+
+struct RrIdAt {
+  const long long* ids;   // this query's kin ids
+  __device__ __forceinline__ long long operator()(unsigned pos) const { return ids[pos]; }
+};
 
 // one id of a candidate's list against the sorted A[0, nA): counts it into |B| and, if A holds it, into I
 __device__ __forceinline__ void rr_count(const long long* A, int nA, long long h, int& nB, int& I) {
@@ -183,14 +115,14 @@ __global__ __launch_bounds__(1024) void rerank_kernel(const float* __restrict__ 
   }
   if (mine) atomicAdd(&cnt[0], mine);
   __syncthreads();
-  rr_sort_ids(A, apad);                                                  // the |A| ids first (an id equal to the filler sorts beside it)
+  block_bitonic_sort(A, apad, PlainBefore{});                            // the |A| ids first (an id equal to the filler sorts beside it)
   const int nA = cnt[0];
 
   // 2. f of every present entry, as its sort key
   const float oml = 1.0f - lam;
   mine = 0;
   for (int pos = tid; pos < npad; pos += T) {
-    unsigned hi = RR_MISSING, lo = (unsigned)pos;
+    unsigned hi = RANK_MISSING, lo = (unsigned)pos;
     if (pos < kin) {
       const long long id = ids[pos];
       const long long* row = nullptr;
@@ -219,28 +151,28 @@ __global__ __launch_bounds__(1024) void rerank_kernel(const float* __restrict__ 
         const float J = U > 0 ? (float)I / (float)U : 0.f;
         const float f = (lam * sc[pos]) + (oml * J);
         const unsigned u = __float_as_uint(f);
-        hi = rr_score_key(u);
-        if (u == 0x80000000u) lo |= RR_NEGZERO;
+        hi = rank_score_key(u);
+        if (u == 0x80000000u) lo |= RANK_NEGZERO;
       }
     }
-    mine += hi != RR_MISSING;                    // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
+    mine += hi != RANK_MISSING;                  // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
     key[pos] = ((u64)hi << 32) | lo;
   }
   if (mine) atomicAdd(&cnt[1], mine);
   __syncthreads();
 
   // 3. rank, and the first k
-  rr_sort_keys(key, npad, ids);
+  block_bitonic_sort(key, npad, RankBefore<RrIdAt>{{ids}});
   const int present = cnt[1];
   for (int r = tid; r < k; r += T) {
     if (r < present) {                           // r < present <= kin <= npad
       const u64 kr = key[r];
-      const unsigned pos = (unsigned)kr & RR_POS_MASK;
-      out_scores[out0 + r] = rr_key_score(kr);
+      const unsigned pos = (unsigned)kr & RANK_POS_MASK;
+      out_scores[out0 + r] = rank_key_score(kr);
       out_idx[out0 + r] = ids[pos];
       if (out_pos) out_pos[out0 + r] = (int)pos;
     } else {
-      out_scores[out0 + r] = RR_NEG_INF;
+      out_scores[out0 + r] = RANK_NEG_INF;
       out_idx[out0 + r] = -1;
       if (out_pos) out_pos[out0 + r] = -1;
     }
@@ -254,7 +186,7 @@ extern "C" int cor_knn_reciprocal(const long long* const* seg_nbr, const long lo
   if (!seg_nbr || !seg_offset || !seg_n || nseg < 1 || k1 < 1 || seg < 0 || seg >= nseg) return COR_EINVAL;
   if (nseg > RR_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
   for (int s = 0; s < nseg; ++s)
-    if (seg_n[s] < 0 || (!seg_nbr[s] && seg_n[s] > 0)) return COR_EINVAL;
+    if (seg_entry_bad(seg_n[s], seg_nbr[s])) return COR_EINVAL;
   if (!out && seg_n[seg] > 0) return COR_EINVAL;
   if (k1 > RR_KMAX) return COR_ENOSUPPORT;
   KrSegs segs = {};
@@ -278,8 +210,8 @@ extern "C" int cor_rerank_reciprocal(const float* scores, const long long* idx, 
   if (nseg > 0 && (!seg_rnbr || !seg_kth || !seg_offset || !seg_n)) return COR_EINVAL;
   if (nseg > RR_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
   for (int s = 0; s < nseg; ++s)
-    if (seg_n[s] < 0 || ((!seg_rnbr[s] || !seg_kth[s]) && seg_n[s] > 0)) return COR_EINVAL;
-  if (kin > RR_NMAX || k > RR_KMAX || k1 > RR_KMAX || kg > RR_KMAX) return COR_ENOSUPPORT;
+    if (seg_entry_bad(seg_n[s], seg_rnbr[s] && seg_kth[s])) return COR_EINVAL;
+  if (kin > COR_MERGE_NMAX || k > RR_KMAX || k1 > RR_KMAX || kg > RR_KMAX) return COR_ENOSUPPORT;
   RrSegs segs = {};
   bool vec = (kg & 1) == 0;                                              // rows of kg ids are 16-byte aligned if the base is and kg is even
   for (int s = 0; s < nseg; ++s) {
@@ -290,9 +222,7 @@ extern "C" int cor_rerank_reciprocal(const float* scores, const long long* idx, 
     if (seg_n[s] > 0 && ((uintptr_t)seg_rnbr[s] & 15)) vec = false;
   }
   if (Bq == 0) return 0;
-  int npad = 2, apad = 2;
-  while (npad < kin) npad <<= 1;
-  while (apad < k1) apad <<= 1;
+  const int npad = next_pow2(kin), apad = next_pow2(k1);
   const int threads = npad < 64 ? 64 : (npad > 1024 ? 1024 : npad);
   const size_t lds = 8 * (size_t)npad + 8 * RR_KMAX + 16;
   const dim3 grid((unsigned)Bq), block(threads);

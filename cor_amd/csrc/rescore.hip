@@ -8,40 +8,19 @@
 //      loads (thread-per-candidate gather) and their four fmaf chains advance interleaved: a chain is C dependent fmaf, four of them
 //      fill the issue slots between. The order inside a chain is that of oracle/c/sim_chain.c: chunk c of 8, k = 8c+i then 8c+4+i.
 //   2. Rank. Every position becomes a 64-bit key in LDS, [order-preserving score key, descending | -0.0 flag | position]; a missing
-//      entry and the padding carry the largest score key and sort last. The bitonic network of merge.hip ranks them: equal score keys
-//      are decided by the 64-bit id read through the position, then by the rest of the key. Repeats of an id have the same score
-//      bits, so they end up adjacent, the first occurrence in front.
+//      entry and the padding carry the largest score key and sort last (ranklist.h has the scheme and the tie rule). Repeats of an id
+//      have the same score bits, so they end up adjacent, the first occurrence in front.
 //   3. Place. keep[r] = rank r is present and the rank before it holds another id; a block scan over the keep flags places the first k
 //      survivors, the rest of the k slots get (-inf, -1, -1). The score bits come back out of the key (the flag restores -0.0).
 // LDS: 8 B per key + 1 B keep flag per rank + 1 KiB query = 37 KiB at kin = 4096; no scratch memory in global.
-#include "common.h"
+#include "ranklist.h"
 
 namespace {
 
-constexpr int RS_NMAX = COR_MERGE_NMAX;        // candidates per query: 4096 = 12 position bits in the key
-static_assert(RS_NMAX == 4096, "the sort keys carry 12 position bits and bit 12 is the -0.0 flag");
-constexpr unsigned RS_POS_MASK = RS_NMAX - 1;
-constexpr unsigned RS_NEGZERO = RS_NMAX;       // bit 12 of the key's low word: the score is -0.0 (its score key is that of +0.0)
-constexpr unsigned RS_MISSING = 0xffffffffu;   // score key of missing entries and padding: above every non-NaN score's key
-constexpr unsigned RS_NEG_INF = 0xff800000u;
 constexpr int RS_CMAX = 256;                   // embedding width limit of the searches
 constexpr int RS_NI = 4;                       // candidates per thread, chains interleaved
 
-typedef unsigned long long u64;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// float bits -> key that ascends as the score DEscends; -0.0 keys as +0.0
-__device__ __forceinline__ unsigned rs_score_key(unsigned u) {
-  if (u == 0x80000000u) u = 0u;
-  const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-// and back: the score bits of a present entry's key
-__device__ __forceinline__ unsigned rs_key_score(u64 key) {
-  if ((unsigned)key & RS_NEGZERO) return 0x80000000u;
-  const unsigned asc = ~(unsigned)(key >> 32);
-  return (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-}
 
 // elements [16 s, 16 s + 16) of a gallery row, widened exactly to fp32 (16-byte loads; rows are 16-byte aligned, C % 16 == 0)
 template <typename TG> __device__ __forceinline__ void rs_load16(const TG* __restrict__ row, int s, float (&g)[16]) {
@@ -72,31 +51,9 @@ template <typename TG> __device__ __forceinline__ void rs_load16(const TG* __res
 
 struct RsList {
   const long long* ids;   // this query's kin candidates
-  __device__ __forceinline__ long long at(u64 key) const { return ids[(unsigned)key & RS_POS_MASK]; }
+  __device__ __forceinline__ long long operator()(unsigned pos) const { return ids[pos]; }
+  __device__ __forceinline__ long long at(u64 key) const { return ids[(unsigned)key & RANK_POS_MASK]; }
 };
-
-__device__ __forceinline__ bool rs_before(u64 a, u64 b, const RsList& L) {
-  const unsigned ha = (unsigned)(a >> 32), hb = (unsigned)(b >> 32);
-  if (ha == hb && ha != RS_MISSING) {            // a tie between two PRESENT entries: positions < kin
-    const long long ia = L.at(a), ib = L.at(b);
-    if (ia != ib) return ia < ib;
-  }
-  return a < b;
-}
-
-// ascending bitonic sort of key[0, npad) (npad a power of two >= 2); ends with a barrier
-__device__ void rs_sort(u64* key, int npad, const RsList& L) {
-  const int half = npad >> 1;
-  for (int size = 2; size <= npad; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < half; t += blockDim.x) {
-        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-        const u64 a = key[i], b = key[j];
-        if (rs_before(b, a, L) == ((i & size) == 0)) { key[i] = b; key[j] = a; }
-      }
-      __syncthreads();
-    }
-}
 
 template <typename TG>
 __global__ __launch_bounds__(1024) void rescore_topk_kernel(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C,
@@ -163,70 +120,47 @@ __global__ __launch_bounds__(1024) void rescore_topk_kernel(const float* __restr
   for (int j = 0; j < RS_NI; ++j) {
     const int pos = tid + j * T;
     if (pos < npad) {
-      unsigned hi = RS_MISSING, lo = (unsigned)pos;
+      unsigned hi = RANK_MISSING, lo = (unsigned)pos;
       if (row[j]) {
         const unsigned u = __float_as_uint(acc[j]);
-        hi = rs_score_key(u);
-        if (u == 0x80000000u) lo |= RS_NEGZERO;
+        hi = rank_score_key(u);
+        if (u == 0x80000000u) lo |= RANK_NEGZERO;
       }
-      mine += hi != RS_MISSING;                  // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
+      mine += hi != RANK_MISSING;                // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
       key[pos] = ((u64)hi << 32) | lo;
     }
   }
   if (mine) atomicAdd(&s_present, mine);
   __syncthreads();
-  rs_sort(key, npad, L);
+  block_bitonic_sort(key, npad, RankBefore<RsList>{L});
   const int present = s_present;
 
   // 3. one entry per id (the first of every run of equal ids: the lowest position), the first k of them
   for (int r = tid; r < npad; r += T) keep[r] = r < present && (r == 0 || L.at(key[r - 1]) != L.at(key[r]));
   __syncthreads();
-  // exclusive scan of the keep flags in rank order: thread t owns ranks [t*chunk, (t+1)*chunk)
-  const int chunk = (npad + T - 1) / T, lo_r = min(tid * chunk, npad), hi_r = min(lo_r + chunk, npad);
-  int cnt = 0;
-  for (int r = lo_r; r < hi_r; ++r) cnt += keep[r];
-  const int lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
-  int incl = cnt;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) s_wsum[wave] = incl;
-  __syncthreads();
-  int before = 0, total = 0;
-  for (int w = 0; w < nwaves; ++w) {
-    const int v = s_wsum[w];
-    if (w < wave) before += v;
-    total += v;
-  }
-  int o = before + incl - cnt;
-  for (int r = lo_r; r < hi_r && o < k; ++r)
+  const KeepScan sc = rank_keep_scan(keep, npad, s_wsum);
+  int o = sc.slot;
+  for (int r = sc.lo; r < sc.hi && o < k; ++r)
     if (keep[r]) {
       const u64 kr = key[r];
-      out_scores[out0 + o] = rs_key_score(kr);
+      out_scores[out0 + o] = rank_key_score(kr);
       out_idx[out0 + o] = L.at(kr);
-      if (out_pos) out_pos[out0 + o] = (int)((unsigned)kr & RS_POS_MASK);
+      if (out_pos) out_pos[out0 + o] = (int)((unsigned)kr & RANK_POS_MASK);
       ++o;
     }
-  for (int t = min(total, k) + tid; t < k; t += T) {
-    out_scores[out0 + t] = RS_NEG_INF;
-    out_idx[out0 + t] = -1;
-    if (out_pos) out_pos[out0 + t] = -1;
-  }
+  rank_fill_tail(sc.total, k, out0, out_scores, out_idx, out_pos);
 }
 
 int rescore_shape_check(int Bq, int kin, int k) {
   if (Bq < 0 || kin < 1 || k < 1 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  if (kin > RS_NMAX) return COR_ENOSUPPORT;
+  if (kin > COR_MERGE_NMAX) return COR_ENOSUPPORT;
   return 0;
 }
 
 template <typename TG>
 int launch_rescore(const float* Q, const void* G, int Bq, int Ng, int C, long long g_offset, const long long* cand, int kin, int k,
                    float* out_scores, long long* out_idx, int* out_pos, hipStream_t s) {
-  int npad = 2;
-  while (npad < kin) npad <<= 1;
+  const int npad = next_pow2(kin);
   const int threads = npad / RS_NI < 64 ? 64 : npad / RS_NI;         // <= 1024; RS_NI * threads >= npad
   const size_t lds = 9 * (size_t)npad + 4 * RS_CMAX;
   hipLaunchKernelGGL(rescore_topk_kernel<TG>, dim3((unsigned)Bq), dim3(threads), lds, s, Q, (const TG*)G, Ng, C, g_offset, cand, kin, npad,

@@ -543,6 +543,37 @@ def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=
     return scores, idx
 
 
+def _list_front(who, scores, idx):
+    """The checks of a (scores f32, idx i64) [Bq,kin] list as a search, the merge or the re-scoring return it. Returns (Bq, kin)."""
+    if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:
+        raise ValueError(f"{who}: scores must be float32 [Bq, kin] with kin >= 1, got {scores.dtype} {tuple(scores.shape)}")
+    if idx.shape != scores.shape or idx.dtype != torch.int64:
+        raise ValueError(f"{who}: idx must be int64 {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
+    return scores.shape
+
+
+def _disjoint_spans(who, segments):
+    """ValueError if the id ranges of two non-empty segments [(rows-like, .., offset)] overlap."""
+    spans = sorted((seg[-1], seg[-1] + seg[0].shape[0]) for seg in segments if seg[0].shape[0])
+    for (_, hi), (lo, _) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise ValueError(f"{who}: the segments' id ranges overlap")
+
+
+def _seg_arrays(offsets, *tensors):
+    """The ctypes segment table of a call, never zero-length: one pointer array per list of tensors (NULL for an empty tensor), the offsets,
+    the row counts of the first list."""
+    c, n = nat.C, max(len(offsets), 1)
+    ptrs = [(c.c_void_p * n)(*[t.data_ptr() or None for t in ts]) for ts in tensors]
+    return (*ptrs, (c.c_longlong * n)(*offsets), (c.c_int * n)(*[t.shape[0] for t in tensors[0]]))
+
+
+def _list_outputs(Bq, k, dev, third, missing=False):
+    """(scores f32, idx i64, third i32 or None), each [Bq,k]: a list kernel's outputs; missing: the (-inf, -1, -1) lists instead of empty tensors."""
+    new = (lambda v, dt: torch.full((Bq, k), v, dtype=dt, device=dev)) if missing else (lambda v, dt: torch.empty((Bq, k), dtype=dt, device=dev))
+    return new(float("-inf"), torch.float32), new(-1, torch.int64), new(-1, torch.int32) if third else None
+
+
 def merge_topk(scores, idx, k, groups=None):
     """Merge P top-k lists per query on the device (cor_merge_topk): scores f32 [P,B,kin], idx i64 [P,B,kin] (global row ids; < 0 =
     missing, ranked after every present entry), as P searches return them, stacked -> (scores f32[B,k], idx i64[B,k]) ordered by
@@ -569,9 +600,7 @@ def merge_topk(scores, idx, k, groups=None):
     if nbytes < 0:
         nat.check(int(nbytes), "cor_merge_topk_workspace_bytes")
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device) if nbytes else None
-    out_s = torch.empty((B, k), dtype=torch.float32, device=scores.device)
-    out_i = torch.empty((B, k), dtype=torch.int64, device=scores.device)
-    out_g = torch.empty((B, k), dtype=torch.int32, device=scores.device) if groups is not None else None
+    out_s, out_i, out_g = _list_outputs(B, k, scores.device, groups is not None)
     if B:                                                     # (no queries: empty tensors have no address to pass)
         nat.check(lib.cor_merge_topk(scores.data_ptr(), idx.data_ptr(), _p(groups) or None, P, B, kin, k, out_s.data_ptr(), out_i.data_ptr(),
                                      _p(out_g) or None, _p(ws) or None, _s()), "cor_merge_topk")
@@ -602,11 +631,7 @@ def rescore_topk(Q, G, cand, k, g_offset=0, return_pos=False):
     if nbytes < 0:
         nat.check(int(nbytes), "cor_rescore_workspace_bytes")
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device) if nbytes else None
-    out_s = torch.full((Bq, k), float("-inf"), dtype=torch.float32, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.float32, device=Q.device)
-    out_i = torch.full((Bq, k), -1, dtype=torch.int64, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.int64, device=Q.device)
-    out_p = None
-    if return_pos:
-        out_p = torch.full((Bq, k), -1, dtype=torch.int32, device=Q.device) if Ng == 0 else torch.empty((Bq, k), dtype=torch.int32, device=Q.device)
+    out_s, out_i, out_p = _list_outputs(Bq, k, Q.device, return_pos, missing=Ng == 0)
     if Bq and Ng:                                             # (no queries / no rows: empty tensors have no address to pass)
         nat.check(lib.cor_rescore_topk(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, int(g_offset), cand.data_ptr(), kin, k, out_s.data_ptr(),
                                        out_i.data_ptr(), _p(out_p) or None, _p(ws) or None, _s()), "cor_rescore_topk")
@@ -626,11 +651,7 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
     segments = [(r, int(o)) for r, o in segments]
     if len(segments) > nat.EXPAND_SEGMAX:
         raise ValueError(f"expand_queries: {len(segments)} segments, one call reads at most {nat.EXPAND_SEGMAX}")
-    if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:
-        raise ValueError(f"expand_queries: scores must be float32 [Bq, kin] with kin >= 1, got {scores.dtype} {tuple(scores.shape)}")
-    if idx.shape != scores.shape or idx.dtype != torch.int64:
-        raise ValueError(f"expand_queries: idx must be int64 {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
-    Bq, kin = scores.shape
+    Bq, kin = _list_front("expand_queries", scores, idx)
     if not 1 <= int(m) <= min(kin, nat.TOPK_KMAX):
         raise ValueError(f"expand_queries: m must be in [1, min(kin, {nat.TOPK_KMAX})] (kin = {kin}), got {m}")
     if int(alpha) != alpha or not 0 <= int(alpha) <= 8:
@@ -650,10 +671,7 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
     for r, o in segments:
         if r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
             raise ValueError(f"expand_queries: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
-    spans = sorted((o, o + r.shape[0]) for r, o in segments if r.shape[0])
-    for (_, hi), (lo, _) in zip(spans, spans[1:]):
-        if lo < hi:
-            raise ValueError("expand_queries: the segments' id ranges overlap")
+    _disjoint_spans("expand_queries", segments)
     if out is not None and (out.shape != (Bq, C) or out.dtype != out_dtype or not out.is_contiguous()):
         raise ValueError(f"expand_queries: out must be a contiguous {out_dtype} [{Bq}, {C}] tensor")
     dev = _dev(Q, scores, idx, out, *[r for r, _ in segments])
@@ -663,11 +681,8 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
     if out is None:
         out = torch.empty((Bq, C), dtype=out_dtype, device=dev)
     n = len(segments)
-    c = nat.C
-    seg_rows = (c.c_void_p * max(n, 1))(*[r.data_ptr() or None for r in rows])
-    seg_off = (c.c_longlong * max(n, 1))(*[o for _, o in segments])
-    seg_n = (c.c_int * max(n, 1))(*[r.shape[0] for r in rows])
-    seg_dt = (c.c_int * max(n, 1))(*[_dt(r) for r in rows])
+    seg_rows, seg_off, seg_n = _seg_arrays([o for _, o in segments], rows)
+    seg_dt = (nat.C.c_int * max(n, 1))(*[_dt(r) for r in rows])
     if Bq:                                                    # (no queries: empty tensors have no address to pass)
         nat.check(_lib().cor_expand_queries(_p(Q) or None, query_weight, seg_rows, seg_off, seg_n, seg_dt, n, scores.data_ptr(), idx.data_ptr(),
                                             Bq, kin, int(m), C, int(alpha), int(bool(normalize)), out.data_ptr(), _DT[out_dtype], _s()),
@@ -679,10 +694,7 @@ def _graph_spans(who, segments):
     """Shared check of a graph's segment list [(…, offset)] whose first tensor has one row per gallery row: count and disjoint ranges."""
     if len(segments) > nat.RERANK_SEGMAX:
         raise ValueError(f"{who}: {len(segments)} segments, one call reads at most {nat.RERANK_SEGMAX}")
-    spans = sorted((seg[-1], seg[-1] + seg[0].shape[0]) for seg in segments if seg[0].shape[0])
-    for (_, hi), (lo, _) in zip(spans, spans[1:]):
-        if lo < hi:
-            raise ValueError(f"{who}: the segments' id ranges overlap")
+    _disjoint_spans(who, segments)
 
 
 def knn_reciprocal(segments, seg, out=None):
@@ -709,13 +721,9 @@ def knn_reciprocal(segments, seg, out=None):
     lists = [t.contiguous() for t, _ in segments]
     if out is None:
         out = torch.empty(mine.shape, dtype=torch.int64, device=dev)
-    n = len(segments)
-    c = nat.C
-    seg_nbr = (c.c_void_p * n)(*[t.data_ptr() or None for t in lists])
-    seg_off = (c.c_longlong * n)(*[o for _, o in segments])
-    seg_n = (c.c_int * n)(*[t.shape[0] for t in lists])
+    seg_nbr, seg_off, seg_n = _seg_arrays([o for _, o in segments], lists)
     if mine.shape[0]:                                         # (no rows: empty tensors have no address to pass)
-        nat.check(_lib().cor_knn_reciprocal(seg_nbr, seg_off, seg_n, n, k1, int(seg), out.data_ptr(), _s()), "cor_knn_reciprocal")
+        nat.check(_lib().cor_knn_reciprocal(seg_nbr, seg_off, seg_n, len(segments), k1, int(seg), out.data_ptr(), _s()), "cor_knn_reciprocal")
     return out
 
 
@@ -730,11 +738,7 @@ def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
     (-inf, -1, -1) tail. include/cor_amd.h has the definition to the bit. 1 <= k1 <= min(kin, 256), 1 <= k <= 256, kin <= nat.MERGE_NMAX
     (4096; beyond that NativeError), lam finite. No host synchronisation; capturable in a graph."""
     segments = [(r, t, int(o)) for r, t, o in segments]
-    if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:
-        raise ValueError(f"rerank_reciprocal: scores must be float32 [Bq, kin] with kin >= 1, got {scores.dtype} {tuple(scores.shape)}")
-    if idx.shape != scores.shape or idx.dtype != torch.int64:
-        raise ValueError(f"rerank_reciprocal: idx must be int64 {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
-    Bq, kin = scores.shape
+    Bq, kin = _list_front("rerank_reciprocal", scores, idx)
     if not 1 <= int(k) <= nat.TOPK_KMAX:
         raise ValueError(f"rerank_reciprocal: k must be in [1, {nat.TOPK_KMAX}], got {k}")
     if not 1 <= int(k1) <= min(kin, nat.TOPK_KMAX):
@@ -754,17 +758,10 @@ def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
     dev = _dev(scores, idx, *[x for r, t, _ in segments for x in (r, t)])
     scores, idx = scores.contiguous(), idx.contiguous()
     lists, kths = [r.contiguous() for r, _, _ in segments], [t.contiguous() for _, t, _ in segments]
-    out_s = torch.empty((Bq, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((Bq, k), dtype=torch.int64, device=dev)
-    out_p = torch.empty((Bq, k), dtype=torch.int32, device=dev) if return_pos else None
-    n = len(segments)
-    c = nat.C
-    seg_rnbr = (c.c_void_p * max(n, 1))(*[r.data_ptr() or None for r in lists])
-    seg_kth = (c.c_void_p * max(n, 1))(*[t.data_ptr() or None for t in kths])
-    seg_off = (c.c_longlong * max(n, 1))(*[o for _, _, o in segments])
-    seg_n = (c.c_int * max(n, 1))(*[r.shape[0] for r in lists])
+    out_s, out_i, out_p = _list_outputs(Bq, k, dev, return_pos)
+    seg_rnbr, seg_kth, seg_off, seg_n = _seg_arrays([o for _, _, o in segments], lists, kths)
     if Bq:                                                    # (no queries: empty tensors have no address to pass)
-        nat.check(_lib().cor_rerank_reciprocal(scores.data_ptr(), idx.data_ptr(), seg_rnbr, seg_kth, seg_off, seg_n, n, Bq, kin, kg, int(k1), lam,
+        nat.check(_lib().cor_rerank_reciprocal(scores.data_ptr(), idx.data_ptr(), seg_rnbr, seg_kth, seg_off, seg_n, len(segments), Bq, kin, kg, int(k1), lam,
                                                int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _s()), "cor_rerank_reciprocal")
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 

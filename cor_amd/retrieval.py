@@ -73,6 +73,24 @@ def merge_topk_distinct_host(scores_parts, idx_parts, group_parts, k: int):
     return out_s.masked_fill(tail, float("-inf")), out_i.masked_fill(tail, -1)
 
 
+def _on(dev):
+    """The context that makes `dev` the current GPU; nothing for a CPU device (whose tensors the ops' own checks refuse)."""
+    return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
+
+
+def _missing_lists(B, k, dev):
+    """The all-missing lists of B queries: (scores f32[B,k] = -inf, idx i64[B,k] = -1)."""
+    return torch.full((B, k), float("-inf"), device=dev), torch.full((B, k), -1, dtype=torch.int64, device=dev)
+
+
+def _row_ids(ids, what, n, dev):
+    """labels / group ids of a shard of n rows -> int32[n] on `dev`"""
+    ids = torch.as_tensor(ids)
+    if ids.dim() != 1 or ids.shape[0] != n:
+        raise ValueError(f"GalleryShard: {tuple(ids.shape)} {what} for {n} rows")
+    return ids.to(dev, torch.int32).contiguous()
+
+
 def _merge_stacked(s, i, g, k: int):
     """Rounds of ops.merge_topk over stacked lists s, i[, g] of shape [P, B, kin] on one GPU -> (scores, idx, groups or None), [B, k]."""
     while s.shape[0] * s.shape[2] > ops.nat.MERGE_NMAX:
@@ -198,7 +216,7 @@ def _pruned_graph(live, k1, lists):
     table = [(nbr, int(sh.offset)) for sh, (nbr, _) in zip(live, lists)]
     rnbr = []
     for n, sh in enumerate(live):
-        with torch.cuda.device(sh.rows.device) if sh.rows.is_cuda else contextlib.nullcontext():
+        with _on(sh.rows.device):
             rnbr.append(ops.knn_reciprocal(table, n))
     return NeighbourGraph(k1, [sh.offset for sh in live], [len(sh) for sh in live], rnbr, [kth for _, kth in lists])
 
@@ -209,8 +227,7 @@ def _rerank(who, live, scores, idx, graph, k1, lam, k):
         raise ValueError(f"{who}: idx must be [Bq, kin], got {tuple(idx.shape)}")
     k1 = graph.width if k1 is None else k1
     k = min(idx.shape[1], ops.nat.TOPK_KMAX) if k is None else k
-    dev = live[0].rows.device if live else scores.device
-    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+    with _on(live[0].rows.device if live else scores.device):
         return ops.rerank_reciprocal(scores, idx, graph.segments, k1, lam, k)
 
 
@@ -224,18 +241,9 @@ class GalleryShard:
             raise RuntimeError("GalleryShard lives in GPU memory (no CPU path)")
         self.rows = rows.to(dtype or rows.dtype).contiguous()
         self.offset = int(offset)
-        self.labels = None
-        if labels is not None:
-            labels = torch.as_tensor(labels)
-            if labels.dim() != 1 or labels.shape[0] != self.rows.shape[0]:
-                raise ValueError(f"GalleryShard: {tuple(labels.shape)} labels for {self.rows.shape[0]} rows")
-            self.labels = labels.to(self.rows.device, torch.int32).contiguous()
-        self.groups = None
-        if groups is not None:
-            groups = torch.as_tensor(groups)
-            if groups.dim() != 1 or groups.shape[0] != self.rows.shape[0]:
-                raise ValueError(f"GalleryShard: {tuple(groups.shape)} group ids for {self.rows.shape[0]} rows")
-            self.groups = groups.to(self.rows.device, torch.int32).contiguous()
+        n, dev = self.rows.shape[0], self.rows.device
+        self.labels = None if labels is None else _row_ids(labels, "labels", n, dev)
+        self.groups = None if groups is None else _row_ids(groups, "group ids", n, dev)
 
     def __len__(self):
         return self.rows.shape[0]
@@ -254,8 +262,7 @@ class GalleryShard:
                 raise ValueError("GalleryShard.search: query_labels given but the shard has no row labels")
             query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
         if self.rows.shape[0] == 0:                  # an empty shard (more ranks than gallery rows): all-missing lists, like Ng < k
-            return (torch.full((q.shape[0], k), float("-inf"), device=q.device),
-                    torch.full((q.shape[0], k), -1, dtype=torch.int64, device=q.device))
+            return _missing_lists(q.shape[0], k, q.device)
         with torch.cuda.device(self.rows.device):
             if distinct:
                 return ops.similarity_topk_distinct(q, self.rows, k, self.groups, None if query_labels is None else self.labels, query_labels,
@@ -274,7 +281,7 @@ class GalleryShard:
         if cand.dim() != 2:
             raise ValueError(f"GalleryShard.rescore: cand must be [Bq, kin], got {tuple(cand.shape)}")
         k = min(cand.shape[1], ops.nat.TOPK_KMAX) if k is None else k
-        with torch.cuda.device(self.rows.device) if self.rows.is_cuda else contextlib.nullcontext():
+        with _on(self.rows.device):
             return ops.rescore_topk(q, self.rows, cand, k, g_offset=self.offset, return_pos=return_pos)
 
     def expand(self, queries, scores: torch.Tensor, idx: torch.Tensor, m: int, alpha: int = 3, query_weight: float = 1.0,
@@ -284,7 +291,7 @@ class GalleryShard:
         entries of max(score, 0)^alpha * row, L2-normalised if `normalize`. Entries this shard does not hold (-1, other shards' ids)
         contribute nothing."""
         q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
-        with torch.cuda.device(self.rows.device) if self.rows.is_cuda else contextlib.nullcontext():
+        with _on(self.rows.device):
             return ops.expand_queries(q, [(self.rows, self.offset)], scores, idx, m, alpha=alpha, query_weight=query_weight,
                                       normalize=normalize, out_dtype=out_dtype, out=out)
 
@@ -365,6 +372,10 @@ class GallerySet:
     def segments(self):
         return list(self._segments)
 
+    def _live(self):
+        """The segments with rows: the ones a search, a graph or a segment table is made of."""
+        return [sh for sh in self._segments if len(sh)]
+
     @property
     def rows(self):
         """A zero-row view [0, C] of the first segment: the set has no single row matrix; this carries its device and width."""
@@ -383,25 +394,23 @@ class GallerySet:
     def entry_groups(self, idx: torch.Tensor) -> torch.Tensor:
         """Group ids (int32, same shape, on idx's device) of global row ids out of any segment; -1 for missing entries."""
         g = torch.full(idx.shape, -1, dtype=torch.int32, device=idx.device)
-        for sh in self._segments:
-            if len(sh):
-                inside = (idx >= int(sh.offset)) & (idx < int(sh.offset) + len(sh))
-                g = torch.where(inside, _entry_groups(sh, torch.where(inside, idx, torch.full_like(idx, -1))), g)
+        for sh in self._live():
+            inside = (idx >= int(sh.offset)) & (idx < int(sh.offset) + len(sh))
+            g = torch.where(inside, _entry_groups(sh, torch.where(inside, idx, torch.full_like(idx, -1))), g)
         return g
 
     def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq", distinct: bool = False):
         """GalleryShard.search over all segments: (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU. One search per non-empty segment
         and one device merge; a single non-empty segment's result is returned as it is; no segment with rows: the all-missing lists.
         distinct: the segments' entry group ids are gathered on the device and the merge keeps the best entry per group."""
-        live = [sh for sh in self._segments if len(sh)]
+        live = self._live()
         if distinct and self._segments and self.groups is None:
             raise ValueError("GallerySet.search: distinct=True but the segments have no group ids")
         if query_labels is not None and self._segments and self.labels is None:
             raise ValueError("GallerySet.search: query_labels given but the segments have no row labels")
         if not live:
-            q = queries.reshape(-1, queries.shape[-1])
-            dev = self._segments[0].rows.device if self._segments else q.device
-            return (torch.full((q.shape[0], k), float("-inf"), device=dev), torch.full((q.shape[0], k), -1, dtype=torch.int64, device=dev))
+            B = queries.reshape(-1, queries.shape[-1]).shape[0]
+            return _missing_lists(B, k, self._segments[0].rows.device if self._segments else queries.device)
         res = [sh.search(queries, k, query_labels=query_labels, mode=mode, distinct=distinct) for sh in live]
         if len(live) == 1:
             return res[0]
@@ -416,12 +425,11 @@ class GallerySet:
         scored exactly once, and the lists are merged on the device (merge_topk_device). A single non-empty segment's result is
         returned as it is; no segment with rows: the all-missing lists. For segments of one dtype the result equals bitwise that of
         a single GalleryShard over the concatenated rows."""
-        live = [sh for sh in self._segments if len(sh)]
+        live = self._live()
         if not live:
             if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
                 raise ValueError(f"GallerySet.rescore: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
-            dev = self._segments[0].rows.device if self._segments else cand.device
-            return (torch.full((cand.shape[0], k), float("-inf"), device=dev), torch.full((cand.shape[0], k), -1, dtype=torch.int64, device=dev))
+            return _missing_lists(cand.shape[0], k, self._segments[0].rows.device if self._segments else cand.device)
         res = [sh.rescore(queries, cand, k) for sh in live]
         if len(live) == 1:
             return res[0]
@@ -433,10 +441,10 @@ class GallerySet:
         """GalleryShard.expand over all segments in ONE launch: the kernel looks every listed id up in the table of the live segments
         (at most 16; their dtypes may differ), so nothing is concatenated and no per-segment partial sums exist. The result equals
         bitwise that of a single GalleryShard over the concatenated rows."""
-        live = [sh for sh in self._segments if len(sh)]
+        live = self._live()
         dev = live[0].rows.device if live else scores.device
         q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(dev, torch.float32).contiguous()
-        with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        with _on(dev):
             return ops.expand_queries(q, [(sh.rows, sh.offset) for sh in live], scores, idx, m, alpha=alpha, query_weight=query_weight,
                                       normalize=normalize, out_dtype=out_dtype, out=out)
 
@@ -449,7 +457,7 @@ class GallerySet:
         """GalleryShard.neighbour_graph over all segments: every row's top-k1 list over the WHOLE set, pruned against the lists of all
         segments (at most 16 non-empty ones). The graph is valid for the segments the set has now; add / drop do not update it."""
         _check_graph_args("GallerySet.neighbour_graph", k1, batch)
-        live = [sh for sh in self._segments if len(sh)]
+        live = self._live()
         if len(live) > ops.nat.RERANK_SEGMAX:
             raise ValueError(f"GallerySet.neighbour_graph: {len(live)} non-empty segments, a graph spans at most {ops.nat.RERANK_SEGMAX}")
         return _pruned_graph(live, int(k1), [_knn_lists(sh, int(k1), batch, self) for sh in live])
@@ -458,7 +466,7 @@ class GallerySet:
         """GalleryShard.rerank over all segments in ONE launch: the kernel looks every id up in the graph's segment table. The result
         equals bitwise that of a single GalleryShard over the concatenated rows with the same lists. ValueError if the set's non-empty
         segments are not the ones the graph was built from."""
-        return _rerank("GallerySet.rerank", [sh for sh in self._segments if len(sh)], scores, idx, graph, k1, lam, k)
+        return _rerank("GallerySet.rerank", self._live(), scores, idx, graph, k1, lam, k)
 
 
 def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int, fine_queries: torch.Tensor | None = None, **search_kwargs):
@@ -649,13 +657,14 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         raise ValueError(f"distributed_search: merge must be 'host' or 'device', got {merge!r}")
     if distinct and getattr(shard, "groups", None) is None:
         raise ValueError("distributed_search: distinct=True but the shard has no group ids")
-    if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
+
+    def search(q, labels):                                       # the three call forms the docstring promises
         if distinct:
-            s, i = shard.search(local_queries, k, query_labels=query_labels, mode=filter_mode, distinct=True)
-        elif query_labels is None:
-            s, i = shard.search(local_queries, k)
-        else:
-            s, i = shard.search(local_queries, k, query_labels=query_labels, mode=filter_mode)
+            return shard.search(q, k, query_labels=labels, mode=filter_mode, distinct=True)
+        return shard.search(q, k) if query_labels is None else shard.search(q, k, query_labels=labels, mode=filter_mode)
+
+    if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
+        s, i = search(local_queries, query_labels)
         if defer:
             both, ev = _to_host_async(_pack_lists(s, i))         # one copy instead of two
             return PendingSearch(lambda: _unpack_lists(both), ev)
@@ -689,15 +698,8 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         marks.mark()
     allb = allb.view(world, cap + 1, width)
     slots = allb[:, :cap, :C].reshape(world * cap, C).to(dev)    # every slot is scored; counts stay where they are
-    slot_labels = None
-    if query_labels is not None:
-        slot_labels = allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
-    if distinct:
-        s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode, distinct=True)
-    elif query_labels is None:
-        s, i = shard.search(slots, k)                            # local shard vs ALL query slots
-    else:
-        s, i = shard.search(slots, k, query_labels=slot_labels, mode=filter_mode)
+    slot_labels = None if query_labels is None else allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
+    s, i = search(slots, slot_labels)                            # local shard vs ALL query slots
     packed = _pack_lists(s, i)
     if distinct:                                                 # [slots,k,4]: + the entry's group id
         eg = shard.entry_groups(i) if hasattr(shard, "entry_groups") else _entry_groups(shard, i)    # (a GallerySet looks up its segments)
@@ -727,12 +729,9 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     pshape = tuple(parts.shape)
 
     def finish(host):
-        counts = host[-world:].tolist()
-        if any(c < 0 or c > cap for c in counts):
-            raise RuntimeError(f"distributed_search: inconsistent per-rank query counts {counts} for max_local={cap}")
+        keep = _kept_slots(host, world, cap)
         lists = host[:-world].view(pshape)
         ps, pi = _unpack_lists(lists[..., :3])                   # [world(shard), world*cap(slot), k]
-        keep = torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
         if distinct:
             return merge_topk_distinct_host(list(ps[:, keep]), list(pi[:, keep]), list(lists[..., 3][:, keep]), k)
         return merge_topk_host(list(ps[:, keep]), list(pi[:, keep]), k)
@@ -741,6 +740,14 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         host, ev = _to_host_async(flat)
         return PendingSearch(lambda: finish(host), ev)
     return finish(flat.cpu())
+
+
+def _kept_slots(host, world, cap):
+    """The slots that hold a query, out of the per-rank counts at the end of the host buffer: rank r's first counts[r] of its `cap`."""
+    counts = host[-world:].tolist()
+    if any(c < 0 or c > cap for c in counts):
+        raise RuntimeError(f"distributed_search: inconsistent per-rank query counts {counts} for max_local={cap}")
+    return torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
 
 
 def _finish_device_merge(parts, counts_i, k, cap, distinct, defer):
@@ -753,10 +760,7 @@ def _finish_device_merge(parts, counts_i, k, cap, distinct, defer):
     flat = torch.cat([mi.view(torch.int32).reshape(-1), ms.view(torch.int32).reshape(-1), counts_i.to(parts.device)])   # (the 8-byte indices first: aligned)
 
     def finish(host):
-        counts = host[-world:].tolist()
-        if any(c < 0 or c > cap for c in counts):
-            raise RuntimeError(f"distributed_search: inconsistent per-rank query counts {counts} for max_local={cap}")
-        keep = torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
+        keep = _kept_slots(host, world, cap)
         return host[2 * n:3 * n].view(torch.float32).view(-1, k)[keep], host[:2 * n].view(torch.int64).view(-1, k)[keep]
 
     if defer:
@@ -855,28 +859,23 @@ def save_gallery(path, rows, world=1, labels=None, groups=None):
     <path>.shardNN.groups.pt and "groups": true likewise."""
     import json
     n = rows.shape[0]
-    if labels is not None:
-        labels = torch.as_tensor(labels).reshape(-1).to(torch.int32).cpu()
-        if labels.shape[0] != n:
-            raise ValueError(f"save_gallery: {labels.shape[0]} labels for {n} rows")
-    if groups is not None:
-        groups = torch.as_tensor(groups).reshape(-1).to(torch.int32).cpu()
-        if groups.shape[0] != n:
-            raise ValueError(f"save_gallery: {groups.shape[0]} group ids for {n} rows")
+    ids = {}                                                     # "labels" / "groups" -> int32[n] on the host, those that were given
+    for name, what, t in (("labels", "labels", labels), ("groups", "group ids", groups)):
+        if t is not None:
+            ids[name] = torch.as_tensor(t).reshape(-1).to(torch.int32).cpu()
+            if ids[name].shape[0] != n:
+                raise ValueError(f"save_gallery: {ids[name].shape[0]} {what} for {n} rows")
     shards = []
     for r in range(world):
         lo, hi = shard_bounds(n, world, r)
         torch.save(rows[lo:hi].cpu().contiguous(), f"{path}.shard{r:02d}.pt")
         shards.append(dict(rank=r, lo=lo, hi=hi, file=f"{path}.shard{r:02d}.pt"))
-        if labels is not None:
-            torch.save(labels[lo:hi].clone(), f"{path}.shard{r:02d}.labels.pt")
-            shards[-1]["labels_file"] = f"{path}.shard{r:02d}.labels.pt"
-        if groups is not None:
-            torch.save(groups[lo:hi].clone(), f"{path}.shard{r:02d}.groups.pt")
-            shards[-1]["groups_file"] = f"{path}.shard{r:02d}.groups.pt"
+        for name, t in ids.items():
+            torch.save(t[lo:hi].clone(), f"{path}.shard{r:02d}.{name}.pt")
+            shards[-1][f"{name}_file"] = f"{path}.shard{r:02d}.{name}.pt"
     with open(f"{path}.manifest.json", "w") as f:
-        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels=labels is not None,
-                       groups=groups is not None, shards=shards), f, indent=1)
+        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels="labels" in ids,
+                       groups="groups" in ids, shards=shards), f, indent=1)
 
 
 def load_gallery_shard(path, rank, device):

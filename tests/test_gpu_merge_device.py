@@ -83,7 +83,7 @@ def _lookup(s, i, g, out_i):
     return out
 
 
-CASES = [(2, 1, 1, 1), (2, 3, 4, 4), (3, 4, 7, 5), (4, 2, 10, 64), (8, 33, 10, 10), (8, 5, 256, 256), (16, 2, 256, 256)]
+CASES = [(1, 1, 1, 1), (1, 2, 5, 3), (2, 1, 1, 1), (2, 3, 4, 4), (3, 4, 7, 5), (4, 2, 10, 64), (8, 33, 10, 10), (8, 5, 256, 256), (16, 2, 256, 256)]
 
 
 @pytest.mark.parametrize("distinct", [False, True], ids=["plain", "distinct"])

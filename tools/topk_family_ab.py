@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Same-process A/B of the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct) between ANOTHER build of the library
-(the parent commit's libcor_amd.so) and this one, for changes that must leave results and speed as they are.
-    python tools/topk_family_ab.py PARENT_LIB.so [ROUNDS=5] [OUT=profiles/topk_family_ab.jsonl]
+"""Same-process A/B between ANOTHER build of the library (the parent commit's libcor_amd.so) and this one, for changes that must leave
+results and speed as they are. Two case tables: `topk`, the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct), and
+`lists`, the list kernels (cor_merge_topk, cor_rescore_topk, cor_rerank_reciprocal, cor_knn_reciprocal, cor_expand_queries) at the shapes of
+their own bench tools.
+    python tools/topk_family_ab.py PARENT_LIB.so [ROUNDS=5] [OUT=profiles/topk_family_ab.jsonl] [TABLE=topk]
 "This one" is the library cor_amd loads (COR_AMD_LIB selects another build of it).
 Both sides are called through ctypes with preallocated outputs and workspace, so they carry the same host work. Per case: the results of
-the two builds must be bitwise equal (scores and indices), then ROUNDS rounds alternate parent / new; a round is one window of >= 50 ms
+the two builds must be bitwise equal (every output), then ROUNDS rounds alternate parent / new; a round is one window of >= 50 ms
 (at least 20 calls, HIP events on the launch stream) after warm-up. The yardstick is the parent's own round-to-round spread: the run
 fails if a case's new median exceeds the parent median by more than the parent's (max - min). One JSON line per case; OUT is written
 afresh by every run, so it holds one run."""
@@ -17,12 +19,13 @@ from cor_amd import _native as nat
 dev = "cuda:0"
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "topk_family_ab.jsonl")
+TABLE = sys.argv[4] if len(sys.argv) > 4 else "topk"
 DT = {torch.float32: nat.F32, torch.bfloat16: nat.BF16, torch.float16: nat.F16}
 
 new = nat.load()
 parent = C.CDLL(os.path.abspath(sys.argv[1]))
 for name, sig in nat.SIGNATURES.items():
-    if "topk" in name and hasattr(parent, name):
+    if hasattr(parent, name):
         getattr(parent, name).argtypes = sig
         getattr(parent, name).restype = C.c_long if name.endswith("_bytes") else C.c_int
 
@@ -67,31 +70,127 @@ def gallery(Bq, Ng, Cc, dt):
     return Q, G, groups, own
 
 
-CASES = [("wide", 512, 1000000, 100, 256, torch.bfloat16), ("wide", 512, 125000, 100, 256, torch.bfloat16), ("wide", 64, 20000, 50, 128, torch.float32),
-         ("filtered_ne", 512, 1000000, 100, 256, torch.bfloat16), ("distinct", 512, 1000000, 100, 256, torch.bfloat16),
-         ("distinct", 512, 1000000, 10, 256, torch.bfloat16)]
-rows, data = [], None
-for route, Bq, Ng, k, Cc, dt in CASES:
-    if data is None or data[0] != (Bq, Ng, Cc, dt):
-        data = ((Bq, Ng, Cc, dt), gallery(Bq, Ng, Cc, dt))
-    Q, G, groups, own = data[1]
-    fp, sp, ip = caller(parent, route, Q, G, k, groups, own)
-    fn, sn, inn = caller(new, route, Q, G, k, groups, own)
+def _enqueue(f, args, keep):
+    def fn():
+        rc = f(*args, torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, rc
+        return keep                                          # keeps the buffers alive with the closure
+    return fn
+
+
+def _outputs(Bq, k, third):
+    outs = [torch.empty((Bq, k), device=dev), torch.empty((Bq, k), dtype=torch.int64, device=dev)]
+    return outs + ([torch.empty((Bq, k), dtype=torch.int32, device=dev)] if third else [])
+
+
+def _rand(shape, seed, **kw):
+    return torch.rand(shape, device=dev, generator=torch.Generator(device=dev).manual_seed(seed), **kw)
+
+
+def _ids(Bq, kin, N, seed):
+    """i64 [Bq,kin], pairwise different within a row: an arithmetic walk with an odd step through N = 2^j ids"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    base, step = torch.randint(0, N, (Bq, 1), device=dev, generator=g), 2 * torch.randint(0, N // 2, (Bq, 1), device=dev, generator=g) + 1
+    return ((base + step * torch.arange(kin, device=dev)) % N).contiguous()
+
+
+def list_data(kernel, Bq, kin, dt, N=131072, Cc=256, KG=20):
+    """the inputs of one list-kernel case, shared by both builds (the shapes of tools/{merge,rescore,rerank,expand}_bench.py)"""
+    d = dict(scores=torch.sort(_rand((Bq, kin), kin), dim=1, descending=True).values.contiguous(), idx=_ids(Bq, kin, N, kin + 1))
+    if kernel == "merge":                                    # P = 8 sorted lists with distinct ids; an image's regions meet across lists
+        P = 8
+        d["scores"] = torch.sort(_rand((P, Bq, kin), kin), dim=2, descending=True).values.contiguous()
+        local = torch.argsort(_rand((P, Bq, 4 * kin), kin + 1), dim=2)[..., :kin]
+        d["idx"] = (local + torch.arange(P, device=dev).view(P, 1, 1) * 4 * kin).contiguous()
+        d["groups"] = (local // 2).to(torch.int32).contiguous()
+    elif kernel in ("rescore", "expand"):
+        d["Q"] = torch.nn.functional.normalize(_rand((Bq, Cc), 3) - 0.5, dim=-1)
+        d["G"] = torch.nn.functional.normalize(_rand((N, Cc), 4) - 0.5, dim=-1).to(dt)
+    else:                                                    # rerank, knn: a graph of width KG, about a third of the slots empty
+        g = torch.Generator(device=dev).manual_seed(5)
+        d["rnbr"] = torch.randint(0, N, (N, KG), device=dev, generator=g)
+        d["rnbr"][_rand((N, KG), 6) < 0.3] = -1
+        d["kth"] = (_rand((N,), 7) >= 0.5).float()           # half of the rows count any query among their nearest
+    return d
+
+
+def list_caller(lib, kernel, d, Bq, kin, k, variant):
+    """(fn, outputs): fn() enqueues one call of the list kernel on the current stream"""
+    c = C
+    if kernel == "merge":
+        grp = d["groups"] if variant == "distinct" else None
+        outs = _outputs(Bq, k, grp is not None)
+        args = (d["scores"].data_ptr(), d["idx"].data_ptr(), grp.data_ptr() if grp is not None else None, 8, Bq, kin, k, outs[0].data_ptr(), outs[1].data_ptr(),
+                outs[2].data_ptr() if grp is not None else None, None)
+        return _enqueue(lib.cor_merge_topk, args, outs), outs
+    if kernel == "rescore":
+        outs = _outputs(Bq, k, True)
+        G = d["G"]
+        args = (d["Q"].data_ptr(), G.data_ptr(), DT[G.dtype], Bq, G.shape[0], G.shape[1], 0, d["idx"].data_ptr(), kin, k, outs[0].data_ptr(), outs[1].data_ptr(),
+                outs[2].data_ptr(), None)
+        return _enqueue(lib.cor_rescore_topk, args, outs), outs
+    one_i, one_ll = (c.c_int * 1), (c.c_longlong * 1)
+    if kernel == "expand":                                   # k is m here
+        G = d["G"]
+        outs = [torch.empty((Bq, G.shape[1]), device=dev)]
+        tabs = ((c.c_void_p * 1)(G.data_ptr()), one_ll(0), one_i(G.shape[0]), one_i(DT[G.dtype]))
+        args = (d["Q"].data_ptr(), 1.0, *tabs, 1, d["scores"].data_ptr(), d["idx"].data_ptr(), Bq, kin, k, G.shape[1], 3, 1, outs[0].data_ptr(), nat.F32)
+        return _enqueue(lib.cor_expand_queries, args, (outs, tabs)), outs
+    N, KG = d["rnbr"].shape
+    if kernel == "knn":                                      # the graph's own lists as the neighbour lists of one segment
+        outs = [torch.empty((N, KG), dtype=torch.int64, device=dev)]
+        tabs = ((c.c_void_p * 1)(d["rnbr"].data_ptr()), one_ll(0), one_i(N))
+        return _enqueue(lib.cor_knn_reciprocal, (*tabs, 1, KG, 0, outs[0].data_ptr()), (outs, tabs)), outs
+    outs = _outputs(Bq, k, True)
+    tabs = ((c.c_void_p * 1)(d["rnbr"].data_ptr()), (c.c_void_p * 1)(d["kth"].data_ptr()), one_ll(0), one_i(N))
+    args = (d["scores"].data_ptr(), d["idx"].data_ptr(), *tabs, 1, Bq, kin, KG, 20, 0.3, k, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr())
+    return _enqueue(lib.cor_rerank_reciprocal, args, (outs, tabs)), outs
+
+
+def ab(desc, fp, outs_p, fn, outs_n):
+    """one case: bitwise-equal outputs, then the alternating rounds and the yardstick"""
     for f in (fp, fn, fp, fn, fp, fn):                       # warm-up, and the results to compare
         f()
     torch.cuda.synchronize()
-    assert torch.equal(ip, inn) and torch.equal(sp.view(torch.int32), sn.view(torch.int32)), f"{route} {Bq}x{Ng} k={k}: parent and new differ"
+    for a, b in zip(outs_p, outs_n):
+        assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), f"{desc}: parent and new differ"
     m = max(20, min(1000, int(50e3 / max(window(fp, 5), 1.0))))
     us_p, us_n = [], []
     for _ in range(ROUNDS):
         us_p.append(window(fp, m)); us_n.append(window(fn, m))
     mp, mn, spread = statistics.median(us_p), statistics.median(us_n), max(us_p) - min(us_p)
-    r = dict(route=route, Bq=Bq, Ng=Ng, k=k, C=Cc, dtype=str(dt), calls_per_round=m, us_parent=us_p, us_new=us_n, median_parent=mp, median_new=mn,
-             parent_spread=spread, bitwise_equal=True, within_margin=mn <= mp + spread)
+    r = dict(desc, calls_per_round=m, us_parent=us_p, us_new=us_n, median_parent=mp, median_new=mn, parent_spread=spread, bitwise_equal=True,
+             within_margin=mn <= mp + spread)
     print(json.dumps(r), flush=True)
-    rows.append(r)
+    return r
+
+
+CASES = [("wide", 512, 1000000, 100, 256, torch.bfloat16), ("wide", 512, 125000, 100, 256, torch.bfloat16), ("wide", 64, 20000, 50, 128, torch.float32),
+         ("filtered_ne", 512, 1000000, 100, 256, torch.bfloat16), ("distinct", 512, 1000000, 100, 256, torch.bfloat16),
+         ("distinct", 512, 1000000, 10, 256, torch.bfloat16)]
+# (kernel, Bq, kin, k (expand: m), gallery dtype, variant)
+LIST_CASES = ([("merge", 512, kin, kin, None, v) for kin in (100, 256) for v in ("plain", "distinct")]
+              + [("rescore", 512, kin, 10, dt, "") for kin in (256, 4096) for dt in (torch.float32, torch.bfloat16)]
+              + [("rerank", 512, kin, 10, None, "") for kin in (256, 1024)] + [("knn", 0, 20, 20, None, "")]
+              + [("expand", 512, 256, m, torch.bfloat16, "") for m in (10, 256)])
+rows, data = [], None
+for route, Bq, Ng, k, Cc, dt in CASES if TABLE == "topk" else []:
+    if data is None or data[0] != (Bq, Ng, Cc, dt):
+        data = ((Bq, Ng, Cc, dt), gallery(Bq, Ng, Cc, dt))
+    Q, G, groups, own = data[1]
+    fp, sp, ip = caller(parent, route, Q, G, k, groups, own)
+    fn, sn, inn = caller(new, route, Q, G, k, groups, own)
+    rows.append(ab(dict(route=route, Bq=Bq, Ng=Ng, k=k, C=Cc, dtype=str(dt)), fp, (sp, ip), fn, (sn, inn)))
+for kernel, Bq, kin, k, dt, variant in LIST_CASES if TABLE == "lists" else []:
+    key = (kernel if kernel in ("merge", "rescore", "expand") else "graph", Bq, kin, dt)
+    if data is None or data[0] != key:
+        data = (key, list_data(kernel, Bq, kin, dt))
+    fp, outs_p = list_caller(parent, kernel, data[1], Bq, kin, k, variant)
+    fn, outs_n = list_caller(new, kernel, data[1], Bq, kin, k, variant)
+    rows.append(ab(dict(route=kernel, variant=variant, Bq=Bq, kin=kin, k=k, dtype=str(dt)), fp, outs_p, fn, outs_n))
+assert rows, f"unknown case table {TABLE!r}"
 with open(OUT, "w") as f:
     for r in rows:
         f.write(json.dumps(r) + "\n")
 bad = [r for r in rows if not r["within_margin"]]
-assert not bad, f"slower than the parent beyond its own spread: {[(r['route'], r['Bq'], r['Ng'], r['k']) for r in bad]}"
+assert not bad, f"slower than the parent beyond its own spread: {[(r['route'], r['Bq'], r.get('Ng', r.get('kin')), r['k']) for r in bad]}"
