@@ -53,14 +53,20 @@ __global__ void __launch_bounds__(256) mask_metrics_kernel(const float* pred, co
   __shared__ float red[4];
   const float* p = pred + (long)blockIdx.x * HW; const float* g = gt + (long)blockIdx.x * HW;
   float pg = 0.f, ps = 0.f, gs = 0.f, ad = 0.f;
-  for (int i = threadIdx.x; i < HW; i += 256) { const float a = p[i], b = g[i]; pg += a * b; ps += a; gs += b; ad += fabsf(a - b); }
+  // background sums (1-p)(1-g), 1-p, 1-g are summed element by element like the reference: formed as n - ps - gs + pg they
+  // cancel sums of size HW when the ground truth is almost all foreground (mdice off by 8e-2 at 1024 x 1024 with 10 background pixels)
+  float bpg = 0.f, bps = 0.f, bgs = 0.f;
+  for (int i = threadIdx.x; i < HW; i += 256) {
+    const float a = p[i], b = g[i], na = 1.f - a, nb = 1.f - b;
+    pg += a * b; ps += a; gs += b; ad += fabsf(a - b);
+    bpg += na * nb; bps += na; bgs += nb;
+  }
   pg = block_reduce(pg, red, false); ps = block_reduce(ps, red, false); gs = block_reduce(gs, red, false); ad = block_reduce(ad, red, false);
+  bpg = block_reduce(bpg, red, false); bps = block_reduce(bps, red, false); bgs = block_reduce(bgs, red, false);
   if (threadIdx.x == 0) {
     const float n = (float)HW;
     const float dice = (2.f * pg + smooth) / (ps + gs + smooth);
     const float iou = (pg + smooth) / (ps + gs - pg + smooth);
-    // background: (1-p)(1-g) summed = n - ps - gs + pg ; sums n - ps, n - gs
-    const float bpg = n - ps - gs + pg, bps = n - ps, bgs = n - gs;
     const float bdice = (2.f * bpg + smooth) / (bps + bgs + smooth);
     const float biou = (bpg + smooth) / (bps + bgs - bpg + smooth);
     float* o = out + blockIdx.x * 5;
