@@ -21,6 +21,7 @@ MERGE_NMAX = 4096    # most entries per query (P * kin) one cor_merge_topk launc
 EXPAND_SEGMAX = 16    # most gallery segments one cor_expand_queries launch reads (COR_EXPAND_SEGMAX)
 RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_reciprocal launch reads (COR_RERANK_SEGMAX)
 ORDER_REVERSE = 1 << 30    # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
+GEMM_KERNEL_SCALAR, GEMM_KERNEL_MASK, GEMM_EPILOGUE_VEC = 32, 0xff, 1 << 8    # cor_gemm_kernel_id (COR_GEMM_KERNEL_SCALAR, ..._MASK, COR_GEMM_EPILOGUE_VEC)
 KERNEL_ROWLANE, KERNEL_FEWQ, KERNEL_FLASH_MFMA, KERNEL_FLASH_PIPELINED, KERNEL_WINDOW_BLOCK = 1, 2, 3, 4, 5
 import numpy as _np
 Q_PRESCALE_HD64 = float(_np.float32(0.125) * _np.float32(1.4426950408889634))   # scale * log2(e) for head_dim 64, as a float32
@@ -31,6 +32,7 @@ _p, _i, _l, _f, _ll = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_longlong
 SIGNATURES = {
     "cor_version": [],
     "cor_gemm": [_p, _l, _p, _l, _i, _p, _l, _i, _i, _i, _i, _p, _i, _p, _p, _l, _i, _i, _p],
+    "cor_gemm_kernel_id": [_p, _l, _p, _l, _i, _p, _l, _i, _i, _i, _i, _p, _i, _p, _p, _l, _i, _i],
     "cor_layernorm": [_p, _i, _p, _i, _p, _p, _i, _i, _f, _i, _p],
     "cor_attention": [_p, _l, _l, _p, _l, _l, _p, _l, _l, _i, _p, _l, _l, _i, _i, _i, _i, _i, _i, _f, _p],
     "cor_attention_f32": [_p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _i, _i, _i, _i, _i, _i, _f, _p],

@@ -433,7 +433,13 @@ __device__ __forceinline__ void epilogue_buf_ct(FILL&& fill, PRE&& pre, BCOL&& b
         v[q4] = *(const f32x4*)(stg + row * 32 + cv * VW + 4 * q4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q4][q] = act_ct<ACT, TO>(v[q4][q]);
-        if constexpr (HAS_RES) v[q4] += res[blk % D][ps][q4];
+        if constexpr (HAS_RES) {
+          // the residual is added to the ROUNDED activation, as in the tile kernels (there the column-scale product stands between the
+          // two): left to contract, hipcc fused the GELUs' last product 0.5 x * (1 + erf) with this add into one fma, and fp32 outputs
+          // with an activation AND a residual differed from cfg 1 / 2 / 3 / 4 / 9 in the last bit (found at 289 x 264 x 192)
+#pragma clang fp contract(off)
+          v[q4] = v[q4] + res[blk % D][ps][q4];
+        }
       }
       // lanes outside C aim past num_records and are dropped by the buffer bounds check: no branch, fixed store count
       const unsigned off = (m < g.M && n < g.N) ? (unsigned)(((long)m * g.ldc + n) * (long)sizeof(TO)) : 0xFFFFFFFFu;
@@ -897,42 +903,27 @@ int launch_tile(GemmArgs g, hipStream_t s) {
   return 0;
 }
 
+// The route of one call: which kernel runs and which epilogue form it takes. ONE host function decides it, for launch_gemm and for
+// cor_gemm_kernel_id (which tests use to assert that a forced selector was not demoted). No launch and no device query: the answer
+// depends on the arguments only (pointer values included: alignment selects the scalar kernel and the scalar epilogue).
+struct GemmRoute { int kernel; int vec_epi; };
+
 template <typename TA, typename TO>
-int launch_gemm(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K,
-                const float* bias, int act, const float* col_scale, const float* residual, long ldr, int res_row_mod,
-                int cfg_arg, hipStream_t s) {
-  const int g_gemm_cfg = cfg_arg & 0xff, g_gemm_dbg = (cfg_arg & ~COR_ORDER_REVERSE) >> 8;
+GemmRoute gemm_route(const void* A, long lda, const void* W, long ldw, const void* C, long ldc, int M, int N, int K, const float* bias,
+                     const float* col_scale, const float* residual, long ldr, int cfg_arg) {
+  const int g_gemm_cfg = cfg_arg & 0xff;
   const long esz = sizeof(TA);
   const bool fast = (K * esz) % 16 == 0 && (lda * esz) % 16 == 0 && (ldw * esz) % 16 == 0 &&
                     ((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0);
-  if (!fast) {
-    hipLaunchKernelGGL((gemm_nt_small<TA, TO>), dim3(cdiv(N, 32), cdiv(M, 32)), dim3(256), 0, s, (const TA*)A, lda,
-                       (const TA*)W, ldw, (TO*)C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod);
-    COR_CHECK_LAUNCH();
-    return 0;
-  }
-  GemmArgs g;
-  g.A = (const char*)A; g.W = (const char*)W; g.C = (char*)C;
-  g.lda_b = lda * esz; g.ldw_b = ldw * esz; g.ldc = ldc;
-  g.M = M; g.N = N; g.Kb = (int)(K * esz);
-  g.stamps = nullptr;
+  if (!fast) return {COR_GEMM_KERNEL_SCALAR, 0};
 #ifdef COR_PROBES
-  if (g_gemm_dbg & 0x100000) { g.stamps = (unsigned long long*)col_scale; col_scale = nullptr; }   // probe: col_scale carries the stamp buffer
+  if (((cfg_arg & ~COR_ORDER_REVERSE) >> 8) & 0x100000) col_scale = nullptr;   // probe: col_scale carries the stamp buffer
 #endif
-  g.bias = bias; g.col_scale = col_scale; g.residual = residual; g.ldr = ldr; g.res_row_mod = res_row_mod; g.act = act;
-  g.dbg = g_gemm_dbg & 0x3fefff; g.rev = (cfg_arg & COR_ORDER_REVERSE) ? 1 : 0;
-  g.order = 1;                                       // resolved below (persistent kernel only): see set_tile
-  // bf16 outputs of the persistent kernel are stored non-temporally: with the whole-line epilogue every store instruction writes
-  // complete 128-byte lines, nothing is left for a cache to merge, and as plain stores the C stream evicts the A / W panels the K
-  // loops re-read from L2 (tools/archive/gemm_store_policy_ab.py: qkv 464 -> 436 us, lin1+GELU 685 -> 644 us on the box where it mattered;
-  // bench A/B of the final build, two alternating rounds: no nt 711 / 712, nt for outputs >= 256 MiB 713 / 720, nt for all 724 / 726
-  // triplets/s). fp32 residual outputs keep the default policy (the next LayerNorm re-reads them out of the Infinity Cache).
-  g.nt_c = (sizeof(TO) == 2 && !residual) ? 1 : 0;
-  g.group_m = ((g_gemm_dbg >> 4) & 0xff) ? ((g_gemm_dbg >> 4) & 0xff) : 8;
+  const long Kb = K * esz, lda_b = lda * esz, ldw_b = ldw * esz;
   const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  g.vec_epi = (N % 4 == 0) && (N >= 8) && (ldc % (sizeof(TO) == 2 ? 8 : 4) == 0) && al16(C) && (!bias || al16(bias)) && (!col_scale || al16(col_scale)) &&
-              (!residual || (al16(residual) && ldr % 4 == 0));
-  const bool k128 = g.Kb % ROWB == 0;                 // direct-to-LDS staging cannot zero-fill a K tail
+  const int vec_epi = (N % 4 == 0) && (N >= 8) && (ldc % (sizeof(TO) == 2 ? 8 : 4) == 0) && al16(C) && (!bias || al16(bias)) && (!col_scale || al16(col_scale)) &&
+                      (!residual || (al16(residual) && ldr % 4 == 0));
+  const bool k128 = Kb % ROWB == 0;                   // direct-to-LDS staging cannot zero-fill a K tail
   int cfg = g_gemm_cfg;
   if (cfg == 0) {
     cfg = (k128 && M >= 512 && N >= 64) ? ((N <= 256 && K >= 2048 && M >= 65536) ? 9 : COR_GEMM_DEFAULT_BIG) : 1;
@@ -957,10 +948,51 @@ int launch_gemm(const void* A, long lda, const void* W, long ldw, void* C, long 
   if (!k128 && (cfg == 2 || cfg == 3 || cfg == 4)) cfg = 1;
   if (cfg == 13 || cfg == 14) {
     const long c_bytes = (((long)M - 1) * ldc + N) * (long)sizeof(TO);
-    const bool ok = sizeof(TA) == 2 && k128 && g.vec_epi && !col_scale && N % 8 == 0 && c_bytes < (1L << 32) - 64 && !(sizeof(TO) == 2 && residual) &&
-                    (long)M * g.lda_b < (1L << 32) && (long)N * g.ldw_b < (1L << 32);   // 32-bit operand offsets
+    const bool ok = sizeof(TA) == 2 && k128 && vec_epi && !col_scale && N % 8 == 0 && c_bytes < (1L << 32) - 64 && !(sizeof(TO) == 2 && residual) &&
+                    (long)M * lda_b < (1L << 32) && (long)N * ldw_b < (1L << 32);   // 32-bit operand offsets
     if (!ok) cfg = k128 ? 2 : 1;
-    else if constexpr (sizeof(TA) == 2) {
+    else return {cfg, vec_epi};
+  }
+  if (!k128 && cfg >= 9) cfg = 1;
+  if (!(cfg == 9 || cfg == 2 || cfg == 3 || cfg == 4)) cfg = 1;   // the launch switch's default
+  return {cfg, vec_epi};
+}
+
+template <typename TA, typename TO>
+int launch_gemm(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K,
+                const float* bias, int act, const float* col_scale, const float* residual, long ldr, int res_row_mod,
+                int cfg_arg, hipStream_t s) {
+  const int g_gemm_dbg = (cfg_arg & ~COR_ORDER_REVERSE) >> 8;
+  const long esz = sizeof(TA);
+  const GemmRoute route = gemm_route<TA, TO>(A, lda, W, ldw, C, ldc, M, N, K, bias, col_scale, residual, ldr, cfg_arg);
+  if (route.kernel == COR_GEMM_KERNEL_SCALAR) {
+    hipLaunchKernelGGL((gemm_nt_small<TA, TO>), dim3(cdiv(N, 32), cdiv(M, 32)), dim3(256), 0, s, (const TA*)A, lda,
+                       (const TA*)W, ldw, (TO*)C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod);
+    COR_CHECK_LAUNCH();
+    return 0;
+  }
+  GemmArgs g;
+  g.A = (const char*)A; g.W = (const char*)W; g.C = (char*)C;
+  g.lda_b = lda * esz; g.ldw_b = ldw * esz; g.ldc = ldc;
+  g.M = M; g.N = N; g.Kb = (int)(K * esz);
+  g.stamps = nullptr;
+#ifdef COR_PROBES
+  if (g_gemm_dbg & 0x100000) { g.stamps = (unsigned long long*)col_scale; col_scale = nullptr; }   // probe: col_scale carries the stamp buffer
+#endif
+  g.bias = bias; g.col_scale = col_scale; g.residual = residual; g.ldr = ldr; g.res_row_mod = res_row_mod; g.act = act;
+  g.dbg = g_gemm_dbg & 0x3fefff; g.rev = (cfg_arg & COR_ORDER_REVERSE) ? 1 : 0;
+  g.order = 1;                                       // resolved below (persistent kernel only): see set_tile
+  // bf16 outputs of the persistent kernel are stored non-temporally: with the whole-line epilogue every store instruction writes
+  // complete 128-byte lines, nothing is left for a cache to merge, and as plain stores the C stream evicts the A / W panels the K
+  // loops re-read from L2 (tools/archive/gemm_store_policy_ab.py: qkv 464 -> 436 us, lin1+GELU 685 -> 644 us on the box where it mattered;
+  // bench A/B of the final build, two alternating rounds: no nt 711 / 712, nt for outputs >= 256 MiB 713 / 720, nt for all 724 / 726
+  // triplets/s). fp32 residual outputs keep the default policy (the next LayerNorm re-reads them out of the Infinity Cache).
+  g.nt_c = (sizeof(TO) == 2 && !residual) ? 1 : 0;
+  g.group_m = ((g_gemm_dbg >> 4) & 0xff) ? ((g_gemm_dbg >> 4) & 0xff) : 8;
+  g.vec_epi = route.vec_epi;
+  const int cfg = route.kernel;
+  if (cfg == 13 || cfg == 14) {
+    if constexpr (sizeof(TA) == 2) {
       g.tm = cdiv(g.M, 256); g.tn = cdiv(g.N, 256);
       // XCD-stationary order where all N-panels form ONE group (N <= 1024: proj / lin2 / patch embed): every A-panel is fetched
       // once (L2 read traffic 1.39 -> 1.17x / 1.16 -> 1.07x of the algorithmic bytes at equal time). Wider GEMMs keep the banded order:
@@ -988,7 +1020,6 @@ int launch_gemm(const void* A, long lda, const void* W, long ldw, void* C, long 
       return 0;
     }
   }
-  if (!k128 && cfg >= 9) cfg = 1;
   switch (cfg) {
     case 9: return launch_tile<TA, TO, 256, 128, 4, 2, true, 3>(g, s);
     case 2: return launch_tile<TA, TO, 128, 128, 2, 2, true>(g, s);
@@ -998,11 +1029,9 @@ int launch_gemm(const void* A, long lda, const void* W, long ldw, void* C, long 
   }
 }
 
-}  // namespace
-
-extern "C" int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab_dtype, void* C, long ldc, int c_dtype,
-                        int M, int N, int K, const float* bias, int act, const float* col_scale,
-                        const float* residual, long ldr, int res_row_mod, int cfg, void* stream) {
+// Argument checks shared by cor_gemm and cor_gemm_kernel_id; resolves COR_BF16X3 to bf16 operands over 3K.
+int gemm_check_args(const void* A, long lda, const void* W, long ldw, int& ab_dtype, const void* C, long ldc, int c_dtype, int M, int N, int& K,
+                    const float* residual, long ldr, int cfg) {
   if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N) return COR_EINVAL;
   {
     const int sel = cfg & 0xff;
@@ -1022,6 +1051,17 @@ extern "C" int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab
     ab_dtype = COR_BF16;
     K *= 3;
   }
+  if (!((ab_dtype == COR_F32 || ab_dtype == COR_BF16) && (c_dtype == COR_F32 || c_dtype == COR_BF16))) return COR_ENOSUPPORT;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab_dtype, void* C, long ldc, int c_dtype,
+                        int M, int N, int K, const float* bias, int act, const float* col_scale,
+                        const float* residual, long ldr, int res_row_mod, int cfg, void* stream) {
+  const int rc = gemm_check_args(A, lda, W, ldw, ab_dtype, C, ldc, c_dtype, M, N, K, residual, ldr, cfg);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (ab_dtype == COR_F32 && c_dtype == COR_F32)
     return launch_gemm<float, float>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);
@@ -1029,7 +1069,19 @@ extern "C" int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab
     return launch_gemm<bf16_t, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);
   if (ab_dtype == COR_BF16 && c_dtype == COR_F32)
     return launch_gemm<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);
-  if (ab_dtype == COR_F32 && c_dtype == COR_BF16)
-    return launch_gemm<float, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);
-  return COR_ENOSUPPORT;
+  return launch_gemm<float, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, bias, act, col_scale, residual, ldr, res_row_mod, cfg, s);
+}
+
+extern "C" int cor_gemm_kernel_id(const void* A, long lda, const void* W, long ldw, int ab_dtype, const void* C, long ldc, int c_dtype,
+                                  int M, int N, int K, const float* bias, int act, const float* col_scale,
+                                  const float* residual, long ldr, int res_row_mod, int cfg) {
+  (void)act; (void)res_row_mod;                      // no route depends on them
+  const int rc = gemm_check_args(A, lda, W, ldw, ab_dtype, C, ldc, c_dtype, M, N, K, residual, ldr, cfg);
+  if (rc) return rc;
+  GemmRoute r;
+  if (ab_dtype == COR_F32 && c_dtype == COR_F32) r = gemm_route<float, float>(A, lda, W, ldw, C, ldc, M, N, K, bias, col_scale, residual, ldr, cfg);
+  else if (ab_dtype == COR_BF16 && c_dtype == COR_BF16) r = gemm_route<bf16_t, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, bias, col_scale, residual, ldr, cfg);
+  else if (ab_dtype == COR_BF16 && c_dtype == COR_F32) r = gemm_route<bf16_t, float>(A, lda, W, ldw, C, ldc, M, N, K, bias, col_scale, residual, ldr, cfg);
+  else r = gemm_route<float, bf16_t>(A, lda, W, ldw, C, ldc, M, N, K, bias, col_scale, residual, ldr, cfg);
+  return r.kernel | (r.vec_epi ? COR_GEMM_EPILOGUE_VEC : 0);
 }

@@ -70,6 +70,19 @@ int cor_gemm(const void* A, long lda, const void* W, long ldw, int ab_dtype,
  * the timing probes of the development builds (result-destroying ablation bits, 16x16 MFMA form) are not in this library
  * (they build into tools/probes/libcor_probes.so with -DCOR_PROBES). */
 
+/* What cor_gemm would run for these arguments (cor_gemm's, without `stream`; pointer VALUES matter: alignment selects the scalar kernel
+ * and the scalar epilogue). Pure host function, no launch. Returns the kernel - 1, 2, 3, 4, 9 or 13 as in `cfg`, after every demotion
+ * (2 / 3 / 4 / 9 -> 1 on a ragged K tail, 13 -> 2 / 1 where the persistent kernel does not apply), or COR_GEMM_KERNEL_SCALAR for the
+ * scalar kernel of unaligned operands - OR-ed with COR_GEMM_EPILOGUE_VEC when the tile kernel takes its 16-byte vector epilogue
+ * (else the per-element one); or the COR_EINVAL / COR_ENOSUPPORT cor_gemm would return. */
+#define COR_GEMM_KERNEL_SCALAR 32
+#define COR_GEMM_KERNEL_MASK 0xff
+#define COR_GEMM_EPILOGUE_VEC (1 << 8)
+int cor_gemm_kernel_id(const void* A, long lda, const void* W, long ldw, int ab_dtype,
+                       const void* C, long ldc, int c_dtype, int M, int N, int K,
+                       const float* bias, int act, const float* col_scale,
+                       const float* residual, long ldr, int res_row_mod, int cfg);
+
 /* y[r,:] = LayerNorm(x[r,:]) * w + b over the last dim, biased variance.
  * ref: nn.LayerNorm (image_encoder.py:169,183), LayerNorm2d common.py:31-43 and mask_adapter.py:226-251 (on
  *      channels-last rows), transformer.py norm1..4. */
