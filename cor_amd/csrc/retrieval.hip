@@ -1861,13 +1861,13 @@ __device__ __forceinline__ float chain_score_c(const TG* __restrict__ G, long id
 // Five chain passes over the shard: slow, exact, rare (DESIGN 3.4 gives the measured cost).
 // FILTER: only the rows allowed for the query (label ql, COR_FILTER_NE if ne) are ranked: a disallowed row has key 0, below every score's
 // key, and a query with nA <= k allowed rows gets all of them followed by the (-inf, -1) tail.
-template <typename TG, bool FILTER = false>
-__device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float* sl_s, int* sl_i,
-                                 unsigned long long* keys, int* hist, float* out_s, long long* out_i, const int* rlab = nullptr, int ql = -1,
-                                 int ne = 0) {
+// The body takes the score of a row and the allow predicate as callables (brute_force_by): the chain over a float / 16-bit gallery here,
+// the integer score of the int8 route in sim_i8_repair.
+template <bool FILTER, typename ScoreAt, typename Allowed>
+__device__ __forceinline__ void brute_force_by(const ScoreAt score_at, const Allowed allowed, int Ng, int k, long long g_offset, float* sl_s,
+                                               int* sl_i, unsigned long long* keys, int* hist, float* out_s, long long* out_i) {
   __shared__ int sel_bin, k_rem, n_above, wcnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  auto allowed = [&](int g) { return !FILTER || ql < 0 || ((rlab[g] == ql) != (ne != 0)); };
   int nA = Ng;                                         // rows that may be ranked (block-uniform)
   if constexpr (FILTER) {
     __shared__ int n_allowed;
@@ -1880,7 +1880,7 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
     nA = n_allowed;
   }
   const int kk = min(k, nA);
-  auto key_at = [&](int g) { return allowed(g) ? f2key(chain_score_c<TG>(G, g, C, qs)) : 0u; };
+  auto key_at = [&](int g) { return allowed(g) ? f2key(score_at(g)) : 0u; };
   unsigned kth = 0u;                                   // nA <= k: every allowed row is above "key 0"
   int above = kk, need = 0;
   if (nA > k) { kth = block_kth_key(key_at, Ng, k, hist, &sel_bin, &k_rem); need = k_rem; above = k - need; }
@@ -1890,7 +1890,7 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
   for (int g0 = 0; g0 < Ng; g0 += 256) {
     const int g = g0 + tid;
     float s = -INFINITY; unsigned key = 0u;
-    if (g < Ng && allowed(g)) { s = chain_score_c<TG>(G, g, C, qs); key = f2key(s); }
+    if (g < Ng && allowed(g)) { s = score_at(g); key = f2key(s); }
     const bool up = g < Ng && key > kth, tie = g < Ng && key == kth && nA > k;
     if (up) { const int p = atomicAdd(&n_above, 1); sl_s[p] = s; sl_i[p] = g; }
     const unsigned long long b = __builtin_amdgcn_ballot_w64(tie);
@@ -1914,6 +1914,14 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
     out_s[j] = j < kk ? rank_key_score(keys[j]) : -INFINITY;
     out_i[j] = j < kk ? (long long)(unsigned)keys[j] + g_offset : -1LL;
   }
+}
+template <typename TG, bool FILTER = false>
+__device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float* sl_s, int* sl_i,
+                                 unsigned long long* keys, int* hist, float* out_s, long long* out_i, const int* rlab = nullptr, int ql = -1,
+                                 int ne = 0) {
+  brute_force_by<FILTER>([&](int g) { return chain_score_c<TG>(G, g, C, qs); },
+                         [&](int g) { return !FILTER || ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
+                         out_s, out_i);
 }
 
 // The tile loop of sim_topk_partial (fp32 galleries: the chain on the f32 MFMA; 16-bit: the 16-bit MFMA; any C <= 256, C % 16 == 0)
@@ -2527,14 +2535,16 @@ struct WidePlan {
   size_t off_sgrow;                  // group: the rows of the sample values
 };
 // group = the distinct-group route (any k): the sample keeps NV = 1 (filter: 4) values WITH rows per group, and the capacity plan below.
-inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false) {
+// i8 = the int8 route (cor_similarity_topk_i8; scan must be set): the scan form's 64-row tiles and lane-quarter streams, query groups of
+// 512 (sim_i8_scan: 8 waves x 64 queries), and entry lists as the tile form keeps them.
+inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false) {
   WidePlan p{};
   p.scan = scan;
   const int rows = scan ? 64 : 32;                     // rows per tile of the scan kernel
   p.ntiles = cdiv(Ng, rows);
   int want;
   if (scan) {
-    p.qb = Bq > 256 ? 2 : 1;
+    p.qb = i8 || Bq > 256 ? 2 : 1;
     p.nqg = cdiv(Bq, 256 * p.qb);
     want = device_cus() / p.nqg;                       // one resident block per CU
     if (want > 256) want = 256;
@@ -2549,7 +2559,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
   const int per_tile = scan ? 4 : 2;                   // streams per slice: lane quarters (scan) / lane halves (tiles)
   p.nstreams = per_tile * p.nsplit;
-  const int stream_max = scan ? 2 * p.tiles_per_split : 16 * p.tiles_per_split;     // records / entries a stream can hold at most
+  const int stream_max = scan && !i8 ? 2 * p.tiles_per_split : 16 * p.tiles_per_split;   // records / entries a stream can hold at most
   if (Ng <= 4096) {                                    // tiny shard: no sample pass, every row is a candidate (<= FSW)
     p.s_stride = 1;
     p.cap = stream_max;
@@ -2589,10 +2599,10 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
     p.cap = (int)(2 * expect / p.nstreams) + 10;
     if (p.cap > stream_max) p.cap = stream_max;
   }
-  const int Bqp = scan ? p.nqg * 256 * p.qb : 0;
+  const int Bqp = scan && !i8 ? p.nqg * 256 * p.qb : 0;
   size_t o = 0;
   auto take = [&](size_t n) { const size_t at = o; o += (n + 255) & ~(size_t)255; return at; };
-  p.off_img = take(scan ? (size_t)p.nqg * 8 * p.qb * 16 * 64 * 16 : 0);
+  p.off_img = take(i8 ? (size_t)Bq * 256 : scan ? (size_t)p.nqg * 8 * p.qb * 16 * 64 * 16 : 0);   // (i8: the quantised queries, scales in off_dq)
   const size_t sg_n = (size_t)Bq * p.ngroups > (size_t)32 * Bqp ? (size_t)Bq * p.ngroups : (size_t)32 * Bqp;   // (sim_prep clears 32 x Bqp)
   p.off_sg = take(sg_n * 4 + 4);
   p.off_dq = take((size_t)Bq * 4);
@@ -2600,8 +2610,8 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   p.off_flags = take(16);
   p.off_ovf = take((size_t)Bq * 4);
   p.off_cnt = take((size_t)Bq * p.nstreams * 4);
-  p.off_recs = take((size_t)Bq * p.nstreams * p.cap * (scan ? 32 : 8));   // a record = 8 scores; an entry = (score, row)
-  p.off_recg = take(scan ? (size_t)Bq * p.nstreams * p.cap * 4 : 0);
+  p.off_recs = take((size_t)Bq * p.nstreams * p.cap * (scan && !i8 ? 32 : 8));   // a record = 8 scores; an entry = (score, row)
+  p.off_recg = take(scan && !i8 ? (size_t)Bq * p.nstreams * p.cap * 4 : 0);
   p.off_sgrow = take(group ? (size_t)Bq * p.ngroups * 4 + 4 : 0);
   p.bytes = o;
   return p;
@@ -2613,6 +2623,7 @@ struct WideCall {
   const float* Q; int Bq, Ng, C, k; long long g_offset;
   const int* grp; const int* rlab; const int* qlab; int ne;
   float* out_s; long long* out_i; char* w; int flags; hipStream_t s;
+  const float* gscale;                               // the int8 route: the gallery rows' scales
 };
 
 // tau_q from the sample values. GROUP: reduced to one value per group first (sim_tau_distinct, with the rows behind the values).
@@ -2743,6 +2754,226 @@ int launch_topk(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long 
   return launch_merge(ws_s, ws_i, Bq, p.nparts * p.kmax, k, g_offset, out_s, out_i, nullptr, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// INT8 GALLERIES (cor_similarity_topk_i8): rows quantised per row by cor_quantize_rows_i8 (Gq int8 [Ng,C], gscale f32 [Ng]), the query
+// quantised the same way inside the call. score = ((float)d * qscale) * gscale with d the int32 dot product: integer arithmetic, exact in
+// any summation order, so the scan's score IS the score: delta = 0, nothing is re-scored (include/cor_amd.h has the definition). Every k
+// takes the wide route's steps with the fp32 gallery's selection: sim_i8_scan<SAMPLE>, sim_tau_wide<float>, sim_i8_scan<APPEND>,
+// sim_final_wide<float> on the entry lists, and for an overflowed query sim_i8_repair (brute_force_by over the int8 scores).
+//
+// sim_i8_scan: v_mfma_i32_16x16x64_i8, gallery rows as the A operand, queries as B. A block is 8 waves; wave w keeps the fragments of ITS 64
+// queries (4 column blocks x C/64 K steps x 16 B per lane = 64 VGPRs at C = 256) for the whole slice, and all 8 waves share every 64-row
+// gallery tile through LDS: 512 queries read the gallery from memory once. Lane (c = lane & 15, rq = lane >> 4) supplies bytes
+// [64 ks + 16 rq, +16) of gallery row / query c to K step ks; the K order inside the instruction does not matter as long as both operands
+// use the same one, and the C/D map is the dtype-independent one: lane holds column c (the query), rows 4 rq + reg (the gallery rows).
+// So lane quarter rq of slice `split` is the private stream split * 4 + rq of each of the lane's four queries: no atomics.
+// Tiles are double-buffered in LDS (global -> registers during the previous tile's MFMAs -> LDS, one barrier per tile), the 64 row scales
+// with them: the tile loop issues no global load but the prefetch, so nothing waits behind it on the in-order load counter. LDS image of a
+// tile: row r at r * stride 16-B slots, chunk ch at slot ch ^ (r & 15) for C = 256 (stride 16: the four 16-lane groups of a ds_read_b128
+// see 16 different slots) and at slot ch with an odd stride (C / 16) | 1 otherwise (consecutive rows start one slot apart).
+// Edges: rows >= Ng score -inf (their bytes are read as zero, never from beyond the gallery), padding queries (q >= Bq) carry tau = +inf
+// and never append, chunks beyond C (C % 64 != 0) are zero in both fragments.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+struct I8ScanArgs {
+  const signed char* qq; const float* qscale; const float* gscale;
+  int Bq, Ng, C, nqg, nsplit, tiles_per_split, ntiles, tile_stride;
+  unsigned* sg; int ngroups;
+  const float* tau; int* cnt; uint2* lst; int cap;
+};
+constexpr int I8_TILE_SLOTS = 64 * 17;                 // 64 rows x the largest stride
+// FULL: C = 256, every chunk and K step present (no tail tests in the loop). APPEND tests a cheap upper bound first: rounding is monotone and
+// qscale, gscale >= 0, so ((float)max(d_0..d_3, 0) * qscale) * max(gscale_0..3) is >= each of the lane's four scores of a query; only
+// where some lane's bound reaches tau_q are the four scores formed and compared (a few rows in 10^4 pass tau_q).
+template <bool SAMPLE, bool FULL>
+__global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict__ G, const I8ScanArgs a) {
+#pragma clang fp contract(off)
+  __shared__ uint4 tile[2][I8_TILE_SLOTS];
+  __shared__ f32x4 tile_gs[2][16];                     // the tile's 64 row scales (0 beyond Ng), fetched with it
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, rq = lane >> 4;
+  const int qg = blockIdx.x % a.nqg, split = blockIdx.x / a.nqg;
+  const int Ng = a.Ng, C = FULL ? 256 : a.C, nch = C >> 4, nks = (C + 63) >> 6;
+  const int stride = nch == 16 ? 16 : (nch | 1), xmask = nch == 16 ? 15 : 0;
+  const int q0 = (qg * 8 + wave) * 64;
+  const bool active = q0 < a.Bq;                       // wave-uniform: a wave without queries only helps to load
+  // the lane's four queries (column block j: q0 + 16 j + c16) and their fragments
+  i32x4 qf[4][4];
+  float qs[4], tq[4], gmax[4];
+  int n[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int q = q0 + 16 * j + c16;
+    const signed char* qrow = a.qq + (long)min(q, a.Bq - 1) * C;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      qf[j][ks] = i32x4{0, 0, 0, 0};
+      if (active && (FULL || ks * 4 + rq < nch)) qf[j][ks] = *(const i32x4*)(qrow + ks * 64 + rq * 16);
+    }
+    qs[j] = active ? a.qscale[min(q, a.Bq - 1)] : 0.f;
+    // padding lanes (q >= Bq) never append; the floor keeps masked -inf scores out of the lists when tau_q is -inf
+    tq[j] = SAMPLE ? 0.f : (active && q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
+    gmax[j] = -INFINITY;
+    n[j] = 0;
+  }
+  const int stream = split * 4 + rq, nstreams = 4 * a.nsplit;
+  // the thread's two 16-B pieces of a tile: piece i = tid + 512 p is chunk i % nch of row i / nch (a tile is contiguous in the gallery)
+  const long gbytes = (long)Ng * C;
+  int slot[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int i = tid + 512 * p, r = i / nch, ch = i - r * nch;
+    slot[p] = r < 64 ? r * stride + (ch ^ (r & xmask)) : -1;
+  }
+  const int t0 = split * a.tiles_per_split, t1 = min(t0 + a.tiles_per_split, a.ntiles);
+  uint4 pre[2];
+  f32x4 pre_gs = {0.f, 0.f, 0.f, 0.f};
+  auto fetch = [&](int t) {
+    const long base = (long)t * a.tile_stride * 64 * C;
+    if (tid < 16) {
+      const int gr = t * a.tile_stride * 64 + 4 * tid;
+      if (gr + 4 <= Ng) pre_gs = *(const f32x4*)(a.gscale + gr);
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pre_gs[e] = gr + e < Ng ? a.gscale[gr + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const long off = base + 16L * (tid + 512 * p);
+      pre[p] = make_uint4(0u, 0u, 0u, 0u);
+      if (slot[p] >= 0 && off < gbytes) pre[p] = *(const uint4*)(G + off);
+    }
+  };
+  if (t0 < t1) fetch(t0);
+  for (int t = t0; t < t1; ++t) {
+    uint4* buf = tile[(t - t0) & 1];
+    const f32x4* buf_gs = tile_gs[(t - t0) & 1];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+      if (slot[p] >= 0) buf[slot[p]] = pre[p];
+    if (tid < 16) tile_gs[(t - t0) & 1][tid] = pre_gs;
+    __syncthreads();                                   // the other buffer was last read before this barrier: the next stores are safe
+    if (t + 1 < t1) fetch(t + 1);
+    if (!active) continue;
+    const int g0 = t * a.tile_stride * 64;
+#pragma unroll
+    for (int sub = 0; sub < 4; ++sub) {
+      const int gr = g0 + 16 * sub + 4 * rq;           // the lane's rows gr .. gr + 3 of this 16-row block
+      if (g0 + 16 * sub >= Ng) break;                  // block-uniform
+      const f32x4 gs = buf_gs[4 * sub + rq];
+      const int r = 16 * sub + c16;
+      i32x4 af[4];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        af[ks] = i32x4{0, 0, 0, 0};
+        if (FULL || ks * 4 + rq < nch) af[ks] = __builtin_bit_cast(i32x4, buf[r * stride + ((ks * 4 + rq) ^ (r & xmask))]);
+      }
+      i32x4 acc[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0], qf[j][0], (i32x4{0, 0, 0, 0}), 0, 0, 0);
+#pragma unroll
+        for (int ks = 1; ks < 4; ++ks)
+          if (FULL || ks < nks) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[ks], qf[j][ks], acc[j], 0, 0, 0);
+      }
+      const float gsmax = fmaxf(fmaxf(gs[0], gs[1]), fmaxf(gs[2], gs[3]));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (SAMPLE) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float s = ((float)acc[j][e] * qs[j]) * gs[e];
+            gmax[j] = fmaxf(gmax[j], gr + e < Ng ? s : -INFINITY);
+          }
+        } else {
+          const int dmax = max(max(max(acc[j][0], acc[j][1]), max(acc[j][2], acc[j][3])), 0);
+          const float bound = ((float)dmax * qs[j]) * gsmax;
+          if (__builtin_amdgcn_ballot_w64(bound >= tq[j]) != 0) {
+            uint2* dst = a.lst + ((long)min(q0 + 16 * j + c16, a.Bq - 1) * nstreams + stream) * a.cap;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float s = ((float)acc[j][e] * qs[j]) * gs[e];
+              if (gr + e < Ng && s >= tq[j]) {
+                if (n[j] < a.cap) dst[n[j]] = make_uint2(__float_as_uint(s), (unsigned)(gr + e));
+                ++n[j];
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  if (!active) return;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int q = q0 + 16 * j + c16;
+    if (q < a.Bq) {
+      if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax[j]);
+      else a.cnt[(long)q * nstreams + stream] = n[j];
+    }
+  }
+}
+
+// Overflowed queries of the int8 route (sim_final_wide ran with the marker on: slot 0 is (-inf, -2), which no ranked query carries):
+// the exact top-k by brute force over the int8 scores, one block of 256 threads per query; every other block leaves at once.
+__global__ void __launch_bounds__(256) sim_i8_repair(const signed char* __restrict__ qq, const float* __restrict__ qscale,
+                                                     const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C, int k,
+                                                     long long g_offset, float* out_s, long long* out_i) {
+#pragma clang fp contract(off)
+  __shared__ float sl_s[COR_TOPK_KMAX];
+  __shared__ int sl_i[COR_TOPK_KMAX], hist[256];
+  __shared__ unsigned long long keys[COR_TOPK_KMAX];
+  __shared__ uint4 qv[16];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (out_i[(long)q * k] != -2LL) return;              // block-uniform: read before any thread of the block writes
+  if (tid < C / 16) qv[tid] = *(const uint4*)(qq + (long)q * C + 16 * tid);
+  __syncthreads();
+  const float qs = qscale[q];
+  auto score_at = [&](int g) {
+    const uint4* row = (const uint4*)(G + (long)g * C);
+    int d = 0;
+    for (int c = 0; c < C / 16; ++c) {
+      const uint4 x = row[c], y = qv[c];
+      const unsigned xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) d += (int)(signed char)(xw[i] >> (8 * b)) * (int)(signed char)(yw[i] >> (8 * b));
+    }
+    return ((float)d * qs) * gscale[g];
+  };
+  brute_force_by<false>(score_at, [](int) { return true; }, Ng, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
+}
+
+int launch_topk_i8(const signed char* Gq, const WideCall& c) {
+  const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, false, false, true);
+  signed char* qq = (signed char*)(c.w + p.off_img); float* qscale = (float*)(c.w + p.off_dq);
+  if (const int e = cor_quantize_rows_i8(c.Q, COR_F32, c.Bq, c.C, qq, qscale, c.s)) return e;
+  I8ScanArgs a{};
+  a.qq = qq; a.qscale = qscale; a.gscale = c.gscale; a.Bq = c.Bq; a.Ng = c.Ng; a.C = c.C; a.nqg = p.nqg;
+  a.sg = (unsigned*)(c.w + p.off_sg); a.ngroups = p.ngroups;
+  if (p.ngroups > 0) {
+    a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
+    if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<true, true>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    else hipLaunchKernelGGL((sim_i8_scan<true, false>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    COR_CHECK_LAUNCH();
+  }
+  if (const int e = launch_wide_tau<float, false>(c, p)) return e;
+  a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
+  a.tau = (const float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.lst = (uint2*)(c.w + p.off_recs); a.cap = p.cap;
+  if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<false, true>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
+  else hipLaunchKernelGGL((sim_i8_scan<false, false>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
+  COR_CHECK_LAUNCH();
+  // the fp32 gallery's selection over the entry lists; an overflow leaves the marker and never touches the (absent) float rows
+  WideCall sel = c;
+  sel.flags |= COR_TOPK_NO_FALLBACK;
+  if (const int e = launch_wide_final<float, false, false, false>((const float*)nullptr, sel, p)) return e;
+  if (!(c.flags & COR_TOPK_NO_FALLBACK)) {
+    hipLaunchKernelGGL(sim_i8_repair, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.out_s, c.out_i);
+    COR_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 // the largest value of a plan field over the two forms of a route (the gallery's dtype and C choose the form at call time)
 template <typename T>
 long wide_max(int Bq, int Ng, int k, bool filter, bool group, T WidePlan::*field) {
@@ -2757,21 +2988,23 @@ inline int distinct_sample_values(int Bq, int Ng, int k) {
 inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
 
 constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
-enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT };
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8 };
 
 // The argument checks of the three search entry points, in the order (and with the codes) of the ABI. What differs by route: the
 // pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither), the A/B flags it refuses
 // (the plain call only at k > 32) and the distinct route's sample bound.
 int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
   const bool own_ptrs = route == ROUTE_TOPK       ? true
+                        : route == ROUTE_I8       ? c.gscale != nullptr
                         : route == ROUTE_FILTERED ? c.rlab && c.qlab
                                                   : c.grp && (c.rlab == nullptr) == (c.qlab == nullptr);
   if (!c.Q || !G || !own_ptrs || !c.out_s || !c.out_i || !c.w || c.Bq <= 0 || c.Ng <= 0 || c.k <= 0) return COR_EINVAL;
   if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
   if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
   if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
+  if (route == ROUTE_I8 && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
   if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
-  if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
+  if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab | (uintptr_t)c.gscale) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
   return 0;
 }
 
@@ -2838,4 +3071,16 @@ extern "C" int cor_similarity_topk_distinct(const float* Q, const void* G, int g
                    out_idx, (char*)workspace, flags, (hipStream_t)stream};
   if (const int e = check_topk_call(ROUTE_DISTINCT, c, G, filter_mode)) return e;
   return by_dtype(g_dtype, G, [&](auto* g) { return filter ? launch_wide<true, true>(g, c) : launch_wide<false, true>(g, c); });
+}
+
+extern "C" long cor_topk_i8_workspace_bytes(int Bq, int Ng, int k) {
+  return topk_shape_ok(Bq, Ng, k) ? (long)make_wide(Bq, Ng, k, true, false, false, true).bytes : COR_EINVAL;
+}
+
+// int8 calls take one route for every k (launch_topk_i8)
+extern "C" int cor_similarity_topk_i8(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k, long long g_offset,
+                                      float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream, gscale};
+  if (const int e = check_topk_call(ROUTE_I8, c, Gq, COR_FILTER_EQ)) return e;
+  return launch_topk_i8(Gq, c);
 }

@@ -543,6 +543,48 @@ def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=
     return scores, idx
 
 
+def quantize_rows_i8(X):
+    """Per-row scalar quantisation: X [n,C] fp32 / bf16 / fp16 (finite values) -> (q int8 [n,C], scale f32 [n]) on the GPU, X untouched.
+    Per row amax = max|x| in fp32; amax == 0: scale 0 and q 0; else q = clamp(rint(x * (127 / amax)), -127, 127) (half to even) and
+    scale = amax / 127, every step one rounded fp32 operation (include/cor_amd.h). C % 16 == 0, C <= 256."""
+    if X.dim() != 2 or X.dtype not in _DT:
+        raise ValueError(f"quantize_rows_i8: X must be [n, C] in float32 / bfloat16 / float16, got {X.dtype} {tuple(X.shape)}")
+    n, C = X.shape
+    if C < 16 or C > 256 or C % 16:
+        raise ValueError(f"quantize_rows_i8: C must be a multiple of 16 up to 256, got {C}")
+    _dev(X)
+    X = X.contiguous()
+    if X.data_ptr() % 16:                                     # a view into a larger tensor: the kernel loads 16 B at a time
+        X = X.clone()
+    q = torch.empty((n, C), dtype=torch.int8, device=X.device)
+    scale = torch.empty((n,), dtype=torch.float32, device=X.device)
+    nat.check(_lib().cor_quantize_rows_i8(X.data_ptr(), _dt(X), n, C, q.data_ptr(), scale.data_ptr(), _s()), "cor_quantize_rows_i8")
+    return q, scale
+
+
+def similarity_topk_i8(Q, Gq, gscale, k, g_offset=0, flags=0):
+    """similarity_topk over an int8 gallery: Q fp32 [Bq,C]; Gq int8 [Ng,C] and gscale f32 [Ng] as quantize_rows_i8 returns them. The query
+    is quantised the same way inside the call; score = ((float)(int32 dot) * qscale) * gscale, exact in any summation order, ranked by
+    (score key desc, index asc): bit-identical to tests/i8_refs.py, scores and indices. 1 <= k <= 256, C % 16 == 0, C <= 256; Ng < k:
+    the tail is (-inf, -1). One route for every k; a candidate overflow is repaired on the device. flags: 0 or nat.TOPK_NO_FALLBACK."""
+    who = "similarity_topk_i8"
+    if Gq.dtype != torch.int8:
+        raise ValueError(f"{who}: Gq must be int8 rows (ops.quantize_rows_i8), got {Gq.dtype}")
+    if gscale.dtype != torch.float32 or gscale.dim() != 1 or Gq.dim() != 2 or gscale.shape[0] != Gq.shape[0]:
+        raise ValueError(f"{who}: gscale must be float32 [Ng] for Gq [Ng, C], got {gscale.dtype} {tuple(gscale.shape)} for {tuple(Gq.shape)}")
+    if int(flags) & ~nat.TOPK_NO_FALLBACK:
+        raise ValueError(f"{who}: flags must be 0 or TOPK_NO_FALLBACK, got {flags}")
+    Bq, Ng, C = _topk_front(who, Q, Gq, k)
+    _dev(Q, gscale)
+    gscale = gscale.contiguous()
+    if gscale.data_ptr() % 16:                                # a view into a larger tensor: the scan loads four scales at a time
+        gscale = gscale.clone()
+    ws, scores, idx = _topk_buffers("cor_topk_i8_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk_i8(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, k, int(g_offset), scores.data_ptr(),
+                                            idx.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_topk_i8")
+    return scores, idx
+
+
 def _list_front(who, scores, idx):
     """The checks of a (scores f32, idx i64) [Bq,kin] list as a search, the merge or the re-scoring return it. Returns (Bq, kin)."""
     if scores.dim() != 2 or scores.shape[1] < 1 or scores.dtype != torch.float32:

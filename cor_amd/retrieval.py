@@ -299,13 +299,15 @@ class GalleryShard:
         """Database-side augmentation: a NEW GalleryShard (same offset, labels and groups; rows in `dtype`, default this shard's) whose
         every row is the expansion, with query_weight = 0, of the row's own top-m list over `neighbours` (a GalleryShard or GallerySet;
         default: this shard, where a unit-norm row finds itself with score 1), normalised. `batch` rows are searched and expanded at a
-        time. This shard is left untouched."""
+        time. This shard is left untouched. `neighbours` that only search (a QuantizedShard over this shard's id space, e.g.
+        self.quantized()) find the lists, which are then expanded over THIS shard's rows."""
         _check_expansion("GalleryShard.augmented", m=m, batch=batch)
         nb = self if neighbours is None else neighbours
+        rows_of = nb if hasattr(nb, "expand") else self
         out = torch.empty(self.rows.shape, dtype=dtype or self.rows.dtype, device=self.rows.device)
         for lo in range(0, len(self), int(batch)):
             s, i = nb.search(self.rows[lo:lo + int(batch)], int(m))
-            nb.expand(None, s, i, int(m), alpha=alpha, query_weight=0.0, out_dtype=out.dtype, out=out[lo:lo + int(batch)])
+            rows_of.expand(None, s, i, int(m), alpha=alpha, query_weight=0.0, out_dtype=out.dtype, out=out[lo:lo + int(batch)])
         return GalleryShard(out, offset=self.offset, labels=self.labels, groups=self.groups)
 
     def neighbour_graph(self, k1: int, batch: int = 4096, neighbours=None):
@@ -325,6 +327,58 @@ class GalleryShard:
         neighbours). k1 defaults to the graph's width, k to min(kin, 256). Entries this shard does not hold are dropped. ValueError if the
         graph was built from other segments."""
         return _rerank("GalleryShard.rerank", [self] if len(self) else [], scores, idx, graph, k1, lam, k)
+
+    def quantized(self):
+        """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
+        coarse stage of two_stage_search over these rows. This shard is left untouched; labels and groups are not carried (filtered and
+        distinct int8 searches do not exist)."""
+        return QuantizedShard.from_rows(self.rows, offset=self.offset)
+
+
+class QuantizedShard:
+    """Rows [offset, offset + n) of a gallery as int8 with one fp32 scale per row (ops.quantize_rows_i8), scanned on the i8 matrix cores
+    (ops.similarity_topk_i8): half the bytes of a 16-bit copy and scores that are defined to the bit. It only SEARCHES: no rescore,
+    expand or rerank, which need real rows. Use it wherever a coarse search is taken: `coarse` of two_stage_search, `neighbours` of
+    GalleryShard.augmented / neighbour_graph (search only; `augmented` also expands over its neighbours and needs real rows there),
+    the `shard` of distributed_search."""
+
+    def __init__(self, rows_i8: torch.Tensor, scales: torch.Tensor, offset: int = 0):
+        if not rows_i8.is_cuda or not scales.is_cuda:
+            raise RuntimeError("QuantizedShard lives in GPU memory (no CPU path)")
+        if rows_i8.dtype != torch.int8 or rows_i8.dim() != 2:
+            raise ValueError(f"QuantizedShard: rows must be int8 [n, C], got {rows_i8.dtype} {tuple(rows_i8.shape)}")
+        if scales.dtype != torch.float32 or scales.dim() != 1 or scales.shape[0] != rows_i8.shape[0]:
+            raise ValueError(f"QuantizedShard: scales must be float32 [{rows_i8.shape[0]}], got {scales.dtype} {tuple(scales.shape)}")
+        self.rows = rows_i8.contiguous()
+        self.scales = scales.to(self.rows.device).contiguous()
+        self.offset = int(offset)
+        self.labels = None
+        self.groups = None
+
+    @classmethod
+    def from_rows(cls, rows: torch.Tensor, offset: int = 0):
+        """Quantise fp32 / bf16 / fp16 rows [n, C] on their device; `rows` is left untouched."""
+        if not rows.is_cuda:
+            raise RuntimeError("QuantizedShard lives in GPU memory (no CPU path)")
+        if rows.shape[0] == 0:
+            return cls(torch.empty(rows.shape, dtype=torch.int8, device=rows.device), torch.empty((0,), dtype=torch.float32, device=rows.device), offset)
+        with torch.cuda.device(rows.device):
+            q, scale = ops.quantize_rows_i8(rows)
+        return cls(q, scale, offset)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq", distinct: bool = False):
+        """queries f32[Bq,C] -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU, the int8 scores of ops.similarity_topk_i8;
+        1 <= k <= 256. Filtered and distinct int8 searches do not exist: query_labels or distinct raise ValueError."""
+        if query_labels is not None or distinct:
+            raise ValueError("QuantizedShard.search: an int8 shard has no filtered or distinct search")
+        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        if self.rows.shape[0] == 0:                  # an empty shard: all-missing lists, like Ng < k
+            return _missing_lists(q.shape[0], k, q.device)
+        with torch.cuda.device(self.rows.device):
+            return ops.similarity_topk_i8(q, self.rows, self.scales, k, g_offset=self.offset)
 
 
 class GallerySet:
@@ -853,12 +907,20 @@ def build_gallery_regions(model, batches, dtype=torch.float16):
     return rows, groups
 
 
-def save_gallery(path, rows, world=1, labels=None, groups=None):
+def save_gallery(path, rows, world=1, labels=None, groups=None, scales=None):
     """On-disk format: <path>.shardNN.pt (rows of shard NN as a tensor) + <path>.manifest.json (row ranges). labels (int32[n], one
     per row): also <path>.shardNN.labels.pt per shard and "labels": true in the manifest; groups (int32[n], one group id per row):
-    <path>.shardNN.groups.pt and "groups": true likewise."""
+    <path>.shardNN.groups.pt and "groups": true likewise. scales (float32[n], with int8 rows: a quantised gallery, QuantizedShard.rows /
+    .scales): <path>.shardNN.scales.pt and "scales": true, and load_gallery_shard returns a QuantizedShard. Without scales the files and
+    the manifest are as they always were."""
     import json
     n = rows.shape[0]
+    if scales is not None:
+        if rows.dtype != torch.int8:
+            raise ValueError(f"save_gallery: scales go with int8 rows, got {rows.dtype}")
+        scales = torch.as_tensor(scales).reshape(-1).to(torch.float32).cpu()
+        if scales.shape[0] != n:
+            raise ValueError(f"save_gallery: {scales.shape[0]} scales for {n} rows")
     ids = {}                                                     # "labels" / "groups" -> int32[n] on the host, those that were given
     for name, what, t in (("labels", "labels", labels), ("groups", "group ids", groups)):
         if t is not None:
@@ -873,9 +935,14 @@ def save_gallery(path, rows, world=1, labels=None, groups=None):
         for name, t in ids.items():
             torch.save(t[lo:hi].clone(), f"{path}.shard{r:02d}.{name}.pt")
             shards[-1][f"{name}_file"] = f"{path}.shard{r:02d}.{name}.pt"
+        if scales is not None:
+            torch.save(scales[lo:hi].clone(), f"{path}.shard{r:02d}.scales.pt")
+            shards[-1]["scales_file"] = f"{path}.shard{r:02d}.scales.pt"
+    man = dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels="labels" in ids, groups="groups" in ids, shards=shards)
+    if scales is not None:
+        man["scales"] = True
     with open(f"{path}.manifest.json", "w") as f:
-        json.dump(dict(rows=n, dim=int(rows.shape[1]), dtype=str(rows.dtype), world=world, labels="labels" in ids,
-                       groups="groups" in ids, shards=shards), f, indent=1)
+        json.dump(man, f, indent=1)
 
 
 def load_gallery_shard(path, rank, device):
@@ -884,4 +951,6 @@ def load_gallery_shard(path, rank, device):
     sh = man["shards"][rank]
     labels = torch.load(sh["labels_file"]) if man.get("labels") else None
     groups = torch.load(sh["groups_file"]) if man.get("groups") else None
+    if man.get("scales"):
+        return QuantizedShard(torch.load(sh["file"]).to(device), torch.load(sh["scales_file"]).to(device), offset=sh["lo"])
     return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"], labels=labels, groups=groups)

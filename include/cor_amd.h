@@ -375,6 +375,36 @@ int cor_similarity_topk_distinct(const float* Q, const void* G, int g_dtype, int
                                  const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
                                  long long* out_idx, void* workspace, int flags, void* stream);
 
+/* Int8 galleries (a scalar-quantised index, "SQ8"): rows quantised per row to int8 with one fp32 scale, scanned on the i8 matrix cores.
+ * ROW QUANTISATION (cor_quantize_rows_i8): X [n,C] in x_dtype (COR_F32 / COR_BF16 / COR_F16; 16-bit values widened exactly), finite
+ * values -> q int8 [n,C], scale f32 [n]. Per row: amax = max_c |x_c| in fp32. amax == 0: scale = 0 and every q_c = 0. Otherwise
+ *     inv = 127.0f / amax;   q_c = clamp((int)rintf(x_c * inv), -127, 127);   scale = amax / 127.0f
+ * with every operation a separately rounded fp32 operation (no contraction, plain division, no fast-math) and rintf rounding half to
+ * even. C % 16 == 0 and C <= 256, an x_dtype above: else COR_ENOSUPPORT; null pointers, n < 0, C <= 0, X or q not 16-byte aligned:
+ * COR_EINVAL; n == 0 is a successful no-op. One launch, memory-bound (16 lanes per row, 16-byte loads and stores).
+ * SCORE of query b against row g (cor_similarity_topk_i8): qq, qscale = the same quantisation of the fp32 query, made inside the call;
+ *     d = sum_c qq[b,c] * Gq[g,c] in int32;   score = ((float)d * qscale[b]) * gscale[g]
+ * two separately rounded fp32 multiplies. |d| <= 127^2 * C < 2^24 for C <= 256: (float)d is exact, d is exact in any summation order, so
+ * the score has no error bound to carry: what the scan computes is the score.
+ * ORDER: by the order-preserving key of the score's bits descending (so +0.0 ranks above -0.0, which a zero scale can produce), then by
+ * row index ascending; out_scores f32 [Bq,k], out_idx i64 [Bq,k] = row + g_offset; Ng < k: the tail is (-inf, -1). The result is
+ * bit-identical to that definition evaluated on the CPU (tests/i8_refs.py), scores and indices.
+ * Q f32 [Bq,C], Gq int8 [Ng,C] and gscale f32 [Ng] 16-byte aligned, 1 <= k <= COR_TOPK_KMAX, C % 16 == 0, C <= 256, workspace (256-byte
+ * aligned) >= cor_topk_i8_workspace_bytes(Bq, Ng, k). Checks in the order and with the codes of cor_similarity_topk: null pointers or
+ * Bq / Ng / k <= 0: COR_EINVAL; k or C unsupported: COR_ENOSUPPORT; a flag other than COR_TOPK_NO_FALLBACK: COR_ENOSUPPORT; misaligned
+ * pointers: COR_EINVAL. No allocation, no host synchronisation: the call can be captured in a graph.
+ * Route, the same for every k: the wide route's steps with the fp32 gallery's selection (delta = 0, nothing re-scored). The queries are
+ * quantised into the workspace; a strided sample scan keeps group maxima; tau_q is their k-th largest; the full scan appends the
+ * (score, row) entries >= tau_q to private per-stream lists (no atomics); one block per query finds the exact k-th key, takes the rows at
+ * or above it and sorts them. An overflowed query (e.g. thousands of identical rows) is ranked on the device by a brute force over the int8
+ * scores of the whole shard (exact, slow, rare); with COR_TOPK_NO_FALLBACK it carries index -2 in every slot instead.
+ * The scan (v_mfma_i32_16x16x64_i8): a block of 8 waves shares every 64-row gallery tile through LDS and each wave keeps the fragments of
+ * its own 64 queries in registers, so up to 512 queries read the gallery from memory once. */
+int cor_quantize_rows_i8(const void* X, int x_dtype, int n, int C, signed char* q, float* scale, void* stream);
+long cor_topk_i8_workspace_bytes(int Bq, int Ng, int k);
+int cor_similarity_topk_i8(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k, long long g_offset,
+                           float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
+
 /* Merge of top-k lists on the device: per query b, P lists of kin entries (what P calls of cor_similarity_topk[_filtered|_distinct] over P
  * shards return, stacked) -> the k best entries of their union. scores f32 [P,Bq,kin], idx i64 [P,Bq,kin] (global row ids), groups NULL or
  * i32 [P,Bq,kin] (one group id per entry), all contiguous; out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_groups NULL or i32 [Bq,k].

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Int8 gallery search (ops.similarity_topk_i8) beside the bf16 call it is meant to undercut, on one box in one process. GPU only.
+Per shape (C = 256): the int8 call and the bf16 ops.similarity_topk call alternate over --reps windows of back-to-back calls after --warmup
+windows (device events around each window; medians and min / max reported), then two_stage_search over fp32 master rows with the int8 and
+with the bf16 coarse stage alternate the same way (k_coarse = max(k, 100), final k = 10). The quantisation of the 1M-row gallery is timed
+once. The mean shader clock over each measurement is reported. One JSON line per measurement, printed and appended to --out (default
+profiles/topk_i8_bench.jsonl).
+    python tools/topk_i8_bench.py [--reps 7] [--warmup 2] [--out FILE]
+    python tools/topk_i8_bench.py --one 512x1000000 10        # the int8 call alone, 20 calls (for a rocprofv3 --kernel-trace --stats run)"""
+import argparse, json, os, statistics, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from cor_amd import ops, _native as nat
+from cor_amd.retrieval import GalleryShard, QuantizedShard, two_stage_search
+from cor_amd.utils import ClockSampler
+
+C = 256
+CASES = ((512, 1_000_000, 10), (512, 1_000_000, 100), (512, 125_000, 10), (32, 100_000, 100))
+dev = "cuda:0"
+
+
+def window_us(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record(); e1.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3
+
+
+def alternate(fa, fb, n, warmup, reps):
+    for _ in range(warmup):
+        window_us(fa, n); window_us(fb, n)
+    ta, tb = [], []
+    for _ in range(reps):
+        ta.append(window_us(fa, n)); tb.append(window_us(fb, n))
+    return ta, tb
+
+
+def data(Bq, Ng):
+    g = torch.Generator(device=dev).manual_seed(Bq + Ng)
+    Q = torch.nn.functional.normalize(torch.randn((Bq, C), device=dev, generator=g), dim=-1)
+    G = torch.nn.functional.normalize(torch.randn((Ng, C), device=dev, generator=g), dim=-1)
+    return Q, G
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "topk_i8_bench.jsonl"))
+    ap.add_argument("--one", nargs=2, metavar=("BQxNG", "K"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise RuntimeError("topk_i8_bench.py measures on the GPU (no CPU path)")
+    if a.one:
+        Bq, Ng = (int(v) for v in a.one[0].split("x"))
+        Q, G = data(Bq, Ng)
+        q, sc = ops.quantize_rows_i8(G)
+        for _ in range(20):
+            ops.similarity_topk_i8(Q, q, sc, int(a.one[1]))
+        torch.cuda.synchronize()
+        return
+    med = statistics.median
+    rows, cache = [], {}
+    for Bq, Ng, k in CASES:
+        if (Bq, Ng) not in cache:
+            cache.clear()
+            Q, G = data(Bq, Ng)
+            q, sc = ops.quantize_rows_i8(G)
+            if Ng == 1_000_000:
+                for _ in range(2):
+                    ops.quantize_rows_i8(G)
+                rows.append(dict(bench="quantize_rows_i8", rows=Ng, C=C, src="torch.float32", us=window_us(lambda: ops.quantize_rows_i8(G), 5)))
+                print(json.dumps(rows[-1]), flush=True)
+            cache[(Bq, Ng)] = (Q, G, G.to(torch.bfloat16), q, sc)
+        Q, G, Gb, q, sc = cache[(Bq, Ng)]
+        _, raw = ops.similarity_topk_i8(Q, q, sc, k, flags=nat.TOPK_NO_FALLBACK)
+        _, fi = ops.similarity_topk(Q, G, k)
+        _, ii = ops.similarity_topk_i8(Q, q, sc, k)
+        overlap = float((ii[:, :, None] == fi[:, None, :]).any(-1).float().mean())       # share of the fp32 top-k the int8 top-k holds
+        n = max(5, min(200, int(2e9 / (Bq * Ng))))                                         # windows of a few ms
+        clock = ClockSampler(dev).start()
+        t8, tb = alternate(lambda: ops.similarity_topk_i8(Q, q, sc, k), lambda: ops.similarity_topk(Q, Gb, k), n, a.warmup, a.reps)
+        clock = clock.stop()
+        rows.append(dict(bench="topk_i8", Bq=Bq, Ng=Ng, C=C, k=k, i8_us=med(t8), i8_us_min_max=[min(t8), max(t8)], bf16_us=med(tb),
+                         bf16_us_min_max=[min(tb), max(tb)], bf16_over_i8=med(tb) / med(t8), calls_per_window=n, reps=a.reps,
+                         queries_overflowed=int((raw == -2).any(dim=1).sum()), overlap_with_fp32_topk=overlap,
+                         sclk_mhz_mean=clock.get("sclk_mhz_mean")))
+        print(json.dumps(rows[-1]), flush=True)
+        fine, c8, cb = GalleryShard(G), QuantizedShard(q, sc), GalleryShard(Gb)
+        kc = max(k, 100)
+        want = fine.search(Q, 10)[1]
+        hit8 = float((two_stage_search(Q, c8, fine, 10, kc)[1] == want).all(1).float().mean())
+        hitb = float((two_stage_search(Q, cb, fine, 10, kc)[1] == want).all(1).float().mean())
+        clock = ClockSampler(dev).start()
+        t8, tb = alternate(lambda: two_stage_search(Q, c8, fine, 10, kc), lambda: two_stage_search(Q, cb, fine, 10, kc), n, a.warmup, a.reps)
+        clock = clock.stop()
+        rows.append(dict(bench="two_stage", Bq=Bq, Ng=Ng, C=C, k=10, k_coarse=kc, i8_coarse_us=med(t8), i8_coarse_us_min_max=[min(t8), max(t8)],
+                         bf16_coarse_us=med(tb), bf16_coarse_us_min_max=[min(tb), max(tb)], bf16_over_i8=med(tb) / med(t8),
+                         queries_equal_to_fp32_top10=dict(i8=hit8, bf16=hitb), calls_per_window=n, reps=a.reps,
+                         sclk_mhz_mean=clock.get("sclk_mhz_mean")))
+        print(json.dumps(rows[-1]), flush=True)
+    with open(a.out, "a") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
