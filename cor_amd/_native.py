@@ -76,6 +76,8 @@ SIGNATURES = {
     "cor_quantize_rows_i8": [_p, _i, _i, _i, _p, _p, _p],
     "cor_topk_i8_workspace_bytes": [_i, _i, _i],
     "cor_similarity_topk_i8": [_p, _p, _p, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p],
+    "cor_topk_i8_filtered_workspace_bytes": [_i, _i, _i],
+    "cor_similarity_topk_i8_filtered": [_p, _p, _p, _i, _i, _i, _i, _ll, _p, _p, _i, _p, _p, _p, _i, _p],
     "cor_merge_topk_workspace_bytes": [_i, _i, _i, _i],
     "cor_merge_topk": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "cor_rescore_workspace_bytes": [_i, _i, _i],
@@ -85,7 +87,8 @@ SIGNATURES = {
     "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
-            "cor_topk_i8_workspace_bytes": _l, "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}
+            "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,
+            "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}
 
 _lib = None
 

@@ -2536,7 +2536,8 @@ struct WidePlan {
 };
 // group = the distinct-group route (any k): the sample keeps NV = 1 (filter: 4) values WITH rows per group, and the capacity plan below.
 // i8 = the int8 route (cor_similarity_topk_i8; scan must be set): the scan form's 64-row tiles and lane-quarter streams, query groups of
-// 512 (sim_i8_scan: 8 waves x 64 queries), and entry lists as the tile form keeps them.
+// 512 (sim_i8_scan: 8 waves x 64 queries), and entry lists as the tile form keeps them. i8 + filter (cor_similarity_topk_i8_filtered): four
+// sample values per group like every filtered plan, but no 128 clamp: sim_i8_scan carries a tile's labels with the tile.
 inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false) {
   WidePlan p{};
   p.scan = scan;
@@ -2555,7 +2556,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   if (want > p.ntiles) want = p.ntiles;
   if (want < 1) want = 1;
   p.tiles_per_split = cdiv(p.ntiles, want);
-  if (filter && scan && p.tiles_per_split > 128) p.tiles_per_split = 128;
+  if (filter && scan && !i8 && p.tiles_per_split > 128) p.tiles_per_split = 128;
   p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
   const int per_tile = scan ? 4 : 2;                   // streams per slice: lane quarters (scan) / lane halves (tiles)
   p.nstreams = per_tile * p.nsplit;
@@ -2591,7 +2592,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
     int sw = scan ? 256 : 512;
     if (sw > p.s_tiles) sw = p.s_tiles;
     p.s_tiles_per_split = cdiv(p.s_tiles, sw);
-    if (filter && scan && p.s_tiles_per_split > 128) p.s_tiles_per_split = 128;
+    if (filter && scan && !i8 && p.s_tiles_per_split > 128) p.s_tiles_per_split = 128;
     p.s_nsplit = cdiv(p.s_tiles, p.s_tiles_per_split);
     p.ngroups = per_tile * p.s_nsplit * (filter ? 4 : 1);
     const long expect = (group ? 6L : 3L) * k * p.s_stride;   // candidates per query, ~2x slack
@@ -2760,6 +2761,7 @@ int launch_topk(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long 
 // any summation order, so the scan's score IS the score: delta = 0, nothing is re-scored (include/cor_amd.h has the definition). Every k
 // takes the wide route's steps with the fp32 gallery's selection: sim_i8_scan<SAMPLE>, sim_tau_wide<float>, sim_i8_scan<APPEND>,
 // sim_final_wide<float> on the entry lists, and for an overflowed query sim_i8_repair (brute_force_by over the int8 scores).
+// cor_similarity_topk_i8_filtered takes the same steps with a label filter inside them (sim_i8_scan<.., FILTER>, sim_i8_repair_filtered).
 //
 // sim_i8_scan: v_mfma_i32_16x16x64_i8, gallery rows as the A operand, queries as B. A block is 8 waves; wave w keeps the fragments of ITS 64
 // queries (4 column blocks x C/64 K steps x 16 B per lane = 64 VGPRs at C = 256) for the whole slice, and all 8 waves share every 64-row
@@ -2779,16 +2781,23 @@ struct I8ScanArgs {
   int Bq, Ng, C, nqg, nsplit, tiles_per_split, ntiles, tile_stride;
   unsigned* sg; int ngroups;
   const float* tau; int* cnt; uint2* lst; int cap;
+  const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
 };
 constexpr int I8_TILE_SLOTS = 64 * 17;                 // 64 rows x the largest stride
 // FULL: C = 256, every chunk and K step present (no tail tests in the loop). APPEND tests a cheap upper bound first: rounding is monotone and
 // qscale, gscale >= 0, so ((float)max(d_0..d_3, 0) * qscale) * max(gscale_0..3) is >= each of the lane's four scores of a query; only
 // where some lane's bound reaches tau_q are the four scores formed and compared (a few rows in 10^4 pass tau_q).
-template <bool SAMPLE, bool FULL>
+// FILTER (cor_similarity_topk_i8_filtered): the tile's 64 row labels travel with its scales (threads 16..31 fetch them, four each, into the
+// same prefetch register; tile_gs[.][16 + i] holds labels 4 i .. 4 i + 3, 0 beyond Ng where the row test already masks), each lane keeps the
+// labels of its four queries, and a disallowed score is -inf: never among a group's best, never appended. The bound test needs no label
+// (it is >= every score of the four rows, allowed or not). SAMPLE keeps the group's four best allowed scores (sim_wide_scan's insertion;
+// sg[q * ngroups + stream * 4 + j], ngroups counts the four), and slice `split` walks the tiles split, split + nsplit, ...: the allowed rows
+// of a class-sorted gallery spread over every stream and every sample group.
+template <bool SAMPLE, bool FULL, bool FILTER = false>
 __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict__ G, const I8ScanArgs a) {
 #pragma clang fp contract(off)
   __shared__ uint4 tile[2][I8_TILE_SLOTS];
-  __shared__ f32x4 tile_gs[2][16];                     // the tile's 64 row scales (0 beyond Ng), fetched with it
+  __shared__ f32x4 tile_gs[2][FILTER ? 32 : 16];       // the tile's 64 row scales (0 beyond Ng), fetched with it; FILTER: and its 64 labels
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, rq = lane >> 4;
   const int qg = blockIdx.x % a.nqg, split = blockIdx.x / a.nqg;
   const int Ng = a.Ng, C = FULL ? 256 : a.C, nch = C >> 4, nks = (C + 63) >> 6;
@@ -2799,6 +2808,8 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
   i32x4 qf[4][4];
   float qs[4], tq[4], gmax[4];
   int n[4];
+  int ql[4];                                           // FILTER: the queries' labels (< 0: unrestricted)
+  float top4[4][4];                                    // FILTER SAMPLE: the group's four best allowed scores, descending
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int q = q0 + 16 * j + c16;
@@ -2813,6 +2824,11 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
     tq[j] = SAMPLE ? 0.f : (active && q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
     gmax[j] = -INFINITY;
     n[j] = 0;
+    if constexpr (FILTER) {
+      ql[j] = active ? a.qlab[min(q, a.Bq - 1)] : -1;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) top4[j][i] = -INFINITY;
+    }
   }
   const int stream = split * 4 + rq, nstreams = 4 * a.nsplit;
   // the thread's two 16-B pieces of a tile: piece i = tid + 512 p is chunk i % nch of row i / nch (a tile is contiguous in the gallery)
@@ -2823,10 +2839,14 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
     const int i = tid + 512 * p, r = i / nch, ch = i - r * nch;
     slot[p] = r < 64 ? r * stride + (ch ^ (r & xmask)) : -1;
   }
-  const int t0 = split * a.tiles_per_split, t1 = min(t0 + a.tiles_per_split, a.ntiles);
+  // the slice's tiles: t0 .. t1 - 1 of the contiguous walk, tile(t) = t; FILTER: the interleaved walk, tile(t) = split + t * nsplit
+  const int t0 = FILTER ? 0 : split * a.tiles_per_split;
+  const int t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
+  auto tile_of = [&](int t) { return FILTER ? split + t * a.nsplit : t; };
   uint4 pre[2];
   f32x4 pre_gs = {0.f, 0.f, 0.f, 0.f};
   auto fetch = [&](int t) {
+    t = tile_of(t);
     const long base = (long)t * a.tile_stride * 64 * C;
     if (tid < 16) {
       const int gr = t * a.tile_stride * 64 + 4 * tid;
@@ -2835,6 +2855,15 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e) pre_gs[e] = gr + e < Ng ? a.gscale[gr + e] : 0.f;
       }
+    } else if (FILTER && tid < 32) {
+      const int gr = t * a.tile_stride * 64 + 4 * (tid - 16);
+      i32x4 l = {0, 0, 0, 0};
+      if (gr + 4 <= Ng) l = *(const i32x4*)(a.rlab + gr);
+      else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) l[e] = gr + e < Ng ? a.rlab[gr + e] : 0;
+      }
+      pre_gs = __builtin_bit_cast(f32x4, l);
     }
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -2850,11 +2879,11 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
 #pragma unroll
     for (int p = 0; p < 2; ++p)
       if (slot[p] >= 0) buf[slot[p]] = pre[p];
-    if (tid < 16) tile_gs[(t - t0) & 1][tid] = pre_gs;
+    if (tid < (FILTER ? 32 : 16)) tile_gs[(t - t0) & 1][tid] = pre_gs;
     __syncthreads();                                   // the other buffer was last read before this barrier: the next stores are safe
     if (t + 1 < t1) fetch(t + 1);
     if (!active) continue;
-    const int g0 = t * a.tile_stride * 64;
+    const int g0 = tile_of(t) * a.tile_stride * 64;
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
       const int gr = g0 + 16 * sub + 4 * rq;           // the lane's rows gr .. gr + 3 of this 16-row block
@@ -2878,7 +2907,18 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
       const float gsmax = fmaxf(fmaxf(gs[0], gs[1]), fmaxf(gs[2], gs[3]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if constexpr (SAMPLE) {
+        if constexpr (SAMPLE && FILTER) {
+          const i32x4 lab = __builtin_bit_cast(i32x4, buf_gs[16 + 4 * sub + rq]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool ok = gr + e < Ng && (ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0)));
+            const float s = ok ? ((float)acc[j][e] * qs[j]) * gs[e] : -INFINITY;
+            top4[j][3] = fmaxf(top4[j][3], fminf(top4[j][2], s));
+            top4[j][2] = fmaxf(top4[j][2], fminf(top4[j][1], s));
+            top4[j][1] = fmaxf(top4[j][1], fminf(top4[j][0], s));
+            top4[j][0] = fmaxf(top4[j][0], s);
+          }
+        } else if constexpr (SAMPLE) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float s = ((float)acc[j][e] * qs[j]) * gs[e];
@@ -2889,10 +2929,13 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
           const float bound = ((float)dmax * qs[j]) * gsmax;
           if (__builtin_amdgcn_ballot_w64(bound >= tq[j]) != 0) {
             uint2* dst = a.lst + ((long)min(q0 + 16 * j + c16, a.Bq - 1) * nstreams + stream) * a.cap;
+            i32x4 lab = {0, 0, 0, 0};
+            if constexpr (FILTER) lab = __builtin_bit_cast(i32x4, buf_gs[16 + 4 * sub + rq]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float s = ((float)acc[j][e] * qs[j]) * gs[e];
-              if (gr + e < Ng && s >= tq[j]) {
+              const bool ok = !FILTER || ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0));
+              if (gr + e < Ng && ok && s >= tq[j]) {
                 if (n[j] < a.cap) dst[n[j]] = make_uint2(__float_as_uint(s), (unsigned)(gr + e));
                 ++n[j];
               }
@@ -2907,7 +2950,9 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
   for (int j = 0; j < 4; ++j) {
     const int q = q0 + 16 * j + c16;
     if (q < a.Bq) {
-      if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax[j]);
+      if constexpr (SAMPLE && FILTER)
+        *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[j][0]), f2key(top4[j][1]), f2key(top4[j][2]), f2key(top4[j][3]));
+      else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax[j]);
       else a.cnt[(long)q * nstreams + stream] = n[j];
     }
   }
@@ -2915,9 +2960,13 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
 
 // Overflowed queries of the int8 route (sim_final_wide ran with the marker on: slot 0 is (-inf, -2), which no ranked query carries):
 // the exact top-k by brute force over the int8 scores, one block of 256 threads per query; every other block leaves at once.
-__global__ void __launch_bounds__(256) sim_i8_repair(const signed char* __restrict__ qq, const float* __restrict__ qscale,
-                                                     const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C, int k,
-                                                     long long g_offset, float* out_s, long long* out_i) {
+// FILTER (sim_i8_repair_filtered, a kernel of its own so that the unfiltered one stays as compiled): only the rows allowed for the query
+// are ranked, and a query with at most k allowed rows gets them followed by the (-inf, -1) tail (brute_force_by<true>).
+template <bool FILTER>
+__device__ __forceinline__ void i8_repair_body(const signed char* __restrict__ qq, const float* __restrict__ qscale,
+                                               const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C, int k,
+                                               long long g_offset, float* out_s, long long* out_i, const int* __restrict__ rlab,
+                                               const int* __restrict__ qlab, int ne) {
 #pragma clang fp contract(off)
   __shared__ float sl_s[COR_TOPK_KMAX];
   __shared__ int sl_i[COR_TOPK_KMAX], hist[256];
@@ -2941,34 +2990,59 @@ __global__ void __launch_bounds__(256) sim_i8_repair(const signed char* __restri
     }
     return ((float)d * qs) * gscale[g];
   };
-  brute_force_by<false>(score_at, [](int) { return true; }, Ng, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
+  if constexpr (FILTER) {
+    const int ql = qlab[q];
+    brute_force_by<true>(score_at, [&](int g) { return ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
+                         out_s + (long)q * k, out_i + (long)q * k);
+  } else {
+    brute_force_by<false>(score_at, [](int) { return true; }, Ng, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
+  }
+}
+__global__ void __launch_bounds__(256) sim_i8_repair(const signed char* __restrict__ qq, const float* __restrict__ qscale,
+                                                     const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C, int k,
+                                                     long long g_offset, float* out_s, long long* out_i) {
+  i8_repair_body<false>(qq, qscale, G, gscale, Ng, C, k, g_offset, out_s, out_i, nullptr, nullptr, 0);
+}
+__global__ void __launch_bounds__(256) sim_i8_repair_filtered(const signed char* __restrict__ qq, const float* __restrict__ qscale,
+                                                              const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C,
+                                                              int k, long long g_offset, float* out_s, long long* out_i,
+                                                              const int* __restrict__ rlab, const int* __restrict__ qlab, int ne) {
+  i8_repair_body<true>(qq, qscale, G, gscale, Ng, C, k, g_offset, out_s, out_i, rlab, qlab, ne);
 }
 
+// FILTER: cor_similarity_topk_i8_filtered, the same steps with the filter inside them (c.rlab / c.qlab / c.ne).
+template <bool FILTER>
 int launch_topk_i8(const signed char* Gq, const WideCall& c) {
-  const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, false, false, true);
+  const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, FILTER, false, true);
   signed char* qq = (signed char*)(c.w + p.off_img); float* qscale = (float*)(c.w + p.off_dq);
   if (const int e = cor_quantize_rows_i8(c.Q, COR_F32, c.Bq, c.C, qq, qscale, c.s)) return e;
   I8ScanArgs a{};
   a.qq = qq; a.qscale = qscale; a.gscale = c.gscale; a.Bq = c.Bq; a.Ng = c.Ng; a.C = c.C; a.nqg = p.nqg;
   a.sg = (unsigned*)(c.w + p.off_sg); a.ngroups = p.ngroups;
+  a.rlab = c.rlab; a.qlab = c.qlab; a.ne = c.ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<true, true>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
-    else hipLaunchKernelGGL((sim_i8_scan<true, false>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<true, true, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    else hipLaunchKernelGGL((sim_i8_scan<true, false, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
     COR_CHECK_LAUNCH();
   }
   if (const int e = launch_wide_tau<float, false>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.tau = (const float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.lst = (uint2*)(c.w + p.off_recs); a.cap = p.cap;
-  if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<false, true>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
-  else hipLaunchKernelGGL((sim_i8_scan<false, false>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
+  if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
+  else hipLaunchKernelGGL((sim_i8_scan<false, false, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
   COR_CHECK_LAUNCH();
-  // the fp32 gallery's selection over the entry lists; an overflow leaves the marker and never touches the (absent) float rows
+  // the fp32 gallery's selection over the entry lists (allowed rows only with FILTER); an overflow leaves the marker and never touches
+  // the (absent) float rows
   WideCall sel = c;
   sel.flags |= COR_TOPK_NO_FALLBACK;
   if (const int e = launch_wide_final<float, false, false, false>((const float*)nullptr, sel, p)) return e;
   if (!(c.flags & COR_TOPK_NO_FALLBACK)) {
-    hipLaunchKernelGGL(sim_i8_repair, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.out_s, c.out_i);
+    if constexpr (FILTER)
+      hipLaunchKernelGGL(sim_i8_repair_filtered, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.out_s, c.out_i,
+                         c.rlab, c.qlab, c.ne);
+    else
+      hipLaunchKernelGGL(sim_i8_repair, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.out_s, c.out_i);
     COR_CHECK_LAUNCH();
   }
   return 0;
@@ -2988,21 +3062,23 @@ inline int distinct_sample_values(int Bq, int Ng, int k) {
 inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
 
 constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
-enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8 };
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED };
 
-// The argument checks of the three search entry points, in the order (and with the codes) of the ABI. What differs by route: the
-// pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither), the A/B flags it refuses
+// The argument checks of the search entry points, in the order (and with the codes) of the ABI. What differs by route: the
+// pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither; int8: the row scales, and
+// filtered int8 both label vectors as well), the A/B flags it refuses
 // (the plain call only at k > 32) and the distinct route's sample bound.
 int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
   const bool own_ptrs = route == ROUTE_TOPK       ? true
                         : route == ROUTE_I8       ? c.gscale != nullptr
+                        : route == ROUTE_I8_FILTERED ? c.gscale && c.rlab && c.qlab
                         : route == ROUTE_FILTERED ? c.rlab && c.qlab
                                                   : c.grp && (c.rlab == nullptr) == (c.qlab == nullptr);
   if (!c.Q || !G || !own_ptrs || !c.out_s || !c.out_i || !c.w || c.Bq <= 0 || c.Ng <= 0 || c.k <= 0) return COR_EINVAL;
   if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
   if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
   if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
-  if (route == ROUTE_I8 && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
+  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED) && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
   if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
   if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab | (uintptr_t)c.gscale) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
   return 0;
@@ -3082,5 +3158,19 @@ extern "C" int cor_similarity_topk_i8(const float* Q, const signed char* Gq, con
                                       float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
   const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream, gscale};
   if (const int e = check_topk_call(ROUTE_I8, c, Gq, COR_FILTER_EQ)) return e;
-  return launch_topk_i8(Gq, c);
+  return launch_topk_i8<false>(Gq, c);
+}
+
+extern "C" long cor_topk_i8_filtered_workspace_bytes(int Bq, int Ng, int k) {
+  return topk_shape_ok(Bq, Ng, k) ? (long)make_wide(Bq, Ng, k, true, true, false, true).bytes : COR_EINVAL;
+}
+
+// filtered int8 calls: the int8 route with the filter inside its scans (launch_topk_i8<true>)
+extern "C" int cor_similarity_topk_i8_filtered(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k,
+                                               long long g_offset, const int* row_labels, const int* query_labels, int filter_mode,
+                                               float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, row_labels, query_labels, filter_mode == COR_FILTER_NE ? 1 : 0, out_scores, out_idx,
+                   (char*)workspace, flags, (hipStream_t)stream, gscale};
+  if (const int e = check_topk_call(ROUTE_I8_FILTERED, c, Gq, filter_mode)) return e;
+  return launch_topk_i8<true>(Gq, c);
 }

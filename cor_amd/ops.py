@@ -494,13 +494,18 @@ def similarity_topk(Q, G, k, g_offset=0, flags=0):
     return scores, idx
 
 
-def _labels(t, n, name, device, who="similarity_topk_filtered"):
+def _label_vec(t, n, name, who):
+    """The shape and dtype checks of a label vector (nothing moves)."""
     t = torch.as_tensor(t)
     if t.dim() != 1 or t.shape[0] != n:
         raise ValueError(f"{who}: {name} must be a vector of {n} labels, got shape {tuple(t.shape)}")
     if t.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"{who}: {name} must be int32 (int64 is converted), got {t.dtype}")
-    t = t.to(device=device, dtype=torch.int32).contiguous()
+    return t
+
+
+def _labels(t, n, name, device, who="similarity_topk_filtered"):
+    t = _label_vec(t, n, name, who).to(device=device, dtype=torch.int32).contiguous()
     if t.data_ptr() % 16:                                     # the kernels read row labels 16 B at a time (a view into a larger tensor)
         t = t.clone()
     return t
@@ -562,26 +567,52 @@ def quantize_rows_i8(X):
     return q, scale
 
 
-def similarity_topk_i8(Q, Gq, gscale, k, g_offset=0, flags=0):
-    """similarity_topk over an int8 gallery: Q fp32 [Bq,C]; Gq int8 [Ng,C] and gscale f32 [Ng] as quantize_rows_i8 returns them. The query
-    is quantised the same way inside the call; score = ((float)(int32 dot) * qscale) * gscale, exact in any summation order, ranked by
-    (score key desc, index asc): bit-identical to tests/i8_refs.py, scores and indices. 1 <= k <= 256, C % 16 == 0, C <= 256; Ng < k:
-    the tail is (-inf, -1). One route for every k; a candidate overflow is repaired on the device. flags: 0 or nat.TOPK_NO_FALLBACK."""
-    who = "similarity_topk_i8"
+def _i8_front(who, Q, Gq, gscale, k, flags, mode="eq"):
+    """The checks the two int8 searches share, before anything touches the device. Returns (Bq, Ng, C, gscale as the scan reads it)."""
     if Gq.dtype != torch.int8:
         raise ValueError(f"{who}: Gq must be int8 rows (ops.quantize_rows_i8), got {Gq.dtype}")
     if gscale.dtype != torch.float32 or gscale.dim() != 1 or Gq.dim() != 2 or gscale.shape[0] != Gq.shape[0]:
         raise ValueError(f"{who}: gscale must be float32 [Ng] for Gq [Ng, C], got {gscale.dtype} {tuple(gscale.shape)} for {tuple(Gq.shape)}")
     if int(flags) & ~nat.TOPK_NO_FALLBACK:
         raise ValueError(f"{who}: flags must be 0 or TOPK_NO_FALLBACK, got {flags}")
-    Bq, Ng, C = _topk_front(who, Q, Gq, k)
+    Bq, Ng, C = _topk_front(who, Q, Gq, k, mode)
     _dev(Q, gscale)
     gscale = gscale.contiguous()
     if gscale.data_ptr() % 16:                                # a view into a larger tensor: the scan loads four scales at a time
         gscale = gscale.clone()
+    return Bq, Ng, C, gscale
+
+
+def similarity_topk_i8(Q, Gq, gscale, k, g_offset=0, flags=0):
+    """similarity_topk over an int8 gallery: Q fp32 [Bq,C]; Gq int8 [Ng,C] and gscale f32 [Ng] as quantize_rows_i8 returns them. The query
+    is quantised the same way inside the call; score = ((float)(int32 dot) * qscale) * gscale, exact in any summation order, ranked by
+    (score key desc, index asc): bit-identical to tests/i8_refs.py, scores and indices. 1 <= k <= 256, C % 16 == 0, C <= 256; Ng < k:
+    the tail is (-inf, -1). One route for every k; a candidate overflow is repaired on the device. flags: 0 or nat.TOPK_NO_FALLBACK."""
+    Bq, Ng, C, gscale = _i8_front("similarity_topk_i8", Q, Gq, gscale, k, flags)
     ws, scores, idx = _topk_buffers("cor_topk_i8_workspace_bytes", Q, Bq, Ng, k)
     nat.check(_lib().cor_similarity_topk_i8(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, k, int(g_offset), scores.data_ptr(),
                                             idx.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_topk_i8")
+    return scores, idx
+
+
+def similarity_topk_i8_filtered(Q, Gq, gscale, k, row_labels, query_labels, mode="eq", g_offset=0, flags=0):
+    """similarity_topk_i8 over the ALLOWED rows only: the score and order of similarity_topk_i8, the allowed rows of
+    similarity_topk_filtered (query_labels[b] < 0: unrestricted; mode "eq": row_labels[g] == query_labels[b]; mode "ne": !=).
+    row_labels int32[Ng], query_labels int32[Bq] (int64 is converted, a misaligned view is realigned). Bit-identical to
+    tests/i8_filtered_refs.py, scores and indices; fewer than k allowed rows: those, then the (-inf, -1) tail. One route for every k, the
+    filter inside the int8 scan; an overflowed query is ranked over its allowed rows on the device. No host synchronisation when the
+    labels already live on the device. flags: 0 or nat.TOPK_NO_FALLBACK."""
+    who = "similarity_topk_i8_filtered"
+    if Gq.dim() == 2 and Q.dim() == 2:                        # the label checks raise before anything touches the device
+        _label_vec(row_labels, Gq.shape[0], "row_labels", who)
+        _label_vec(query_labels, Q.shape[0], "query_labels", who)
+    Bq, Ng, C, gscale = _i8_front(who, Q, Gq, gscale, k, flags, mode)
+    rl = _labels(row_labels, Ng, "row_labels", Q.device, who)
+    qlab = _labels(query_labels, Bq, "query_labels", Q.device, who)
+    ws, scores, idx = _topk_buffers("cor_topk_i8_filtered_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk_i8_filtered(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, k, int(g_offset), rl.data_ptr(),
+                                                     qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                                     int(flags), _s()), "cor_similarity_topk_i8_filtered")
     return scores, idx
 
 

@@ -405,6 +405,30 @@ long cor_topk_i8_workspace_bytes(int Bq, int Ng, int k);
 int cor_similarity_topk_i8(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k, long long g_offset,
                            float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
 
+/* Filtered int8 search (cor_similarity_topk_i8_filtered): the top-k of the ALLOWED rows of an int8 gallery.
+ * SCORE and ORDER are exactly those of cor_similarity_topk_i8: d = the int32 dot product of the quantised query and the row,
+ * score = ((float)d * qscale) * gscale, ranked by the order-preserving key of the score's bits descending, then row index ascending.
+ * ALLOWED rows are exactly those of cor_similarity_topk_filtered: row g is allowed for query b if query_labels[b] < 0 (unrestricted), or
+ * COR_FILTER_EQ and row_labels[g] == query_labels[b], or COR_FILTER_NE and row_labels[g] != query_labels[b]. row_labels i32 [Ng]
+ * (shard-local row g; 16-byte aligned), query_labels i32 [Bq]. Per query the result is the top-k of its allowed rows only: fewer than k
+ * allowed rows give those first and then the (-inf, -1) tail, no allowed row gives only the tail. The result is bit-identical to that
+ * definition evaluated on the CPU (tests/i8_filtered_refs.py), scores and indices.
+ * Other arguments as for cor_similarity_topk_i8; workspace (256-byte aligned) >= cor_topk_i8_filtered_workspace_bytes(Bq, Ng, k). Checks in
+ * the order and with the codes of cor_similarity_topk_i8: null pointers (the label pointers included) or Bq / Ng / k <= 0: COR_EINVAL;
+ * filter_mode neither COR_FILTER_EQ nor COR_FILTER_NE: COR_EINVAL; k > COR_TOPK_KMAX, C > 256 or C % 16: COR_ENOSUPPORT; a flag other than
+ * COR_TOPK_NO_FALLBACK: COR_ENOSUPPORT; Q, Gq, gscale or row_labels not 16-byte aligned, workspace not 256-byte aligned: COR_EINVAL. No
+ * allocation, no host synchronisation: the call can be captured in a graph.
+ * Route: the int8 route's steps with the filter inside them: a disallowed score is -inf before the sample's group values, the threshold
+ * and the append decision. A tile's 64 row labels travel through LDS with its 64 row scales, each lane keeps the labels of its four
+ * queries in registers. The sample keeps the four best allowed scores per group and the scan slices walk the gallery interleaved (slice s
+ * takes tiles s, s + nsplit, ...), so a selective filter keeps its threshold and a class-sorted gallery does not crowd a few candidate
+ * streams. An overflowed query is ranked over its allowed rows by the brute force over the int8 scores; with COR_TOPK_NO_FALLBACK it
+ * carries index -2 in every slot instead. Distinct-group int8 search does not exist. */
+long cor_topk_i8_filtered_workspace_bytes(int Bq, int Ng, int k);
+int cor_similarity_topk_i8_filtered(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k,
+                                    long long g_offset, const int* row_labels, const int* query_labels, int filter_mode,
+                                    float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
+
 /* Merge of top-k lists on the device: per query b, P lists of kin entries (what P calls of cor_similarity_topk[_filtered|_distinct] over P
  * shards return, stacked) -> the k best entries of their union. scores f32 [P,Bq,kin], idx i64 [P,Bq,kin] (global row ids), groups NULL or
  * i32 [P,Bq,kin] (one group id per entry), all contiguous; out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_groups NULL or i32 [Bq,k].

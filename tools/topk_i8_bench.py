@@ -6,7 +6,14 @@ with the bf16 coarse stage alternate the same way (k_coarse = max(k, 100), final
 once. The mean shader clock over each measurement is reported. One JSON line per measurement, printed and appended to --out (default
 profiles/topk_i8_bench.jsonl).
     python tools/topk_i8_bench.py [--reps 7] [--warmup 2] [--out FILE]
-    python tools/topk_i8_bench.py --one 512x1000000 10        # the int8 call alone, 20 calls (for a rocprofv3 --kernel-trace --stats run)"""
+    python tools/topk_i8_bench.py --one 512x1000000 10        # the int8 call alone, 20 calls (for a rocprofv3 --kernel-trace --stats run)
+--filtered: the filtered int8 call (ops.similarity_topk_i8_filtered's entry point) instead, appended to profiles/topk_i8_filtered_bench.jsonl.
+Per shape and label layout ("ne": image ids in runs of 1-8 rows, every query excludes its own image; "eq": 16 uniformly random classes) three
+sides rotate, each through the C entry point with preallocated outputs and workspace: the new call, (a) cor_similarity_topk_filtered over
+the bf16 copy of the same rows with the same labels, (b) the unfiltered cor_similarity_topk_i8. Then (c) two_stage_search (k_coarse = 100,
+k = 10, fp32 master rows) with the int8 and with the bf16 coarse stage alternate, both filtered.
+    python tools/topk_i8_bench.py --filtered [--reps 7] [--warmup 2] [--out FILE]
+    python tools/topk_i8_bench.py --filtered --one 512x1000000 10 [--layout ne|eq]"""
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,6 +45,107 @@ def alternate(fa, fb, n, warmup, reps):
     return ta, tb
 
 
+def rotate(fns, n, warmup, reps):
+    """alternate() for any number of sides"""
+    for _ in range(warmup):
+        for f in fns:
+            window_us(f, n)
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for t, f in zip(ts, fns):
+            t.append(window_us(f, n))
+    return ts
+
+
+def labels(layout, Bq, Ng):
+    """(row labels i32[Ng], query labels i32[Bq], mode) on the device. ne: image ids in runs of 1-8 rows, query b is a region of the image
+    of row b * Ng // Bq and excludes it; eq: 16 uniformly random classes, a random class per query."""
+    g = torch.Generator(device=dev).manual_seed(Bq * 3 + Ng)
+    if layout == "ne":
+        runs = torch.randint(1, 9, (Ng,), device=dev, generator=g)
+        rl = torch.repeat_interleave(torch.arange(Ng, device=dev), runs)[:Ng].to(torch.int32).contiguous()
+        return rl, rl[(torch.arange(Bq, device=dev) * Ng) // Bq].contiguous(), "ne"
+    rl = torch.randint(0, 16, (Ng,), device=dev, generator=g).to(torch.int32)
+    return rl, torch.randint(0, 16, (Bq,), device=dev, generator=g).to(torch.int32), "eq"
+
+
+def direct_calls(Q, Gb, q, sc, rl, ql, mode, k):
+    """the three sides as closures over preallocated buffers: (int8 filtered, bf16 filtered, int8 unfiltered), and the int8 filtered outputs"""
+    lib, st = nat.load(), torch.cuda.current_stream().cuda_stream
+    Bq, Ng, m = Q.shape[0], q.shape[0], ops._FILTER_MODES[mode]
+    w8f, s8f, i8f = ops._topk_buffers("cor_topk_i8_filtered_workspace_bytes", Q, Bq, Ng, k)
+    wbf, sbf, ibf = ops._topk_buffers("cor_topk_filtered_workspace_bytes", Q, Bq, Ng, k)
+    w8, s8, i8 = ops._topk_buffers("cor_topk_i8_workspace_bytes", Q, Bq, Ng, k)
+
+    def i8_filtered(flags=0):
+        nat.check(lib.cor_similarity_topk_i8_filtered(Q.data_ptr(), q.data_ptr(), sc.data_ptr(), Bq, Ng, C, k, 0, rl.data_ptr(), ql.data_ptr(), m,
+                                                      s8f.data_ptr(), i8f.data_ptr(), w8f.data_ptr(), flags, st), "cor_similarity_topk_i8_filtered")
+
+    def bf16_filtered():
+        nat.check(lib.cor_similarity_topk_filtered(Q.data_ptr(), Gb.data_ptr(), nat.BF16, Bq, Ng, C, k, 0, rl.data_ptr(), ql.data_ptr(), m,
+                                                   sbf.data_ptr(), ibf.data_ptr(), wbf.data_ptr(), 0, st), "cor_similarity_topk_filtered")
+
+    def i8_plain():
+        nat.check(lib.cor_similarity_topk_i8(Q.data_ptr(), q.data_ptr(), sc.data_ptr(), Bq, Ng, C, k, 0, s8.data_ptr(), i8.data_ptr(), w8.data_ptr(),
+                                             0, st), "cor_similarity_topk_i8")
+
+    return i8_filtered, bf16_filtered, i8_plain, (s8f, i8f)
+
+
+def filtered_main(a):
+    med = statistics.median
+    if a.one:
+        Bq, Ng = (int(v) for v in a.one[0].split("x"))
+        Q, G = data(Bq, Ng)
+        q, sc = ops.quantize_rows_i8(G)
+        rl, ql, mode = labels(a.layout, Bq, Ng)
+        f = direct_calls(Q, None, q, sc, rl, ql, mode, int(a.one[1]))[0]
+        for _ in range(20):
+            f()
+        torch.cuda.synchronize()
+        return
+    rows, cache = [], {}
+    for Bq, Ng, k in CASES:
+        if (Bq, Ng) not in cache:
+            cache.clear()
+            Q, G = data(Bq, Ng)
+            cache[(Bq, Ng)] = (Q, G, G.to(torch.bfloat16)) + ops.quantize_rows_i8(G)
+        Q, G, Gb, q, sc = cache[(Bq, Ng)]
+        n = max(5, min(200, int(2e9 / (Bq * Ng))))                                         # windows of a few ms
+        for layout in ("ne", "eq"):
+            rl, ql, mode = labels(layout, Bq, Ng)
+            f8, fb, fp, (s8f, i8f) = direct_calls(Q, Gb, q, sc, rl, ql, mode, k)
+            f8(nat.TOPK_NO_FALLBACK)
+            overflowed = int((i8f == -2).any(dim=1).sum())
+            f8()
+            ok = (rl[i8f.clamp(min=0)] == ql[:, None]) == (mode == "eq")                   # every returned row is an allowed one
+            clock = ClockSampler(dev).start()
+            t8, tb, tp = rotate((f8, fb, fp), n, a.warmup, a.reps)
+            clock = clock.stop()
+            rows.append(dict(bench="topk_i8_filtered", layout=layout, mode=mode, Bq=Bq, Ng=Ng, C=C, k=k, i8_filtered_us=med(t8),
+                             i8_filtered_us_min_max=[min(t8), max(t8)], bf16_filtered_us=med(tb), bf16_filtered_us_min_max=[min(tb), max(tb)],
+                             i8_unfiltered_us=med(tp), i8_unfiltered_us_min_max=[min(tp), max(tp)], bf16_filtered_over_i8_filtered=med(tb) / med(t8),
+                             i8_filtered_over_i8_unfiltered=med(t8) / med(tp), calls_per_window=n, reps=a.reps, queries_overflowed=overflowed,
+                             rows_allowed=bool((ok | (i8f < 0)).all()), sclk_mhz_mean=clock.get("sclk_mhz_mean")))
+            print(json.dumps(rows[-1]), flush=True)
+            if k != 10:
+                continue
+            fine, c8, cb = GalleryShard(G), QuantizedShard(q, sc, labels=rl), GalleryShard(Gb, labels=rl)
+            kw = dict(query_labels=ql, mode=mode)
+            clock = ClockSampler(dev).start()
+            t8, tb = alternate(lambda: two_stage_search(Q, c8, fine, 10, 100, **kw), lambda: two_stage_search(Q, cb, fine, 10, 100, **kw), n,
+                               a.warmup, a.reps)
+            clock = clock.stop()
+            rows.append(dict(bench="two_stage_filtered", layout=layout, mode=mode, Bq=Bq, Ng=Ng, C=C, k=10, k_coarse=100, i8_coarse_us=med(t8),
+                             i8_coarse_us_min_max=[min(t8), max(t8)], bf16_coarse_us=med(tb), bf16_coarse_us_min_max=[min(tb), max(tb)],
+                             bf16_over_i8=med(tb) / med(t8), calls_per_window=n, reps=a.reps, sclk_mhz_mean=clock.get("sclk_mhz_mean")))
+            print(json.dumps(rows[-1]), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+
+
 def data(Bq, Ng):
     g = torch.Generator(device=dev).manual_seed(Bq + Ng)
     Q = torch.nn.functional.normalize(torch.randn((Bq, C), device=dev, generator=g), dim=-1)
@@ -49,11 +157,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "topk_i8_bench.jsonl"))
+    ap.add_argument("--out")
     ap.add_argument("--one", nargs=2, metavar=("BQxNG", "K"))
+    ap.add_argument("--filtered", action="store_true")
+    ap.add_argument("--layout", choices=("ne", "eq"), default="ne")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "topk_i8_filtered_bench.jsonl" if a.filtered else "topk_i8_bench.jsonl")
     if not torch.cuda.is_available():
         raise RuntimeError("topk_i8_bench.py measures on the GPU (no CPU path)")
+    if a.filtered:
+        return filtered_main(a)
     if a.one:
         Bq, Ng = (int(v) for v in a.one[0].split("x"))
         Q, G = data(Bq, Ng)
