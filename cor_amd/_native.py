@@ -78,6 +78,9 @@ SIGNATURES = {
     "cor_similarity_topk_i8": [_p, _p, _p, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p],
     "cor_topk_i8_filtered_workspace_bytes": [_i, _i, _i],
     "cor_similarity_topk_i8_filtered": [_p, _p, _p, _i, _i, _i, _i, _ll, _p, _p, _i, _p, _p, _p, _i, _p],
+    "cor_topk_i8_distinct_workspace_bytes": [_i, _i, _i],
+    "cor_topk_i8_distinct_sample_values": [_i, _i, _i],
+    "cor_similarity_topk_i8_distinct": [_p, _p, _p, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p, _p, _p, _i, _p],
     "cor_merge_topk_workspace_bytes": [_i, _i, _i, _i],
     "cor_merge_topk": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "cor_rescore_workspace_bytes": [_i, _i, _i],
@@ -88,6 +91,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,
+            "cor_topk_i8_distinct_workspace_bytes": _l,
             "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}
 
 _lib = None

@@ -2295,14 +2295,15 @@ __device__ int block_prefix8(const int* flag, int m, int* wtot, int* total) {
 // first_of_group marks the page's first row of every group, the marks of groups already in the table are dropped, and the survivors -
 // representatives, in rank order - go straight to the output. Stops at k groups or when the rows run out. Every page consumes SLW rows,
 // so it terminates; five chain passes over the shard per page: slow only for inputs that are pathological anyway (thousands of rows of
-// one group ahead of everything else). rlab == nullptr: unfiltered.
-template <typename TG>
-__device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, const int* __restrict__ grp,
-                                     float* sl_s, int* sl_i, int* flag, unsigned long long* keys, unsigned long long* k2, unsigned* found, int* hist,
-                                     float* out_s, long long* out_i, const int* __restrict__ rlab, int ql, int ne) {
+// one group ahead of everything else).
+// The body takes the score of a row and the allow predicate as callables (distinct_brute_force_by, as brute_force_by does): the chain over a
+// float / 16-bit gallery in distinct_brute_force (rlab == nullptr: unfiltered), the integer score of the int8 route in sim_i8_repair_distinct.
+template <typename ScoreAt, typename Allowed>
+__device__ __forceinline__ void distinct_brute_force_by(const ScoreAt score_at, const Allowed allowed, int Ng, int k, long long g_offset,
+                                                        const int* __restrict__ grp, float* sl_s, int* sl_i, int* flag, unsigned long long* keys,
+                                                        unsigned long long* k2, unsigned* found, int* hist, float* out_s, long long* out_i) {
   __shared__ int sel_bin, k_rem, n_above, n_allowed, wcnt[4], wtot[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  auto allowed = [&](int g) { return rlab == nullptr || ql < 0 || ((rlab[g] == ql) != (ne != 0)); };
   if (tid == 0) n_allowed = 0;
   __syncthreads();
   {
@@ -2319,7 +2320,7 @@ __device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, co
     // score and eligibility of row g: allowed and behind `last` in rank order; key 0 = not eligible (below every score's key)
     auto score_of = [&](int g, float& s) {
       if (!allowed(g)) return 0u;
-      s = chain_score_c<TG>(G, g, C, qs);
+      s = score_at(g);
       return (first || rank_key(s, g) > last) ? f2key(s) : 0u;
     };
     unsigned kth = 0u;
@@ -2383,6 +2384,14 @@ __device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, co
     first = false;
   }
   for (int j = nfound + tid; j < k; j += 256) { out_s[j] = -INFINITY; out_i[j] = -1LL; }
+}
+template <typename TG>
+__device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, const int* __restrict__ grp,
+                                     float* sl_s, int* sl_i, int* flag, unsigned long long* keys, unsigned long long* k2, unsigned* found, int* hist,
+                                     float* out_s, long long* out_i, const int* __restrict__ rlab, int ql, int ne) {
+  distinct_brute_force_by([&](int g) { return chain_score_c<TG>(G, g, C, qs); },
+                          [&](int g) { return rlab == nullptr || ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, grp, sl_s, sl_i, flag,
+                          keys, k2, found, hist, out_s, out_i);
 }
 
 // Exact selection of the distinct route, one block of 256 threads per query; the gather front ends of sim_final_wide (RECORDS / entry
@@ -2538,6 +2547,9 @@ struct WidePlan {
 // i8 = the int8 route (cor_similarity_topk_i8; scan must be set): the scan form's 64-row tiles and lane-quarter streams, query groups of
 // 512 (sim_i8_scan: 8 waves x 64 queries), and entry lists as the tile form keeps them. i8 + filter (cor_similarity_topk_i8_filtered): four
 // sample values per group like every filtered plan, but no 128 clamp: sim_i8_scan carries a tile's labels with the tile.
+// i8 + group (cor_similarity_topk_i8_distinct): the group capacity numbers as they are (stride <= 1024 / k, expect = 6 k stride: the sampled
+// values are maxima of the same disjoint row classes, rows 4 rq .. 4 rq + 3 of every 16 of a slice). Without the clamp the sample has at
+// most 256 slices for every Ng, so ngroups <= 4 streams x 256 x 4 values = TAU_DISTINCT_MAX with the filter and the stride never widens.
 inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false) {
   WidePlan p{};
   p.scan = scan;
@@ -2579,7 +2591,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
     // galleries overflow into the paging fallback: exact, slower.
     const int smax = group ? (1024 / k > 1 ? 1024 / k : 1) : (2048 / k > 1 ? 2048 / k : 1);
     if (p.s_stride > smax) p.s_stride = smax;
-    if (group && filter && scan) {
+    if (group && filter && scan && !i8) {
       // sim_tau_distinct sorts at most TAU_DISTINCT_MAX = 4096 sample values per query in LDS. With a filter the scan form's sample slices
       // walk <= 128 super-tiles (the label ring), so the slice count, and with it ngroups = 16 per slice, grows with Ng: beyond
       // 128 * 256 sample super-tiles the stride widens to keep 256 slices. That trades candidates for the bound: ~2.8 k * stride rows pass
@@ -2762,6 +2774,8 @@ int launch_topk(const float* Q, const TG* G, int Bq, int Ng, int C, int k, long 
 // takes the wide route's steps with the fp32 gallery's selection: sim_i8_scan<SAMPLE>, sim_tau_wide<float>, sim_i8_scan<APPEND>,
 // sim_final_wide<float> on the entry lists, and for an overflowed query sim_i8_repair (brute_force_by over the int8 scores).
 // cor_similarity_topk_i8_filtered takes the same steps with a label filter inside them (sim_i8_scan<.., FILTER>, sim_i8_repair_filtered).
+// cor_similarity_topk_i8_distinct takes them with the distinct route's sample rows, threshold and selection (sim_i8_scan<true, .., GROUP>,
+// sim_tau_distinct<float>, sim_final_distinct<float>, sim_i8_repair_distinct), with or without the filter.
 //
 // sim_i8_scan: v_mfma_i32_16x16x64_i8, gallery rows as the A operand, queries as B. A block is 8 waves; wave w keeps the fragments of ITS 64
 // queries (4 column blocks x C/64 K steps x 16 B per lane = 64 VGPRs at C = 256) for the whole slice, and all 8 waves share every 64-row
@@ -2782,6 +2796,7 @@ struct I8ScanArgs {
   unsigned* sg; int ngroups;
   const float* tau; int* cnt; uint2* lst; int cap;
   const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
+  int* sgrow;                                        // GROUP SAMPLE: the shard row behind every stored sample value
 };
 constexpr int I8_TILE_SLOTS = 64 * 17;                 // 64 rows x the largest stride
 // FULL: C = 256, every chunk and K step present (no tail tests in the loop). APPEND tests a cheap upper bound first: rounding is monotone and
@@ -2793,7 +2808,12 @@ constexpr int I8_TILE_SLOTS = 64 * 17;                 // 64 rows x the largest 
 // (it is >= every score of the four rows, allowed or not). SAMPLE keeps the group's four best allowed scores (sim_wide_scan's insertion;
 // sg[q * ngroups + stream * 4 + j], ngroups counts the four), and slice `split` walks the tiles split, split + nsplit, ...: the allowed rows
 // of a class-sorted gallery spread over every stream and every sample group.
-template <bool SAMPLE, bool FULL, bool FILTER = false>
+// GROUP (cor_similarity_topk_i8_distinct, SAMPLE only): every stored sample value travels with the ROW that produced it (a.sgrow, parallel
+// to sg): the lane-quarter group's maximum and its row, with FILTER its four best allowed scores and their rows through one insertion
+// network (sim_wide_scan's). Invariant: every sgrow entry written is a row in [0, Ng): a row is kept only behind `gr + e < Ng` (the ragged
+// last tile's rows beyond Ng never are), and a slot that no score reached holds (-inf, row 0); sim_tau_distinct dereferences only the
+// rows behind values above key(-inf).
+template <bool SAMPLE, bool FULL, bool FILTER = false, bool GROUP = false>
 __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict__ G, const I8ScanArgs a) {
 #pragma clang fp contract(off)
   __shared__ uint4 tile[2][I8_TILE_SLOTS];
@@ -2810,6 +2830,7 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
   int n[4];
   int ql[4];                                           // FILTER: the queries' labels (< 0: unrestricted)
   float top4[4][4];                                    // FILTER SAMPLE: the group's four best allowed scores, descending
+  int grow[4][GROUP && FILTER ? 4 : 1];                // GROUP SAMPLE: the rows behind gmax (FILTER: behind top4)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int q = q0 + 16 * j + c16;
@@ -2824,6 +2845,10 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
     tq[j] = SAMPLE ? 0.f : (active && q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
     gmax[j] = -INFINITY;
     n[j] = 0;
+    if constexpr (GROUP) {
+#pragma unroll
+      for (int i = 0; i < (FILTER ? 4 : 1); ++i) grow[j][i] = 0;
+    }
     if constexpr (FILTER) {
       ql[j] = active ? a.qlab[min(q, a.Bq - 1)] : -1;
 #pragma unroll
@@ -2907,7 +2932,36 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
       const float gsmax = fmaxf(fmaxf(gs[0], gs[1]), fmaxf(gs[2], gs[3]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if constexpr (SAMPLE && FILTER) {
+        if constexpr (SAMPLE && FILTER && GROUP) {
+          const i32x4 lab = __builtin_bit_cast(i32x4, buf_gs[16 + 4 * sub + rq]);
+          float s[4], smax = -INFINITY;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const bool ok = gr + e < Ng && (ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0)));
+            s[e] = ok ? ((float)acc[j][e] * qs[j]) * gs[e] : -INFINITY;
+            smax = fmaxf(smax, s[e]);
+          }
+          if (__builtin_amdgcn_ballot_w64(smax > top4[j][3]) != 0) {   // (a masked score is -inf: never > a slot, its row never kept)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if (s[e] > top4[j][3]) { top4[j][3] = s[e]; grow[j][3] = gr + e; }
+#pragma unroll
+              for (int i = 3; i > 0; --i) {
+                const float s0 = top4[j][i - 1], s1 = top4[j][i];
+                const int i0 = grow[j][i - 1], i1 = grow[j][i];
+                const bool up = s1 > s0;
+                top4[j][i - 1] = up ? s1 : s0; top4[j][i] = up ? s0 : s1;
+                grow[j][i - 1] = up ? i1 : i0; grow[j][i] = up ? i0 : i1;
+              }
+            }
+          }
+        } else if constexpr (SAMPLE && GROUP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float s = ((float)acc[j][e] * qs[j]) * gs[e];
+            if (gr + e < Ng && s > gmax[j]) { gmax[j] = s; grow[j][0] = gr + e; }
+          }
+        } else if constexpr (SAMPLE && FILTER) {
           const i32x4 lab = __builtin_bit_cast(i32x4, buf_gs[16 + 4 * sub + rq]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -2950,7 +3004,15 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
   for (int j = 0; j < 4; ++j) {
     const int q = q0 + 16 * j + c16;
     if (q < a.Bq) {
-      if constexpr (SAMPLE && FILTER)
+      if constexpr (SAMPLE && GROUP) {
+        if constexpr (FILTER) {
+          *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[j][0]), f2key(top4[j][1]), f2key(top4[j][2]), f2key(top4[j][3]));
+          *(i32x4*)(a.sgrow + (long)q * a.ngroups + stream * 4) = i32x4{grow[j][0], grow[j][1], grow[j][2], grow[j][3]};
+        } else {
+          a.sg[(long)q * a.ngroups + stream] = f2key(gmax[j]);
+          a.sgrow[(long)q * a.ngroups + stream] = grow[j][0];
+        }
+      } else if constexpr (SAMPLE && FILTER)
         *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[j][0]), f2key(top4[j][1]), f2key(top4[j][2]), f2key(top4[j][3]));
       else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax[j]);
       else a.cnt[(long)q * nstreams + stream] = n[j];
@@ -2962,6 +3024,22 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
 // the exact top-k by brute force over the int8 scores, one block of 256 threads per query; every other block leaves at once.
 // FILTER (sim_i8_repair_filtered, a kernel of its own so that the unfiltered one stays as compiled): only the rows allowed for the query
 // are ranked, and a query with at most k allowed rows gets them followed by the (-inf, -1) tail (brute_force_by<true>).
+// the int8 score of gallery row g against the quantised query qv (C bytes in LDS), scale qs: the definition, one row per call
+__device__ __forceinline__ float i8_score_at(const signed char* __restrict__ G, const float* __restrict__ gscale, const uint4* qv, float qs, int C,
+                                             int g) {
+#pragma clang fp contract(off)
+  const uint4* row = (const uint4*)(G + (long)g * C);
+  int d = 0;
+  for (int c = 0; c < C / 16; ++c) {
+    const uint4 x = row[c], y = qv[c];
+    const unsigned xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) d += (int)(signed char)(xw[i] >> (8 * b)) * (int)(signed char)(yw[i] >> (8 * b));
+  }
+  return ((float)d * qs) * gscale[g];
+}
 template <bool FILTER>
 __device__ __forceinline__ void i8_repair_body(const signed char* __restrict__ qq, const float* __restrict__ qscale,
                                                const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C, int k,
@@ -2977,19 +3055,7 @@ __device__ __forceinline__ void i8_repair_body(const signed char* __restrict__ q
   if (tid < C / 16) qv[tid] = *(const uint4*)(qq + (long)q * C + 16 * tid);
   __syncthreads();
   const float qs = qscale[q];
-  auto score_at = [&](int g) {
-    const uint4* row = (const uint4*)(G + (long)g * C);
-    int d = 0;
-    for (int c = 0; c < C / 16; ++c) {
-      const uint4 x = row[c], y = qv[c];
-      const unsigned xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) d += (int)(signed char)(xw[i] >> (8 * b)) * (int)(signed char)(yw[i] >> (8 * b));
-    }
-    return ((float)d * qs) * gscale[g];
-  };
+  auto score_at = [&](int g) { return i8_score_at(G, gscale, qv, qs, C, g); };
   if constexpr (FILTER) {
     const int ql = qlab[q];
     brute_force_by<true>(score_at, [&](int g) { return ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
@@ -3010,10 +3076,39 @@ __global__ void __launch_bounds__(256) sim_i8_repair_filtered(const signed char*
   i8_repair_body<true>(qq, qscale, G, gscale, Ng, C, k, g_offset, out_s, out_i, rlab, qlab, ne);
 }
 
+// Overflowed queries of the int8 distinct route (sim_final_distinct<float> ran with the marker on): the paging fallback of the distinct
+// route (distinct_brute_force_by) over the int8 scores of the allowed rows; rlab == nullptr: unfiltered. One block of 256 threads per
+// query, every other block leaves at once. Static LDS: sl_s / sl_i / flag [SLW] 24 KiB, keys and k2 [SLW] 32 KiB, the found-group table
+// and the histogram 1 KiB each, the query 256 B: 58.3 KiB.
+__global__ void __launch_bounds__(256) sim_i8_repair_distinct(const signed char* __restrict__ qq, const float* __restrict__ qscale,
+                                                              const signed char* __restrict__ G, const float* __restrict__ gscale, int Ng, int C,
+                                                              int k, long long g_offset, const int* __restrict__ grp, float* out_s, long long* out_i,
+                                                              const int* __restrict__ rlab, const int* __restrict__ qlab, int ne) {
+#pragma clang fp contract(off)
+  __shared__ float sl_s[SLW];
+  __shared__ int sl_i[SLW], flag[SLW], hist[256];
+  __shared__ unsigned long long keys[SLW], k2[SLW];
+  __shared__ unsigned found[COR_TOPK_KMAX];
+  __shared__ uint4 qv[16];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (out_i[(long)q * k] != -2LL) return;              // block-uniform: read before any thread of the block writes
+  if (tid < C / 16) qv[tid] = *(const uint4*)(qq + (long)q * C + 16 * tid);
+  __syncthreads();
+  const float qs = qscale[q];
+  const int ql = rlab ? qlab[q] : -1;
+  distinct_brute_force_by([&](int g) { return i8_score_at(G, gscale, qv, qs, C, g); },
+                          [&](int g) { return ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, grp, sl_s, sl_i, flag, keys, k2, found,
+                          hist, out_s + (long)q * k, out_i + (long)q * k);
+}
+
 // FILTER: cor_similarity_topk_i8_filtered, the same steps with the filter inside them (c.rlab / c.qlab / c.ne).
-template <bool FILTER>
+// GROUP: cor_similarity_topk_i8_distinct (c.grp): the distinct route's three changes. The SAMPLE scan keeps the rows behind its values
+// (sgrow), tau_q is sim_tau_distinct<float> (delta = 0), the APPEND scan is the unchanged <false, FULL, FILTER> instantiation (it appends
+// scores >= tau_q whatever the groups are), the selection is sim_final_distinct<float> over the entry lists (delta = 0: nothing is
+// re-scored, G is never dereferenced) and marked queries go to sim_i8_repair_distinct.
+template <bool FILTER, bool GROUP = false>
 int launch_topk_i8(const signed char* Gq, const WideCall& c) {
-  const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, FILTER, false, true);
+  const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, FILTER, GROUP, true);
   signed char* qq = (signed char*)(c.w + p.off_img); float* qscale = (float*)(c.w + p.off_dq);
   if (const int e = cor_quantize_rows_i8(c.Q, COR_F32, c.Bq, c.C, qq, qscale, c.s)) return e;
   I8ScanArgs a{};
@@ -3022,11 +3117,12 @@ int launch_topk_i8(const signed char* Gq, const WideCall& c) {
   a.rlab = c.rlab; a.qlab = c.qlab; a.ne = c.ne;
   if (p.ngroups > 0) {
     a.nsplit = p.s_nsplit; a.tiles_per_split = p.s_tiles_per_split; a.ntiles = p.s_tiles; a.tile_stride = p.s_stride;
-    if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<true, true, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
-    else hipLaunchKernelGGL((sim_i8_scan<true, false, FILTER>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    if constexpr (GROUP) a.sgrow = (int*)(c.w + p.off_sgrow);
+    if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<true, true, FILTER, GROUP>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
+    else hipLaunchKernelGGL((sim_i8_scan<true, false, FILTER, GROUP>), dim3(p.nqg * p.s_nsplit), dim3(512), 0, c.s, Gq, a);
     COR_CHECK_LAUNCH();
   }
-  if (const int e = launch_wide_tau<float, false>(c, p)) return e;
+  if (const int e = launch_wide_tau<float, GROUP>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.tau = (const float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.lst = (uint2*)(c.w + p.off_recs); a.cap = p.cap;
   if (c.C == 256) hipLaunchKernelGGL((sim_i8_scan<false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), 0, c.s, Gq, a);
@@ -3036,9 +3132,12 @@ int launch_topk_i8(const signed char* Gq, const WideCall& c) {
   // the (absent) float rows
   WideCall sel = c;
   sel.flags |= COR_TOPK_NO_FALLBACK;
-  if (const int e = launch_wide_final<float, false, false, false>((const float*)nullptr, sel, p)) return e;
+  if (const int e = launch_wide_final<float, false, false, GROUP>((const float*)nullptr, sel, p)) return e;
   if (!(c.flags & COR_TOPK_NO_FALLBACK)) {
-    if constexpr (FILTER)
+    if constexpr (GROUP)
+      hipLaunchKernelGGL(sim_i8_repair_distinct, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.grp, c.out_s,
+                         c.out_i, c.rlab, c.qlab, c.ne);
+    else if constexpr (FILTER)
       hipLaunchKernelGGL(sim_i8_repair_filtered, dim3(c.Bq), dim3(256), 0, c.s, qq, qscale, Gq, c.gscale, c.Ng, c.C, c.k, c.g_offset, c.out_s, c.out_i,
                          c.rlab, c.qlab, c.ne);
     else
@@ -3059,27 +3158,43 @@ inline long wide_bytes(int Bq, int Ng, int k, bool filter, bool group) { return 
 inline int distinct_sample_values(int Bq, int Ng, int k) {
   return (int)std::max(wide_max(Bq, Ng, k, false, true, &WidePlan::ngroups), wide_max(Bq, Ng, k, true, true, &WidePlan::ngroups));
 }
+// the same for an int8 distinct call (one form; the filtered plan has the most)
+inline int i8_distinct_sample_values(int Bq, int Ng, int k) {
+  return std::max(make_wide(Bq, Ng, k, true, false, true, true).ngroups, make_wide(Bq, Ng, k, true, true, true, true).ngroups);
+}
+// Its workspace. A plan depends on Bq through the number of 512-query groups only (more groups: fewer slices, fewer streams), and within
+// one group count every buffer grows with Bq; the maximum over the smaller group counts makes the size monotone in Bq, so a workspace
+// sized for the largest batch serves every smaller one. Beyond device_cus() groups every plan has one slice: nothing more to look at.
+inline long i8_distinct_bytes(int Bq, int Ng, int k) {
+  auto at = [&](int b) { return (long)std::max(make_wide(b, Ng, k, true, false, true, true).bytes, make_wide(b, Ng, k, true, true, true, true).bytes); };
+  long m = at(Bq);
+  const int top = std::min(cdiv(Bq, 512) - 1, device_cus() + 1);
+  for (int g = 1; g <= top; ++g) m = std::max(m, at(512 * g));
+  return m;
+}
 inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
 
 constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
-enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED };
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED, ROUTE_I8_DISTINCT };
 
 // The argument checks of the search entry points, in the order (and with the codes) of the ABI. What differs by route: the
 // pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither; int8: the row scales, and
-// filtered int8 both label vectors as well), the A/B flags it refuses
-// (the plain call only at k > 32) and the distinct route's sample bound.
+// filtered int8 both label vectors as well, distinct int8 the group ids and the labels both or neither), the A/B flags it refuses
+// (the plain call only at k > 32) and the distinct routes' sample bound.
 int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
   const bool own_ptrs = route == ROUTE_TOPK       ? true
                         : route == ROUTE_I8       ? c.gscale != nullptr
                         : route == ROUTE_I8_FILTERED ? c.gscale && c.rlab && c.qlab
+                        : route == ROUTE_I8_DISTINCT ? c.gscale && c.grp && (c.rlab == nullptr) == (c.qlab == nullptr)
                         : route == ROUTE_FILTERED ? c.rlab && c.qlab
                                                   : c.grp && (c.rlab == nullptr) == (c.qlab == nullptr);
   if (!c.Q || !G || !own_ptrs || !c.out_s || !c.out_i || !c.w || c.Bq <= 0 || c.Ng <= 0 || c.k <= 0) return COR_EINVAL;
   if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
   if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
   if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
-  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED) && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
+  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED || route == ROUTE_I8_DISTINCT) && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
   if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
+  if (route == ROUTE_I8_DISTINCT && i8_distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;
   if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab | (uintptr_t)c.gscale) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
   return 0;
 }
@@ -3173,4 +3288,24 @@ extern "C" int cor_similarity_topk_i8_filtered(const float* Q, const signed char
                    (char*)workspace, flags, (hipStream_t)stream, gscale};
   if (const int e = check_topk_call(ROUTE_I8_FILTERED, c, Gq, filter_mode)) return e;
   return launch_topk_i8<true>(Gq, c);
+}
+
+extern "C" long cor_topk_i8_distinct_workspace_bytes(int Bq, int Ng, int k) {
+  return topk_shape_ok(Bq, Ng, k) ? i8_distinct_bytes(Bq, Ng, k) : COR_EINVAL;
+}
+
+extern "C" int cor_topk_i8_distinct_sample_values(int Bq, int Ng, int k) {
+  return topk_shape_ok(Bq, Ng, k) ? i8_distinct_sample_values(Bq, Ng, k) : COR_EINVAL;
+}
+
+// distinct int8 calls: the int8 route with the distinct route's sample rows, threshold, selection and repair (launch_topk_i8<.., true>);
+// the labels are optional: both or neither
+extern "C" int cor_similarity_topk_i8_distinct(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k,
+                                               long long g_offset, const int* row_groups, const int* row_labels, const int* query_labels,
+                                               int filter_mode, float* out_scores, long long* out_idx, void* workspace, int flags, void* stream) {
+  const bool filter = row_labels != nullptr;
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, row_groups, row_labels, query_labels, filter && filter_mode == COR_FILTER_NE ? 1 : 0, out_scores,
+                   out_idx, (char*)workspace, flags, (hipStream_t)stream, gscale};
+  if (const int e = check_topk_call(ROUTE_I8_DISTINCT, c, Gq, filter_mode)) return e;
+  return filter ? launch_topk_i8<true, true>(Gq, c) : launch_topk_i8<false, true>(Gq, c);
 }

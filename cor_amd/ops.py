@@ -568,7 +568,7 @@ def quantize_rows_i8(X):
 
 
 def _i8_front(who, Q, Gq, gscale, k, flags, mode="eq"):
-    """The checks the two int8 searches share, before anything touches the device. Returns (Bq, Ng, C, gscale as the scan reads it)."""
+    """The checks the int8 searches share, before anything touches the device. Returns (Bq, Ng, C, gscale as the scan reads it)."""
     if Gq.dtype != torch.int8:
         raise ValueError(f"{who}: Gq must be int8 rows (ops.quantize_rows_i8), got {Gq.dtype}")
     if gscale.dtype != torch.float32 or gscale.dim() != 1 or Gq.dim() != 2 or gscale.shape[0] != Gq.shape[0]:
@@ -613,6 +613,35 @@ def similarity_topk_i8_filtered(Q, Gq, gscale, k, row_labels, query_labels, mode
     nat.check(_lib().cor_similarity_topk_i8_filtered(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, k, int(g_offset), rl.data_ptr(),
                                                      qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(),
                                                      int(flags), _s()), "cor_similarity_topk_i8_filtered")
+    return scores, idx
+
+
+def similarity_topk_i8_distinct(Q, Gq, gscale, k, row_groups, row_labels=None, query_labels=None, mode="eq", g_offset=0, flags=0):
+    """Top-k DISTINCT groups of an int8 gallery: the score and order of similarity_topk_i8, the groups and allowed rows of
+    similarity_topk_distinct. row_groups int32[Ng] (a negative id: a group of its own); per query, a group's representative is its first
+    allowed row by (score key desc, index asc) and the result is the k best representatives in that order: scores f32[Bq,k], idx
+    i64[Bq,k] (global ROW ids, no group twice; fewer than k groups: the (-inf, -1) tail). row_labels / query_labels / mode: the optional
+    filter (both or neither; may be the group tensor itself, e.g. mode "ne" with the query's own image id). int64 ids are converted, a
+    misaligned view is realigned. Bit-identical to tests/i8_distinct_refs.py, scores and indices. One route for every k; an overflowed
+    query is ranked on the device. No host synchronisation when the vectors already live on the device. flags: 0 or
+    nat.TOPK_NO_FALLBACK."""
+    who = "similarity_topk_i8_distinct"
+    if (row_labels is None) != (query_labels is None):
+        raise ValueError(f"{who}: row_labels and query_labels go together (both or neither)")
+    if Gq.dim() == 2 and Q.dim() == 2:                        # the id checks raise before anything touches the device
+        _label_vec(row_groups, Gq.shape[0], "row_groups", who)
+        if row_labels is not None:
+            _label_vec(row_labels, Gq.shape[0], "row_labels", who)
+            _label_vec(query_labels, Q.shape[0], "query_labels", who)
+    Bq, Ng, C, gscale = _i8_front(who, Q, Gq, gscale, k, flags, mode)
+    rg = _labels(row_groups, Ng, "row_groups", Q.device, who)
+    rl = _labels(row_labels, Ng, "row_labels", Q.device, who) if row_labels is not None else None
+    qlab = _labels(query_labels, Bq, "query_labels", Q.device, who) if query_labels is not None else None
+    ws, scores, idx = _topk_buffers("cor_topk_i8_distinct_workspace_bytes", Q, Bq, Ng, k)
+    nat.check(_lib().cor_similarity_topk_i8_distinct(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, k, int(g_offset), rg.data_ptr(),
+                                                     rl.data_ptr() if rl is not None else None, qlab.data_ptr() if qlab is not None else None,
+                                                     _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), int(flags), _s()),
+              "cor_similarity_topk_i8_distinct")
     return scores, idx
 
 

@@ -330,9 +330,9 @@ class GalleryShard:
 
     def quantized(self):
         """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
-        coarse stage of two_stage_search over these rows. This shard is left untouched. The labels are carried (the same tensor, nothing is
-        copied), so the copy takes the filtered searches this shard takes; groups are not (distinct int8 searches do not exist)."""
-        return QuantizedShard.from_rows(self.rows, offset=self.offset, labels=self.labels)
+        coarse stage of two_stage_search over these rows. This shard is left untouched. The labels and the group ids are carried (the same
+        tensors, nothing is copied), so the copy takes the filtered and the distinct searches this shard takes."""
+        return QuantizedShard.from_rows(self.rows, offset=self.offset, labels=self.labels, groups=self.groups)
 
 
 class QuantizedShard:
@@ -342,13 +342,18 @@ class QuantizedShard:
     GallerySet, `neighbours` of GalleryShard.augmented / neighbour_graph (search only; `augmented` also expands over its neighbours and
     needs real rows there), the `shard` of distributed_search.
     labels (int32[n], one per row): the shard also takes the filtered searches of a GalleryShard (ops.similarity_topk_i8_filtered).
-    Distinct-group int8 searches do not exist: `groups` is always None."""
+    groups (int32[n], one group id per row, typically the source image id; negative: a group of its own): it also takes the distinct
+    searches (ops.similarity_topk_i8_distinct), with or without the filter. Without them `groups` is None."""
 
-    def __init__(self, rows_i8: torch.Tensor, scales: torch.Tensor, offset: int = 0, labels=None):
+    def __init__(self, rows_i8: torch.Tensor, scales: torch.Tensor, offset: int = 0, labels=None, groups=None):
         if labels is not None:
             labels = torch.as_tensor(labels)
             if labels.dim() != 1 or rows_i8.dim() != 2 or labels.shape[0] != rows_i8.shape[0]:
                 raise ValueError(f"QuantizedShard: {tuple(labels.shape)} labels for rows {tuple(rows_i8.shape)}")
+        if groups is not None:
+            groups = torch.as_tensor(groups)
+            if groups.dim() != 1 or rows_i8.dim() != 2 or groups.shape[0] != rows_i8.shape[0]:
+                raise ValueError(f"QuantizedShard: {tuple(groups.shape)} group ids for rows {tuple(rows_i8.shape)}")
         if not rows_i8.is_cuda or not scales.is_cuda:
             raise RuntimeError("QuantizedShard lives in GPU memory (no CPU path)")
         if rows_i8.dtype != torch.int8 or rows_i8.dim() != 2:
@@ -359,19 +364,20 @@ class QuantizedShard:
         self.scales = scales.to(self.rows.device).contiguous()
         self.offset = int(offset)
         self.labels = None if labels is None else _row_ids(labels, "labels", self.rows.shape[0], self.rows.device)
-        self.groups = None
+        self.groups = None if groups is None else _row_ids(groups, "group ids", self.rows.shape[0], self.rows.device)
 
     @classmethod
-    def from_rows(cls, rows: torch.Tensor, offset: int = 0, labels=None):
-        """Quantise fp32 / bf16 / fp16 rows [n, C] on their device; `rows` is left untouched. labels: as the constructor takes them."""
+    def from_rows(cls, rows: torch.Tensor, offset: int = 0, labels=None, groups=None):
+        """Quantise fp32 / bf16 / fp16 rows [n, C] on their device; `rows` is left untouched. labels, groups: as the constructor takes
+        them."""
         if not rows.is_cuda:
             raise RuntimeError("QuantizedShard lives in GPU memory (no CPU path)")
         if rows.shape[0] == 0:
             return cls(torch.empty(rows.shape, dtype=torch.int8, device=rows.device), torch.empty((0,), dtype=torch.float32, device=rows.device), offset,
-                       labels)
+                       labels, groups)
         with torch.cuda.device(rows.device):
             q, scale = ops.quantize_rows_i8(rows)
-        return cls(q, scale, offset, labels)
+        return cls(q, scale, offset, labels, groups)
 
     def __len__(self):
         return self.rows.shape[0]
@@ -379,10 +385,11 @@ class QuantizedShard:
     def search(self, queries: torch.Tensor, k: int, query_labels=None, mode: str = "eq", distinct: bool = False):
         """queries f32[Bq,C] -> (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU, the int8 scores of ops.similarity_topk_i8;
         1 <= k <= 256. query_labels (int32[Bq], < 0 = unrestricted): only the rows allowed by the shard's labels and `mode` ("eq": same
-        label, "ne": another label) are ranked (ops.similarity_topk_i8_filtered); ValueError if the shard has no labels. Distinct int8
-        searches do not exist: distinct=True raises ValueError."""
-        if distinct:
-            raise ValueError("QuantizedShard.search: an int8 shard has no distinct search")
+        label, "ne": another label) are ranked (ops.similarity_topk_i8_filtered); ValueError if the shard has no labels.
+        distinct: one row per group id of the shard's `groups`, the k best groups (ops.similarity_topk_i8_distinct), with or without the
+        filter; idx still names the winning ROW of each group. ValueError if the shard has no group ids."""
+        if distinct and self.groups is None:
+            raise ValueError("QuantizedShard.search: distinct=True but the shard has no group ids")
         if query_labels is not None and self.labels is None:
             raise ValueError("QuantizedShard.search: query_labels given but the shard has no row labels")
         q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
@@ -390,7 +397,10 @@ class QuantizedShard:
             query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
         if self.rows.shape[0] == 0:                  # an empty shard: all-missing lists, like Ng < k
             return _missing_lists(q.shape[0], k, q.device)
-        with torch.cuda.device(self.rows.device):
+        with _on(self.rows.device):
+            if distinct:
+                return ops.similarity_topk_i8_distinct(q, self.rows, self.scales, k, self.groups, None if query_labels is None else self.labels,
+                                                       query_labels, mode=mode, g_offset=self.offset)
             if query_labels is None:
                 return ops.similarity_topk_i8(q, self.rows, self.scales, k, g_offset=self.offset)
             return ops.similarity_topk_i8_filtered(q, self.rows, self.scales, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
@@ -967,5 +977,6 @@ def load_gallery_shard(path, rank, device):
     labels = torch.load(sh["labels_file"]) if man.get("labels") else None
     groups = torch.load(sh["groups_file"]) if man.get("groups") else None
     if man.get("scales"):
-        return QuantizedShard(torch.load(sh["file"]).to(device), torch.load(sh["scales_file"]).to(device), offset=sh["lo"], labels=labels)
+        return QuantizedShard(torch.load(sh["file"]).to(device), torch.load(sh["scales_file"]).to(device), offset=sh["lo"], labels=labels,
+                              groups=groups)
     return GalleryShard(torch.load(sh["file"]).to(device), offset=sh["lo"], labels=labels, groups=groups)

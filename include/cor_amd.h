@@ -423,10 +423,45 @@ int cor_similarity_topk_i8(const float* Q, const signed char* Gq, const float* g
  * queries in registers. The sample keeps the four best allowed scores per group and the scan slices walk the gallery interleaved (slice s
  * takes tiles s, s + nsplit, ...), so a selective filter keeps its threshold and a class-sorted gallery does not crowd a few candidate
  * streams. An overflowed query is ranked over its allowed rows by the brute force over the int8 scores; with COR_TOPK_NO_FALLBACK it
- * carries index -2 in every slot instead. Distinct-group int8 search does not exist. */
+ * carries index -2 in every slot instead. */
 long cor_topk_i8_filtered_workspace_bytes(int Bq, int Ng, int k);
 int cor_similarity_topk_i8_filtered(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k,
                                     long long g_offset, const int* row_labels, const int* query_labels, int filter_mode,
+                                    float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
+
+/* Distinct-group int8 search (cor_similarity_topk_i8_distinct): the best row of each of the k best groups of an int8 gallery.
+ * SCORE and ORDER are exactly those of cor_similarity_topk_i8: d = the int32 dot product of the quantised query and the row,
+ * score = ((float)d * qscale) * gscale, ranked by the order-preserving key of the score's bits descending (+0.0 above -0.0), then row
+ * index ascending. ALLOWED rows are exactly those of cor_similarity_topk_distinct: every row when row_labels and query_labels are both
+ * NULL; both given: the COR_FILTER_EQ / COR_FILTER_NE rule of cor_similarity_topk_filtered (query_labels[b] < 0: unrestricted); exactly
+ * one NULL: COR_EINVAL. Filter labels and group ids are separate vectors and may be the same memory.
+ * GROUPS: row_groups i32 [Ng] (shard-local row g; 16-byte aligned); a negative id makes the row a group of its own. Per query, among its
+ * allowed rows, a group's representative is its first row in the ORDER above, and the result is the k best representatives in that
+ * order: out_scores f32 [Bq,k], out_idx i64 [Bq,k] = the representative ROWS (+ g_offset), so no group appears twice. Fewer than k groups
+ * with an allowed row: those first, then the (-inf, -1) tail; no allowed row: only the tail. The result is bit-identical, scores and
+ * indices, to "rank the allowed rows by the int8 definition, keep the first row of each group, keep the first k" evaluated on the CPU
+ * (tests/i8_distinct_refs.py).
+ * Other arguments as for cor_similarity_topk_i8; workspace (256-byte aligned) >= cor_topk_i8_distinct_workspace_bytes(Bq, Ng, k), which
+ * covers the call with or without labels and never shrinks when Bq grows (size it once for the largest batch). Checks in
+ * the order and with the codes of cor_similarity_topk_i8_filtered: null Q / Gq / gscale / row_groups / outputs / workspace, Bq / Ng / k
+ * <= 0 or exactly one label pointer null: COR_EINVAL; filter_mode neither COR_FILTER_EQ nor COR_FILTER_NE (also when unfiltered):
+ * COR_EINVAL; k > COR_TOPK_KMAX, C > 256 or C % 16: COR_ENOSUPPORT; a flag other than COR_TOPK_NO_FALLBACK: COR_ENOSUPPORT; Q, Gq, gscale,
+ * row_groups or row_labels not 16-byte aligned, workspace not 256-byte aligned: COR_EINVAL. No allocation, no host synchronisation: the
+ * call can be captured in a graph.
+ * Route: the int8 route's steps with the distinct route's three changes. The sample scan keeps the ROW behind every sampled value (the
+ * lane-quarter group's maximum, with a filter its four best allowed scores); the threshold kernel of cor_similarity_topk_distinct
+ * reduces the sampled values to one per group id before it takes the k-th (delta = 0); the append scan is that of the plain / filtered
+ * int8 call unchanged; one block per query reduces the candidates to one per group, finds the exact k-th group, sorts every candidate at
+ * or above it and keeps the first row of each group (nothing is re-scored: the scan's score is the score). An overflowed query is ranked
+ * on the device by the paging fallback of cor_similarity_topk_distinct over the int8 scores (its cost note applies: Ng^2 / 410 row
+ * scores for a shard with fewer than k allowed groups); with COR_TOPK_NO_FALLBACK it carries index -2 in every slot instead.
+ * cor_topk_i8_distinct_sample_values: the most sample values per query a plan of this call shape hands the threshold kernel; at most
+ * 4096 for every Ng (4 streams x <= 256 sample slices x 4 values with a filter), and a plan beyond it would be refused with
+ * COR_ENOSUPPORT. */
+long cor_topk_i8_distinct_workspace_bytes(int Bq, int Ng, int k);
+int cor_topk_i8_distinct_sample_values(int Bq, int Ng, int k);
+int cor_similarity_topk_i8_distinct(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, int k,
+                                    long long g_offset, const int* row_groups, const int* row_labels, const int* query_labels, int filter_mode,
                                     float* out_scores, long long* out_idx, void* workspace, int flags, void* stream);
 
 /* Merge of top-k lists on the device: per query b, P lists of kin entries (what P calls of cor_similarity_topk[_filtered|_distinct] over P
