@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COR_AMD_LIB") or os.path.join(_HERE, "csrc", "libcor_amd.so")   # COR_AMD_LIB: another build of the SAME ABI (same-box A/B runs of tools/)
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3    # BF16X3: x3 split rows (exact-query mode, include/cor_amd.h)
+I8 = 4    # int8 rows with one fp32 scale per row (COR_I8): accepted only where include/cor_amd.h says so
 ACT_NONE, ACT_GELU_ERF, ACT_RELU, ACT_SIGMOID, ACT_GELU_TANH = 0, 1, 2, 3, 4
 EINVAL, ENOSUPPORT = -1, -2
 TOPK_FORCE_LISTS, TOPK_NO_FALLBACK, TOPK_FORCE_GLOBAL_THRESHOLD, TOPK_WAVE_FINAL = 1, 2, 8, 16
@@ -86,13 +87,18 @@ SIGNATURES = {
     "cor_rescore_workspace_bytes": [_i, _i, _i],
     "cor_rescore_topk": [_p, _p, _i, _i, _i, _i, _ll, _p, _i, _i, _p, _p, _p, _p, _p],
     "cor_expand_queries": [_p, _f, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p],
+    "cor_dequantize_rows_i8": [_p, _p, _i, _i, _p, _i, _p],
+    "cor_rescore_i8_workspace_bytes": [_i, _i, _i],
+    "cor_rescore_topk_i8": [_p, _p, _p, _i, _i, _i, _ll, _p, _i, _i, _p, _p, _p, _p, _p],
+    "cor_expand_queries_sq": [_p, _f, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p],
     "cor_knn_reciprocal": [_p, _p, _p, _i, _i, _i, _p, _p],
     "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,
             "cor_topk_i8_distinct_workspace_bytes": _l,
-            "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l}
+            "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l,
+            "cor_rescore_i8_workspace_bytes": _l}
 
 _lib = None
 

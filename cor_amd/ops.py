@@ -567,6 +567,36 @@ def quantize_rows_i8(X):
     return q, scale
 
 
+def dequantize_rows_i8(q, scale, out_dtype=torch.float32, out=None):
+    """The way back from quantize_rows_i8 (cor_dequantize_rows_i8): q int8 [n,C], scale f32 [n] -> X [n,C] in out_dtype on the GPU,
+    x = float(q) * scale[row], ONE rounded fp32 multiply, stored as float32 or rounded again (nearest even) to bfloat16 / float16 (what
+    .to(dtype) of the fp32 result gives). C % 16 == 0, C <= 256. out: an optional contiguous [n,C] tensor of out_dtype to write into.
+    No host synchronisation; capturable in a graph."""
+    if q.dim() != 2 or q.dtype != torch.int8:
+        raise ValueError(f"dequantize_rows_i8: q must be int8 [n, C], got {q.dtype} {tuple(q.shape)}")
+    n, C = q.shape
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != n:
+        raise ValueError(f"dequantize_rows_i8: scale must be float32 [{n}], got {scale.dtype} {tuple(scale.shape)}")
+    if C < 16 or C > 256 or C % 16:
+        raise ValueError(f"dequantize_rows_i8: C must be a multiple of 16 up to 256, got {C}")
+    if out_dtype not in _DT:
+        raise ValueError(f"dequantize_rows_i8: out_dtype must be float32 / bfloat16 / float16, got {out_dtype}")
+    if out is not None and (out.shape != (n, C) or out.dtype != out_dtype or not out.is_contiguous()):
+        raise ValueError(f"dequantize_rows_i8: out must be a contiguous {out_dtype} [{n}, {C}] tensor")
+    dev = _dev(q, scale, out)
+    q, scale = q.contiguous(), scale.contiguous()
+    if q.data_ptr() % 16:                                     # a view into a larger tensor: the kernel loads 16 B at a time
+        q = q.clone()
+    dst = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty((n, C), dtype=out_dtype, device=dev)
+    if n:                                                     # (no rows: empty tensors have no address to pass)
+        nat.check(_lib().cor_dequantize_rows_i8(q.data_ptr(), scale.data_ptr(), n, C, dst.data_ptr(), _DT[out_dtype], _s()),
+                  "cor_dequantize_rows_i8")
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        dst = out
+    return dst
+
+
 def _i8_front(who, Q, Gq, gscale, k, flags, mode="eq"):
     """The checks the int8 searches share, before anything touches the device. Returns (Bq, Ng, C, gscale as the scan reads it)."""
     if Gq.dtype != torch.int8:
@@ -740,17 +770,60 @@ def rescore_topk(Q, G, cand, k, g_offset=0, return_pos=False):
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
+def rescore_topk_i8(Q, Gq, gscale, cand, k, g_offset=0, return_pos=False):
+    """rescore_topk over an int8 shard (cor_rescore_topk_i8): Q f32 [Bq,C]; Gq int8 [Ng,C] and gscale f32 [Ng] as quantize_rows_i8 returns
+    them (the rows with global ids [g_offset, g_offset + Ng)); cand i64 [Bq,kin] global row ids -> (scores f32[Bq,k], idx i64[Bq,k]) ordered
+    by (score desc, id asc), and with return_pos a third tensor pos i32[Bq,k]. The PRESENT / MISSING rule, the first occurrence per id and
+    the (-inf, -1, -1) tail are rescore_topk's; the score is similarity_topk_i8's (the query is quantised inside the call, score =
+    ((float)(int32 dot) * qscale) * gscale), so the list an int8 search returned comes back bitwise (one exception: a list holding both
+    +0.0 and -0.0 scores, where this call lets the id decide; include/cor_amd.h). Bit-identical to tests/i8_list_refs.py.
+    1 <= k <= 256, 1 <= kin <= nat.MERGE_NMAX (4096; beyond that NativeError), C <= 256 and C % 16 == 0. No host synchronisation."""
+    who = "rescore_topk_i8"
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if Q.dim() != 2 or Gq.dim() != 2 or Q.shape[1] != Gq.shape[1]:
+        raise ValueError(f"{who}: Q must be [Bq, C] and Gq [Ng, C], got {tuple(Q.shape)} and {tuple(Gq.shape)}")
+    if Q.dtype != torch.float32:
+        raise ValueError(f"{who}: Q must be float32, got {Q.dtype}")
+    if Q.shape[1] < 16 or Q.shape[1] > 256 or Q.shape[1] % 16:
+        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {Q.shape[1]}")
+    if cand.dim() != 2 or cand.shape[0] != Q.shape[0] or cand.shape[1] < 1 or cand.dtype != torch.int64:
+        raise ValueError(f"{who}: cand must be int64 [{Q.shape[0]}, kin] with kin >= 1, got {cand.dtype} {tuple(cand.shape)}")
+    Q, Gq = Q.contiguous(), Gq.contiguous()
+    if Q.data_ptr() % 16:                                     # a view into a larger tensor: the kernel loads 16 B at a time
+        Q = Q.clone()
+    if Gq.data_ptr() % 16:
+        Gq = Gq.clone()
+    Bq, Ng, C, gscale = _i8_front(who, Q, Gq, gscale, k, 0)
+    _dev(Q, cand)
+    cand, kin = cand.contiguous(), cand.shape[1]
+    lib = _lib()
+    nbytes = lib.cor_rescore_i8_workspace_bytes(Bq, kin, k)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_rescore_i8_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=Q.device) if nbytes else None
+    out_s, out_i, out_p = _list_outputs(Bq, k, Q.device, return_pos, missing=Ng == 0)
+    if Bq and Ng:                                             # (no queries / no rows: empty tensors have no address to pass)
+        nat.check(lib.cor_rescore_topk_i8(Q.data_ptr(), Gq.data_ptr(), gscale.data_ptr(), Bq, Ng, C, int(g_offset), cand.data_ptr(), kin, k,
+                                          out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _p(ws) or None, _s()), "cor_rescore_topk_i8")
+    return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
+
+
 def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, normalize=True, out_dtype=torch.float32, out=None):
     """Query expansion on the device (cor_expand_queries; AQE / alpha-QE, and with query_weight = 0 over gallery rows: DBA).
     Q f32 [Bq,C] (None is allowed when query_weight == 0), segments a list of (rows, offset): rows [n,C] fp32 / bf16 / fp16 holding the
-    global ids [offset, offset + n), at most nat.EXPAND_SEGMAX (16) of them, pairwise disjoint, dtypes free to differ; scores f32
+    global ids [offset, offset + n), or of (rows_i8, scales, offset): int8 rows with their f32 [n] row scales as quantize_rows_i8 returns
+    them, whose value is float(q) * scale, one rounded multiply (with such a segment the call is cor_expand_queries_sq, without one it
+    is cor_expand_queries exactly as before); at most nat.EXPAND_SEGMAX (16) of them, pairwise disjoint, dtypes free to differ; scores f32
     [Bq,kin] and idx i64 [Bq,kin] as a search, the merge or the re-scoring return them -> [Bq,C] in out_dtype:
     v = query_weight * Q; for j < m in list order, if idx[b,j] lies in a segment: v += max(scores[b,j], +0)^alpha * row; then
     v / max(|v|, 1e-12) if normalize. Every step is one separately rounded fp32 operation in a fixed order (include/cor_amd.h has the
     definition to the bit), so the result does not depend on how the rows are cut into segments. An id of no segment (-1, another
     shard's, any 64-bit value) contributes nothing and its score is not read. 1 <= m <= min(kin, 256), 0 <= alpha <= 8, C <= 256 and
     C % 16 == 0. out: an optional contiguous [Bq,C] tensor of out_dtype to write into. No host synchronisation; capturable in a graph."""
-    segments = [(r, int(o)) for r, o in segments]
+    segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
+    if any(len(seg) not in (2, 3) for seg in segments):
+        raise ValueError("expand_queries: a segment is (rows, offset) or (rows_i8, scales, offset)")
     if len(segments) > nat.EXPAND_SEGMAX:
         raise ValueError(f"expand_queries: {len(segments)} segments, one call reads at most {nat.EXPAND_SEGMAX}")
     Bq, kin = _list_front("expand_queries", scores, idx)
@@ -770,20 +843,36 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
         raise ValueError(f"expand_queries: the width must be a multiple of 16 up to 256, got {C}")
     if out_dtype not in _DT:
         raise ValueError(f"expand_queries: out_dtype must be float32 / bfloat16 / float16, got {out_dtype}")
-    for r, o in segments:
-        if r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
+    for seg in segments:
+        r = seg[0]
+        if len(seg) == 3:
+            if r.dim() != 2 or r.shape[1] != C or r.dtype != torch.int8 or r.shape[0] >= 2 ** 31:
+                raise ValueError(f"expand_queries: a segment with scales must be int8 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+            if seg[1].dtype != torch.float32 or seg[1].dim() != 1 or seg[1].shape[0] != r.shape[0]:
+                raise ValueError(f"expand_queries: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
+        elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
             raise ValueError(f"expand_queries: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
     _disjoint_spans("expand_queries", segments)
     if out is not None and (out.shape != (Bq, C) or out.dtype != out_dtype or not out.is_contiguous()):
         raise ValueError(f"expand_queries: out must be a contiguous {out_dtype} [{Bq}, {C}] tensor")
-    dev = _dev(Q, scores, idx, out, *[r for r, _ in segments])
+    dev = _dev(Q, scores, idx, out, *[t for seg in segments for t in seg[:-1]])
     Q = Q.contiguous() if Q is not None else None
     scores, idx = scores.contiguous(), idx.contiguous()
-    rows = [r.contiguous() for r, _ in segments]
+    rows = [seg[0].contiguous() for seg in segments]
     if out is None:
         out = torch.empty((Bq, C), dtype=out_dtype, device=dev)
     n = len(segments)
-    seg_rows, seg_off, seg_n = _seg_arrays([o for _, o in segments], rows)
+    if any(len(seg) == 3 for seg in segments):                # an int8 segment: the table with row scales
+        scales = [seg[1].contiguous() if len(seg) == 3 else None for seg in segments]
+        seg_rows, seg_off, seg_n = _seg_arrays([seg[-1] for seg in segments], rows)
+        seg_sc = (nat.C.c_void_p * n)(*[_p(t) or None for t in scales])
+        seg_dt = (nat.C.c_int * n)(*[nat.I8 if len(seg) == 3 else _dt(r) for seg, r in zip(segments, rows)])
+        if Bq:
+            nat.check(_lib().cor_expand_queries_sq(_p(Q) or None, query_weight, seg_rows, seg_sc, seg_off, seg_n, seg_dt, n, scores.data_ptr(),
+                                                   idx.data_ptr(), Bq, kin, int(m), C, int(alpha), int(bool(normalize)), out.data_ptr(),
+                                                   _DT[out_dtype], _s()), "cor_expand_queries_sq")
+        return out
+    seg_rows, seg_off, seg_n = _seg_arrays([seg[-1] for seg in segments], rows)
     seg_dt = (nat.C.c_int * max(n, 1))(*[_dt(r) for r in rows])
     if Bq:                                                    # (no queries: empty tensors have no address to pass)
         nat.check(_lib().cor_expand_queries(_p(Q) or None, query_weight, seg_rows, seg_off, seg_n, seg_dt, n, scores.data_ptr(), idx.data_ptr(),

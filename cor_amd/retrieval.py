@@ -199,13 +199,22 @@ def _check_graph_args(who, k1, batch):
         raise ValueError(f"{who}: k1 must be in [1, {ops.nat.TOPK_KMAX}] and batch at least 1, got k1={k1}, batch={batch}")
 
 
+def _rows_as_queries(shard, lo, hi):
+    """Rows [lo, hi) of `shard` as search queries: a GalleryShard's stored rows; a QuantizedShard's dequantised fp32 rows (an int8 search
+    quantises them again: that is the definition of an int8 gallery's own neighbours)."""
+    if isinstance(shard, QuantizedShard):
+        with _on(shard.rows.device):
+            return ops.dequantize_rows_i8(shard.rows[lo:hi], shard.scales[lo:hi])
+    return shard.rows[lo:hi]
+
+
 def _knn_lists(shard, k1, batch, nb):
     """(nbr i64[n,k1], kth f32[n]) of `shard`'s rows searched, unfiltered, in `nb`, `batch` rows at a time."""
     n, dev = len(shard), shard.rows.device
     nbr = torch.empty((n, k1), dtype=torch.int64, device=dev)
     kth = torch.empty((n,), dtype=torch.float32, device=dev)
     for lo in range(0, n, int(batch)):
-        s, i = nb.search(shard.rows[lo:lo + int(batch)], k1)
+        s, i = nb.search(_rows_as_queries(shard, lo, lo + int(batch)), k1)
         nbr[lo:lo + int(batch)] = i
         kth[lo:lo + int(batch)] = s[:, k1 - 1]
     return nbr, kth
@@ -300,7 +309,8 @@ class GalleryShard:
         every row is the expansion, with query_weight = 0, of the row's own top-m list over `neighbours` (a GalleryShard or GallerySet;
         default: this shard, where a unit-norm row finds itself with score 1), normalised. `batch` rows are searched and expanded at a
         time. This shard is left untouched. `neighbours` that only search (a QuantizedShard over this shard's id space, e.g.
-        self.quantized()) find the lists, which are then expanded over THIS shard's rows."""
+        self.quantized()) find the lists, which are then expanded over THIS shard's rows; a QuantizedGallery, like every gallery that
+        expands, is also summed over."""
         _check_expansion("GalleryShard.augmented", m=m, batch=batch)
         nb = self if neighbours is None else neighbours
         rows_of = nb if hasattr(nb, "expand") else self
@@ -337,10 +347,12 @@ class GalleryShard:
 
 class QuantizedShard:
     """Rows [offset, offset + n) of a gallery as int8 with one fp32 scale per row (ops.quantize_rows_i8), scanned on the i8 matrix cores
-    (ops.similarity_topk_i8): half the bytes of a 16-bit copy and scores that are defined to the bit. It only SEARCHES: no rescore,
-    expand or rerank, which need real rows. Use it wherever a coarse search is taken: `coarse` of two_stage_search, a segment of a
-    GallerySet, `neighbours` of GalleryShard.augmented / neighbour_graph (search only; `augmented` also expands over its neighbours and
-    needs real rows there), the `shard` of distributed_search.
+    (ops.similarity_topk_i8): half the bytes of a 16-bit copy and scores that are defined to the bit. This class only SEARCHES: it is the
+    coarse copy that stands beside real rows, and it has no rescore, expand or rerank. Its subclass QuantizedGallery (below; gallery()
+    turns one into the other without copying) is the int8-ONLY gallery, which takes every list stage over the quantised rows alone. Use a
+    QuantizedShard wherever a coarse search is taken: `coarse` of two_stage_search, a segment of a GallerySet (where the set itself
+    carries the list stages for it), `neighbours` of GalleryShard.augmented / neighbour_graph (search only; GalleryShard.augmented then
+    expands over its own rows), the `shard` of distributed_search.
     labels (int32[n], one per row): the shard also takes the filtered searches of a GalleryShard (ops.similarity_topk_i8_filtered).
     groups (int32[n], one group id per row, typically the source image id; negative: a group of its own): it also takes the distinct
     searches (ops.similarity_topk_i8_distinct), with or without the filter. Without them `groups` is None."""
@@ -405,15 +417,97 @@ class QuantizedShard:
                 return ops.similarity_topk_i8(q, self.rows, self.scales, k, g_offset=self.offset)
             return ops.similarity_topk_i8_filtered(q, self.rows, self.scales, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
 
+    def gallery(self):
+        """This shard as a QuantizedGallery over the SAME tensors (nothing is copied): the int8-only gallery with the list stages."""
+        return QuantizedGallery.of(self)
+
+
+class QuantizedGallery(QuantizedShard):
+    """An int8-ONLY gallery: a QuantizedShard (the same constructor, from_rows and searches) that is a gallery in its own right. Beside
+    the searches it takes every list stage a GalleryShard takes, over the quantised rows alone: rescore (ops.rescore_topk_i8, the int8
+    score), expand (ops.expand_queries over rows whose value is float(q) * scale), neighbour_graph, rerank and augmented; no float copy of
+    the rows has to be resident. dequantized() gives the float rows it stands for. Use it as `coarse`, `fine` or both of two_stage_search,
+    as the gallery of expanded_search / reranked_search, as a segment of a GallerySet beside float segments, as `neighbours` of
+    GalleryShard.augmented (which then sums over THIS gallery's rows) / neighbour_graph."""
+
+    @classmethod
+    def of(cls, shard: QuantizedShard):
+        """A QuantizedGallery over the tensors of `shard` (rows, scales, labels, groups: the same objects, nothing is copied or checked
+        again); a QuantizedGallery is returned as it is."""
+        if isinstance(shard, cls):
+            return shard
+        g = cls.__new__(cls)
+        g.rows, g.scales, g.offset, g.labels, g.groups = shard.rows, shard.scales, shard.offset, shard.labels, shard.groups
+        return g
+
+    def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int | None = None, return_pos: bool = False):
+        """GalleryShard.rescore over the int8 rows (ops.rescore_topk_i8): queries f32[Bq,C], cand i64[Bq,kin] global row ids (at most 4096
+        per query) -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]) on the GPU: the int8 scores (those of search) of the candidates
+        this shard holds, ranked by (score desc, id asc), every id once. Ids outside [offset, offset + len) are dropped; fewer than k
+        left: the (-inf, -1[, -1]) tail. k defaults to min(kin, 256). The list search returned comes back bitwise."""
+        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        if cand.dim() != 2:
+            raise ValueError(f"QuantizedGallery.rescore: cand must be [Bq, kin], got {tuple(cand.shape)}")
+        k = min(cand.shape[1], ops.nat.TOPK_KMAX) if k is None else k
+        with _on(self.rows.device):
+            return ops.rescore_topk_i8(q, self.rows, self.scales, cand, k, g_offset=self.offset, return_pos=return_pos)
+
+    def expand(self, queries, scores: torch.Tensor, idx: torch.Tensor, m: int, alpha: int = 3, query_weight: float = 1.0,
+               normalize: bool = True, out_dtype: torch.dtype = torch.float32, out=None):
+        """GalleryShard.expand over the int8 rows (ops.expand_queries with an int8 segment): a row's value is float(q) * scale, one rounded
+        multiply, so the result equals bitwise the expansion over dequantized()'s fp32 rows."""
+        q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        with _on(self.rows.device):
+            return ops.expand_queries(q, [(self.rows, self.scales, self.offset)], scores, idx, m, alpha=alpha, query_weight=query_weight,
+                                      normalize=normalize, out_dtype=out_dtype, out=out)
+
+    def dequantized(self, dtype: torch.dtype = torch.float32):
+        """A GalleryShard (same offset, labels and groups) of the rows this shard stands for, float(q) * scale in fp32, rounded again to
+        `dtype` if it is bfloat16 / float16 (ops.dequantize_rows_i8). This shard is left untouched."""
+        with _on(self.rows.device):
+            rows = ops.dequantize_rows_i8(self.rows, self.scales, out_dtype=dtype)
+        return GalleryShard(rows, offset=self.offset, labels=self.labels, groups=self.groups)
+
+    def neighbour_graph(self, k1: int, batch: int = 4096, neighbours=None):
+        """GalleryShard.neighbour_graph of an int8 shard: the queries of a batch are that batch's dequantised fp32 rows (the search
+        quantises them again), searched over `neighbours` (default: this shard), then pruned on the device. Only one batch of rows
+        ever exists in fp32."""
+        _check_graph_args("QuantizedGallery.neighbour_graph", k1, batch)
+        live = [self] if len(self) else []
+        return _pruned_graph(live, int(k1), [_knn_lists(sh, int(k1), batch, self if neighbours is None else neighbours) for sh in live])
+
+    def rerank(self, scores: torch.Tensor, idx: torch.Tensor, graph, k1: int | None = None, lam: float = 0.3, k: int | None = None):
+        """GalleryShard.rerank over this shard: the graph and the lists are all it reads. ValueError if the graph was built from other
+        segments."""
+        return _rerank("QuantizedGallery.rerank", [self] if len(self) else [], scores, idx, graph, k1, lam, k)
+
+    def augmented(self, m: int, alpha: int = 3, batch: int = 4096, neighbours=None):
+        """Database-side augmentation of an int8 gallery: a NEW QuantizedGallery (same offset, labels and groups). Per batch the dequantised
+        rows are searched in `neighbours` (a gallery over the same id space; default: this shard), the top-m lists are expanded over
+        `neighbours` with query_weight = 0 and normalised into fp32, and that batch is quantised into the new shard: only one batch
+        ever exists in fp32. This shard is left untouched."""
+        _check_expansion("QuantizedGallery.augmented", m=m, batch=batch)
+        nb = self if neighbours is None else neighbours
+        q = torch.empty(self.rows.shape, dtype=torch.int8, device=self.rows.device)
+        sc = torch.empty(self.scales.shape, dtype=torch.float32, device=self.rows.device)
+        for lo in range(0, len(self), int(batch)):
+            s, i = nb.search(_rows_as_queries(self, lo, lo + int(batch)), int(m))
+            x = nb.expand(None, s, i, int(m), alpha=alpha, query_weight=0.0)
+            with _on(self.rows.device):
+                q[lo:lo + int(batch)], sc[lo:lo + int(batch)] = ops.quantize_rows_i8(x)
+        return QuantizedGallery(q, sc, offset=self.offset, labels=self.labels, groups=self.groups)
+
 
 class GallerySet:
-    """Several GalleryShard segments on ONE device, searched as one gallery: a gallery that grows (index today's images as a new
+    """Several GalleryShard and / or QuantizedShard (or QuantizedGallery) segments on ONE device, searched as one gallery: a gallery that grows (index today's images as a new
     segment: add(); retire a segment: drop()) without concatenating the resident rows. The segments own pairwise disjoint global row
     ranges [offset, offset + len), share the embedding width and either all carry labels (groups) or none does; their row dtypes may
     differ. A search runs every non-empty segment and merges the lists on the device (merge_topk_device): the result stays there.
     For segments of one dtype it equals bitwise the search of a single GalleryShard over the concatenated rows, because a row's
     chain score does not depend on which rows share its shard. A set can stand in for a shard in distributed_search (a rank that
-    owns several segments)."""
+    owns several segments). Int8 segments take part in every call (rescore, expand, neighbour_graph, rerank, augmented) beside float ones;
+    the set carries the list stages of an int8 segment itself, so a plain QuantizedShard will do as a segment. For int8 segments alone
+    each call equals bitwise the same call on ONE QuantizedGallery over the concatenated rows and scales."""
 
     def __init__(self, shards=()):
         self._segments = []
@@ -509,7 +603,7 @@ class GallerySet:
             if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
                 raise ValueError(f"GallerySet.rescore: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
             return _missing_lists(cand.shape[0], k, self._segments[0].rows.device if self._segments else cand.device)
-        res = [sh.rescore(queries, cand, k) for sh in live]
+        res = [_with_lists(sh).rescore(queries, cand, k) for sh in live]
         if len(live) == 1:
             return res[0]
         with torch.cuda.device(live[0].rows.device):
@@ -518,19 +612,23 @@ class GallerySet:
     def expand(self, queries, scores: torch.Tensor, idx: torch.Tensor, m: int, alpha: int = 3, query_weight: float = 1.0,
                normalize: bool = True, out_dtype: torch.dtype = torch.float32, out=None):
         """GalleryShard.expand over all segments in ONE launch: the kernel looks every listed id up in the table of the live segments
-        (at most 16; their dtypes may differ), so nothing is concatenated and no per-segment partial sums exist. The result equals
-        bitwise that of a single GalleryShard over the concatenated rows."""
+        (at most 16; their dtypes may differ, int8 segments with their row scales included), so nothing is concatenated and no
+        per-segment partial sums exist. The result equals bitwise that of a single GalleryShard (for int8 segments alone: a single
+        QuantizedGallery) over the concatenated rows."""
         live = self._live()
         dev = live[0].rows.device if live else scores.device
         q = None if queries is None else queries.reshape(-1, queries.shape[-1]).to(dev, torch.float32).contiguous()
         with _on(dev):
-            return ops.expand_queries(q, [(sh.rows, sh.offset) for sh in live], scores, idx, m, alpha=alpha, query_weight=query_weight,
+            table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
+            return ops.expand_queries(q, table, scores, idx, m, alpha=alpha, query_weight=query_weight,
                                       normalize=normalize, out_dtype=out_dtype, out=out)
 
     def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
         """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new
-        GallerySet of new segments; this set and its segments are left untouched."""
-        return GallerySet([sh.augmented(m, alpha=alpha, batch=batch, dtype=dtype, neighbours=self) for sh in self._segments])
+        GallerySet of new segments; this set and its segments are left untouched. An int8 segment becomes a new int8 segment
+        (QuantizedGallery.augmented; `dtype` applies to the float segments)."""
+        return GallerySet([QuantizedGallery.of(sh).augmented(m, alpha=alpha, batch=batch, neighbours=self) if isinstance(sh, QuantizedShard) else
+                           sh.augmented(m, alpha=alpha, batch=batch, dtype=dtype, neighbours=self) for sh in self._segments])
 
     def neighbour_graph(self, k1: int, batch: int = 4096):
         """GalleryShard.neighbour_graph over all segments: every row's top-k1 list over the WHOLE set, pruned against the lists of all
@@ -548,10 +646,16 @@ class GallerySet:
         return _rerank("GallerySet.rerank", self._live(), scores, idx, graph, k1, lam, k)
 
 
+def _with_lists(shard):
+    """A segment as something that takes the list stages: a plain QuantizedShard as the QuantizedGallery over its tensors."""
+    return QuantizedGallery.of(shard) if isinstance(shard, QuantizedShard) else shard
+
+
 def two_stage_search(queries: torch.Tensor, coarse, fine, k: int, k_coarse: int, fine_queries: torch.Tensor | None = None, **search_kwargs):
     """Two-stage search on one device: coarse.search(queries, k_coarse, **search_kwargs) finds the candidates, fine.rescore(fine_queries
     if given else queries, idx, k) orders them again and keeps k -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU, the scores being
-    `fine`'s chain scores. coarse and fine are each a GalleryShard or a GallerySet over the SAME global id space: typically a bf16 /
+    `fine`'s scores (chain scores of float rows, int8 scores of a QuantizedGallery). coarse and fine are each a GalleryShard, a QuantizedShard
+    (coarse only), a QuantizedGallery or a GallerySet (float, int8 or mixed segments) over the SAME global id space: typically a bf16 /
     fp16 copy that is scanned on the matrix cores and the fp32 master rows, which give the final order at fp32 precision (the 16-bit
     stage rounds the query to the gallery dtype too; the second stage takes it unrounded). fine_queries: another embedding of the same
     requests for the second stage (e.g. the exact-query mode's fp32 feat). A candidate row that `fine` does not hold drops out; fewer
@@ -574,7 +678,8 @@ def _check_expansion(who, m=1, k=1, rounds=1, batch=1):
 def expanded_search(queries: torch.Tensor, gallery, k: int, m: int, alpha: int = 3, query_weight: float = 1.0, rounds: int = 1, **search_kwargs):
     """Search with query expansion on one device: `rounds` times q <- gallery.expand(q, *gallery.search(q, m, **search_kwargs), m)
     (q starts as `queries`; each round expands the query of the round before), then gallery.search(q, k, **search_kwargs)
-    -> (scores f32[Bq,k], idx i64[Bq,k], expanded queries f32[Bq,C]) on the GPU. gallery: a GalleryShard or a GallerySet. alpha and
+    -> (scores f32[Bq,k], idx i64[Bq,k], expanded queries f32[Bq,C]) on the GPU. gallery: a GalleryShard, a QuantizedGallery (an int8-only
+    gallery) or a GallerySet of either. alpha and
     query_weight as in ops.expand_queries (alpha = 0, query_weight = 1: plain AQE); the expanded query is L2-normalised. 1 <= m <= 256,
     1 <= k <= 256, rounds >= 1, else ValueError. search_kwargs (query_labels, mode, distinct) apply to EVERY search, so a filtered
     expansion only sums rows the filter allows. Nothing leaves the device and the host is not waited for. distributed_search has no
@@ -590,8 +695,8 @@ def expanded_search(queries: torch.Tensor, gallery, k: int, m: int, alpha: int =
 
 def reranked_search(queries: torch.Tensor, gallery, graph, k: int, k_coarse: int, k1: int | None = None, lam: float = 0.3, **search_kwargs):
     """Search with k-reciprocal re-ranking on one device: gallery.search(queries, k_coarse, **search_kwargs) followed by
-    gallery.rerank(scores, idx, graph, k1=k1, lam=lam, k=k) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU. gallery: a GalleryShard or a
-    GallerySet, graph: its neighbour_graph. 1 <= k <= k_coarse <= 256, else ValueError; k1 defaults to the graph's width and must not
+    gallery.rerank(scores, idx, graph, k1=k1, lam=lam, k=k) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU. gallery: a GalleryShard, a
+    QuantizedGallery (an int8-only gallery) or a GallerySet of either, graph: its neighbour_graph. 1 <= k <= k_coarse <= 256, else ValueError; k1 defaults to the graph's width and must not
     exceed k_coarse. search_kwargs (query_labels, mode, distinct) go to the search; with distinct=True the candidates are the
     representatives' rows and their graph rows are used as they are. Nothing leaves the device and the host is not waited for.
     distributed_search has no such option: a candidate's graph row lives on the rank that owns the row."""

@@ -38,7 +38,8 @@ extern "C" {
 #define COR_FILTER_EQ 0       /* cor_similarity_topk_filtered: a row is allowed if its label equals the query's */
 #define COR_FILTER_NE 1       /* ... : a row is allowed if its label differs from the query's */
 
-enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */, COR_BF16X3 = 3 /* x3 split rows, see below */ };
+enum { COR_F32 = 0, COR_BF16 = 1, COR_F16 = 2 /* gallery storage only */, COR_BF16X3 = 3 /* x3 split rows, see below */,
+       COR_I8 = 4 /* int8 rows with one fp32 scale per row; accepted only where stated */ };
 /* COR_BF16X3 (exact-query mode: the support branch at fp32 accuracy on the bf16 matrix cores). An fp32 value x is carried as
  * hi = bf16_rne(x) and lo = bf16_rne(x - hi); a SPLIT ROW of C logical values is bf16 [lo(0..C) | hi(0..C) | hi(0..C)] (3C elements,
  * segment stride C unless stated), a split WEIGHT row is [hi | lo | hi]. A bf16 GEMM over the 3K columns then computes
@@ -551,6 +552,64 @@ int cor_rescore_topk(const float* Q, const void* G, int g_dtype, int Bq, int Ng,
 int cor_expand_queries(const float* Q, float query_weight, const void* const* seg_rows, const long long* seg_offset, const int* seg_n,
                        const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int m, int C, int alpha,
                        int normalize, void* out, int out_dtype, void* stream);
+
+/* Int8-only galleries: the list stages over quantised rows (Gq int8 [n,C] with scale f32 [n], as cor_quantize_rows_i8 makes them), so that
+ * a gallery resident as int8 alone is re-scored, expanded, augmented and re-ranked without a float copy of its rows. The int32 dot product
+ * is exact in any summation order and every floating-point step below is ONE separately rounded IEEE fp32 operation, never contracted, so
+ * none of these calls carries an error bound: each is bit-identical to its definition evaluated on the CPU (tests/i8_list_refs.py). No
+ * call allocates or synchronises with the host; each runs on `stream` and can be captured in a graph; all argument errors are decided
+ * before any HIP call.
+ *
+ * cor_dequantize_rows_i8: the dequantised row, x[g,c] = (float)q[g,c] * scale[g], ONE rounded fp32 multiply, stored into X [n,C] as fp32
+ * (x_dtype COR_F32) or rounded again, to nearest-even, to COR_BF16 / COR_F16: the 16-bit forms are the ROUNDED fp32 product rounded a second
+ * time (what a conversion of the fp32 output gives), not the exact product rounded once. C % 16 == 0 and C <= 256, an x_dtype above: else
+ * COR_ENOSUPPORT; null pointers, n < 0, C <= 0, X or q not 16-byte aligned, scale not 4-byte aligned: COR_EINVAL (the checks and their
+ * order are those of cor_quantize_rows_i8); n == 0 is a successful no-op. One launch, memory-bound (16 lanes per row, 16-byte loads and
+ * stores).
+ *
+ * cor_rescore_topk_i8: cor_rescore_topk over an int8 shard. Q f32 [Bq,C]; Gq int8 [Ng,C] and gscale f32 [Ng], the shard's rows, global ids
+ * [g_offset, g_offset + Ng); cand i64 [Bq,kin], contiguous; out_scores f32 [Bq,k], out_idx i64 [Bq,k] (global ids), out_pos NULL or
+ * i32 [Bq,k]. Entry j of query b is PRESENT if g_offset <= cand[b,j] < g_offset + Ng and no earlier position j' < j of the same query
+ * holds the same id; every other entry (negative ids, ids of other shards, repeats) is MISSING: it is dropped, and no address is ever
+ * derived from an id that has not passed the range test, so the ids may be arbitrary 64-bit values. The SCORE of a present entry is that
+ * of cor_similarity_topk_i8: qq, qscale = the quantisation of the fp32 query by the rule of cor_quantize_rows_i8, made inside the call;
+ * d = sum_c qq[b,c] * Gq[g,c] in int32; score = ((float)d * qscale[b]) * gscale[g], two separately rounded fp32 multiplies. Present
+ * entries are ordered by (score desc, global id asc) with the list kernels' rules: scores compare as floats (-0.0 and +0.0 tie and the id
+ * decides) and the first k go out with the score bits as computed. out_pos, if given, receives the entry's position j in the input list
+ * (of a repeated id: its first occurrence). Positions past the number of present entries hold (-inf, -1, -1).
+ * Hence re-scoring the list an int8 search returned against the gallery it searched gives that list back bitwise, whatever the order of
+ * the candidates, with ONE exception: a list that holds both +0.0 and -0.0 scores (which needs row scales small enough for the product to
+ * underflow, or hand-made scales of both signs). The search orders by the score's bits, so every +0.0 ranks before every -0.0; this call
+ * compares them as equal and lets the id decide. The lists of several shards over disjoint id ranges, each re-scoring the same cand,
+ * merge (cor_merge_topk, which has the same tie rule) into the list of one shard over all the rows.
+ * One launch, one block per query: the first wave reduces the query's amax and writes the int8 query (C bytes) and qscale to LDS;
+ * thread-per-candidate row gathers with 16-byte loads (a row is C bytes; four candidates interleaved per thread) feeding v_dot4c_i32_i8;
+ * then the ranking, keep flags, block scan and tail of cor_rescore_topk.
+ * 1 <= k <= COR_TOPK_KMAX, kin >= 1, Ng >= 0, Bq >= 0 and non-null Q / cand / out_scores / out_idx (Gq and gscale too unless Ng == 0),
+ * else COR_EINVAL; then kin > COR_MERGE_NMAX, C > 256 or C % 16 != 0: COR_ENOSUPPORT (the order of cor_rescore_topk's checks); Bq == 0 is
+ * a successful no-op. Q and Gq 16-byte aligned as for the searches. cor_rescore_i8_workspace_bytes reports the errors it can see as
+ * negative values; the kernel needs no scratch memory, so it returns 0 for every supported shape and `workspace` may then be NULL.
+ *
+ * cor_expand_queries_sq: cor_expand_queries with one more HOST array, seg_scale: for a segment of seg_dtype COR_I8 (rows int8
+ * [seg_n[s], C]) seg_scale[s] is the DEVICE pointer of its f32 [seg_n[s]] row scales (a null entry, or a null seg_scale, with seg_n[s] > 0
+ * there: COR_EINVAL); for a float segment the entry is ignored and seg_scale may be NULL when no segment is COR_I8. Float and int8 segments
+ * may stand in one table. The definition is that of cor_expand_queries with one added line in step 2: for a row of an int8 segment the
+ * stored value widened to fp32 is x[c] = (float)q[c] * scale[row], ONE rounded fp32 multiply; then v[c] = v[c] + (w * x[c]) as before.
+ * The result therefore equals bitwise the expansion over an fp32 segment that holds the dequantised rows (cor_dequantize_rows_i8), and
+ * still does not depend on how the rows are cut into segments or on which dtype stores equal values. All other arguments, limits and
+ * error codes are those of cor_expand_queries, an unknown seg_dtype (COR_I8 is known here) being COR_ENOSUPPORT; cor_expand_queries itself
+ * keeps refusing COR_I8. Kernel: that of cor_expand_queries; the lane's four channels of an int8 row are ONE dword, so at C = 256 a row is
+ * one 256-byte wave load, and the row's scale is fetched by the lane that looked the id up and travels with the weight by v_readlane. A
+ * table without int8 rows runs cor_expand_queries' own kernels. */
+int cor_dequantize_rows_i8(const signed char* q, const float* scale, int n, int C, void* X, int x_dtype, void* stream);
+long cor_rescore_i8_workspace_bytes(int Bq, int kin, int k);
+int cor_rescore_topk_i8(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, long long g_offset,
+                        const long long* cand, int kin, int k, float* out_scores, long long* out_idx, int* out_pos, void* workspace,
+                        void* stream);
+int cor_expand_queries_sq(const float* Q, float query_weight, const void* const* seg_rows, const float* const* seg_scale,
+                          const long long* seg_offset, const int* seg_n, const int* seg_dtype, int nseg, const float* scores,
+                          const long long* idx, int Bq, int kin, int m, int C, int alpha, int normalize, void* out, int out_dtype,
+                          void* stream);
 
 /* k-reciprocal re-ranking (Zhong et al., CVPR 2017), SET FORM: uniform weights and the Jaccard index of k-reciprocal neighbour sets, mixed
  * with the original score by lam. Not implemented: the paper's Gaussian weights, the 2/3-overlap set expansion, the local query expansion
