@@ -21,6 +21,7 @@ FILTER_EQ, FILTER_NE = 0, 1    # cor_similarity_topk_filtered modes (COR_FILTER_
 MERGE_NMAX = 4096    # most entries per query (P * kin) one cor_merge_topk launch ranks (COR_MERGE_NMAX)
 EXPAND_SEGMAX = 16    # most gallery segments one cor_expand_queries launch reads (COR_EXPAND_SEGMAX)
 RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_reciprocal launch reads (COR_RERANK_SEGMAX)
+DIVERSIFY_SEGMAX = 16    # most gallery segments one cor_diversify_mmr launch reads (COR_DIVERSIFY_SEGMAX)
 ORDER_REVERSE = 1 << 30    # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
 GEMM_KERNEL_SCALAR, GEMM_KERNEL_MASK, GEMM_EPILOGUE_VEC = 32, 0xff, 1 << 8    # cor_gemm_kernel_id (COR_GEMM_KERNEL_SCALAR, ..._MASK, COR_GEMM_EPILOGUE_VEC)
 KERNEL_ROWLANE, KERNEL_FEWQ, KERNEL_FLASH_MFMA, KERNEL_FLASH_PIPELINED, KERNEL_WINDOW_BLOCK = 1, 2, 3, 4, 5
@@ -93,6 +94,7 @@ SIGNATURES = {
     "cor_expand_queries_sq": [_p, _f, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p],
     "cor_knn_reciprocal": [_p, _p, _p, _i, _i, _i, _p, _p],
     "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
+    "cor_diversify_mmr": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,

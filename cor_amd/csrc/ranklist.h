@@ -1,5 +1,5 @@
 // cor_amd — the device steps the one-block-per-query list kernels share (merge.hip, rescore.hip, rerank.hip) and the id -> segment lookup
-// (expand.hip, rerank.hip). Integer code only: the files that include this keep their own floating-point rules. Not for retrieval.hip,
+// (expand.hip, rerank.hip, diversify.hip). Integer code only: the files that include this keep their own floating-point rules. Not for retrieval.hip,
 // whose block_sort_u64 / rank_key use another key layout.
 //
 // Rank keys. An entry of a list of n <= COR_MERGE_NMAX = 4096 becomes a 64-bit key in LDS,

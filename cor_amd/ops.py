@@ -957,6 +957,67 @@ def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
+def diversify_mmr(segments, scores, idx, k, lam=0.5, max_sim=None, return_pos=False, return_value=False):
+    """Diversified lists on the device (cor_diversify_mmr): greedy maximal marginal relevance with optional near-duplicate suppression.
+    segments as expand_queries takes them: a list of (rows, offset), rows [n,C] fp32 / bf16 / fp16 holding the global ids
+    [offset, offset + n), or of (rows_i8, scales, offset), int8 rows with their f32 [n] row scales whose value is float(q) * scale; at most
+    nat.DIVERSIFY_SEGMAX (16), pairwise disjoint, dtypes free to differ. scores f32 [Bq,kin] and idx i64 [Bq,kin] as a search, the merge
+    or the re-scoring return them -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]][, value f32[Bq,k]]). Per query, k times: among
+    the entries still alive the one with the greatest f = lam * score - (1 - lam) * (its largest similarity to an entry already chosen,
+    at least 0) goes out, by (f desc, id asc, position asc), with its INPUT score (value: f itself; pos: its position in the input list);
+    then every alive entry whose similarity to it is >= max_sim leaves for good (max_sim None: no suppression). The similarity is the
+    fmaf chain of the searches over the rows' fp32 values, so neither the segmentation nor the storage dtype of equal values changes
+    a bit; include/cor_amd.h has the definition to the bit. An id of no segment (-1, another shard's, any 64-bit value) is dropped and its
+    score is not read; a repeated id is an entry of its own. Fewer than k chosen: the (-inf, -1, -1, -inf) tail. lam = 1 without max_sim
+    returns the present entries by (score desc, id asc); lam = 1 with max_sim is plain near-duplicate suppression. 0 <= lam <= 1,
+    1 <= k <= 256, kin <= nat.MERGE_NMAX (4096; beyond that NativeError), C <= 256 and C % 16 == 0. No host synchronisation; capturable
+    in a graph."""
+    who = "diversify_mmr"
+    segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
+    if any(len(seg) not in (2, 3) for seg in segments):
+        raise ValueError(f"{who}: a segment is (rows, offset) or (rows_i8, scales, offset)")
+    if len(segments) > nat.DIVERSIFY_SEGMAX:
+        raise ValueError(f"{who}: {len(segments)} segments, one call reads at most {nat.DIVERSIFY_SEGMAX}")
+    Bq, kin = _list_front(who, scores, idx)
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{who}: lam must be in [0, 1], got {lam}")
+    max_sim = float("inf") if max_sim is None else float(max_sim)
+    if max_sim != max_sim:
+        raise ValueError(f"{who}: max_sim must not be NaN")
+    C = segments[0][0].shape[-1] if segments and segments[0][0].dim() == 2 else 16    # (no segment: every entry is missing, any width will do)
+    if C < 16 or C > 256 or C % 16 != 0:
+        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
+    for seg in segments:
+        r = seg[0]
+        if len(seg) == 3:
+            if r.dim() != 2 or r.shape[1] != C or r.dtype != torch.int8 or r.shape[0] >= 2 ** 31:
+                raise ValueError(f"{who}: a segment with scales must be int8 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+            if seg[1].dtype != torch.float32 or seg[1].dim() != 1 or seg[1].shape[0] != r.shape[0]:
+                raise ValueError(f"{who}: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
+        elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
+            raise ValueError(f"{who}: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+    _disjoint_spans(who, segments)
+    dev = _dev(scores, idx, *[t for seg in segments for t in seg[:-1]])
+    scores, idx = scores.contiguous(), idx.contiguous()
+    rows = [seg[0].contiguous() for seg in segments]
+    rows = [r.clone() if r.data_ptr() % 16 else r for r in rows]   # a view into a larger tensor: the kernel loads 16 B at a time
+    scales = [seg[1].contiguous() if len(seg) == 3 else None for seg in segments]
+    n = len(segments)
+    seg_rows, seg_off, seg_n = _seg_arrays([seg[-1] for seg in segments], rows)
+    seg_sc = (nat.C.c_void_p * max(n, 1))(*[_p(t) or None for t in scales])
+    seg_dt = (nat.C.c_int * max(n, 1))(*[nat.I8 if len(seg) == 3 else _dt(r) for seg, r in zip(segments, rows)])
+    out_s, out_i, out_p = _list_outputs(Bq, int(k), dev, return_pos)
+    out_v = torch.empty((Bq, int(k)), dtype=torch.float32, device=dev) if return_value else None
+    if Bq:                                                    # (no queries: empty tensors have no address to pass)
+        nat.check(_lib().cor_diversify_mmr(seg_rows, seg_sc, seg_off, seg_n, seg_dt, n, scores.data_ptr(), idx.data_ptr(), Bq, kin, C, lam, max_sim,
+                                           int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _p(out_v) or None, _s()),
+                  "cor_diversify_mmr")
+    return (out_s, out_i) + ((out_p,) if return_pos else ()) + ((out_v,) if return_value else ())
+
+
 def decoder_heads(hs, w01, b01, w2, b2):
     """The mask decoder's five output MLPs in one launch (cor_decoder_heads). hs [B*6,256] in the weights' dtype ->
     (hyper f32 [B,4,32], iou f32 [B,4])."""

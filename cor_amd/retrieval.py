@@ -240,6 +240,14 @@ def _rerank(who, live, scores, idx, graph, k1, lam, k):
         return ops.rerank_reciprocal(scores, idx, graph.segments, k1, lam, k)
 
 
+def _diversify(who, table, dev, scores, idx, k, lam, max_sim, return_pos):
+    if idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be [Bq, kin], got {tuple(idx.shape)}")
+    k = min(idx.shape[1], ops.nat.TOPK_KMAX) if k is None else k
+    with _on(dev):
+        return ops.diversify_mmr(table, scores, idx, k, lam=lam, max_sim=max_sim, return_pos=return_pos)
+
+
 class GalleryShard:
     """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16. labels: optional int32[n], one label
     per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches. groups: optional int32[n],
@@ -338,6 +346,15 @@ class GalleryShard:
         graph was built from other segments."""
         return _rerank("GalleryShard.rerank", [self] if len(self) else [], scores, idx, graph, k1, lam, k)
 
+    def diversify(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, lam: float = 0.5, max_sim: float | None = None,
+                  return_pos: bool = False):
+        """Diversified lists over this shard's rows (ops.diversify_mmr): scores / idx [Bq,kin] as search, rescore, two_stage_search or
+        rerank return them -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]) on the GPU: greedy MMR, k times the entry with the
+        greatest lam * score - (1 - lam) * (largest chain similarity to an entry already chosen), each with its input score; with
+        max_sim an entry at least that similar to a chosen one is dropped for good (lam = 1: plain near-duplicate suppression). k
+        defaults to min(kin, 256). Entries this shard does not hold are dropped; fewer than k chosen: the (-inf, -1[, -1]) tail."""
+        return _diversify("GalleryShard.diversify", [(self.rows, self.offset)], self.rows.device, scores, idx, k, lam, max_sim, return_pos)
+
     def quantized(self):
         """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
         coarse stage of two_stage_search over these rows. This shard is left untouched. The labels and the group ids are carried (the same
@@ -348,7 +365,7 @@ class GalleryShard:
 class QuantizedShard:
     """Rows [offset, offset + n) of a gallery as int8 with one fp32 scale per row (ops.quantize_rows_i8), scanned on the i8 matrix cores
     (ops.similarity_topk_i8): half the bytes of a 16-bit copy and scores that are defined to the bit. This class only SEARCHES: it is the
-    coarse copy that stands beside real rows, and it has no rescore, expand or rerank. Its subclass QuantizedGallery (below; gallery()
+    coarse copy that stands beside real rows, and it has no rescore, expand, rerank or diversify. Its subclass QuantizedGallery (below; gallery()
     turns one into the other without copying) is the int8-ONLY gallery, which takes every list stage over the quantised rows alone. Use a
     QuantizedShard wherever a coarse search is taken: `coarse` of two_stage_search, a segment of a GallerySet (where the set itself
     carries the list stages for it), `neighbours` of GalleryShard.augmented / neighbour_graph (search only; GalleryShard.augmented then
@@ -425,7 +442,7 @@ class QuantizedShard:
 class QuantizedGallery(QuantizedShard):
     """An int8-ONLY gallery: a QuantizedShard (the same constructor, from_rows and searches) that is a gallery in its own right. Beside
     the searches it takes every list stage a GalleryShard takes, over the quantised rows alone: rescore (ops.rescore_topk_i8, the int8
-    score), expand (ops.expand_queries over rows whose value is float(q) * scale), neighbour_graph, rerank and augmented; no float copy of
+    score), expand (ops.expand_queries over rows whose value is float(q) * scale), neighbour_graph, rerank, diversify and augmented; no float copy of
     the rows has to be resident. dequantized() gives the float rows it stands for. Use it as `coarse`, `fine` or both of two_stage_search,
     as the gallery of expanded_search / reranked_search, as a segment of a GallerySet beside float segments, as `neighbours` of
     GalleryShard.augmented (which then sums over THIS gallery's rows) / neighbour_graph."""
@@ -460,6 +477,14 @@ class QuantizedGallery(QuantizedShard):
         with _on(self.rows.device):
             return ops.expand_queries(q, [(self.rows, self.scales, self.offset)], scores, idx, m, alpha=alpha, query_weight=query_weight,
                                       normalize=normalize, out_dtype=out_dtype, out=out)
+
+    def diversify(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, lam: float = 0.5, max_sim: float | None = None,
+                  return_pos: bool = False):
+        """GalleryShard.diversify over the int8 rows (ops.diversify_mmr with an int8 segment): a row's value is float(q) * scale and the
+        similarity is the fp32 chain over those values (not the int8 search score), so the result equals bitwise the diversification over
+        dequantized()'s fp32 rows."""
+        return _diversify("QuantizedGallery.diversify", [(self.rows, self.scales, self.offset)], self.rows.device, scores, idx, k, lam, max_sim,
+                          return_pos)
 
     def dequantized(self, dtype: torch.dtype = torch.float32):
         """A GalleryShard (same offset, labels and groups) of the rows this shard stands for, float(q) * scale in fp32, rounded again to
@@ -623,6 +648,15 @@ class GallerySet:
             return ops.expand_queries(q, table, scores, idx, m, alpha=alpha, query_weight=query_weight,
                                       normalize=normalize, out_dtype=out_dtype, out=out)
 
+    def diversify(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, lam: float = 0.5, max_sim: float | None = None,
+                  return_pos: bool = False):
+        """GalleryShard.diversify over all segments in ONE launch: the kernel looks every listed id up in the table of the live segments
+        (at most 16; their dtypes may differ, int8 segments, a plain QuantizedShard included, with their row scales). The result equals
+        bitwise that of a single fp32 GalleryShard over the concatenated widened / dequantised rows."""
+        live = self._live()
+        table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
+        return _diversify("GallerySet.diversify", table, live[0].rows.device if live else scores.device, scores, idx, k, lam, max_sim, return_pos)
+
     def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
         """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new
         GallerySet of new segments; this set and its segments are left untouched. An int8 segment becomes a new int8 segment
@@ -704,6 +738,22 @@ def reranked_search(queries: torch.Tensor, gallery, graph, k: int, k_coarse: int
         raise ValueError(f"reranked_search: need 1 <= k <= k_coarse <= {ops.nat.TOPK_KMAX}, got k={k}, k_coarse={k_coarse}")
     s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
     return gallery.rerank(s, i, graph, k1=k1, lam=lam, k=int(k))
+
+
+def diversified_search(queries: torch.Tensor, gallery, k: int, k_coarse: int, lam: float = 0.5, max_sim: float | None = None, **search_kwargs):
+    """Search with diversified results on one device: gallery.search(queries, k_coarse, **search_kwargs) followed by
+    gallery.diversify(scores, idx, k=k, lam=lam, max_sim=max_sim) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU: the k entries greedy MMR
+    picks out of the k_coarse best, each with its search score. gallery: a GalleryShard, a QuantizedGallery (an int8-only gallery) or a
+    GallerySet of either. 1 <= k <= k_coarse <= 256, 0 <= lam <= 1, max_sim not NaN, else ValueError before anything runs. search_kwargs
+    (query_labels, mode, distinct) go to the search; distinct=True removes repeats that share a group id, the diversification those that
+    merely look alike. Nothing leaves the device and the host is not waited for. distributed_search has no such option: a candidate's row
+    lives on the rank that owns it."""
+    if not 1 <= int(k) <= int(k_coarse) <= ops.nat.TOPK_KMAX:
+        raise ValueError(f"diversified_search: need 1 <= k <= k_coarse <= {ops.nat.TOPK_KMAX}, got k={k}, k_coarse={k_coarse}")
+    if not 0.0 <= float(lam) <= 1.0 or (max_sim is not None and float(max_sim) != float(max_sim)):
+        raise ValueError(f"diversified_search: lam must be in [0, 1] and max_sim not NaN, got lam={lam}, max_sim={max_sim}")
+    s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
+    return gallery.diversify(s, i, k=int(k), lam=lam, max_sim=max_sim)
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):

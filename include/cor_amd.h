@@ -661,6 +661,62 @@ int cor_rerank_reciprocal(const float* scores, const long long* idx, const long 
                           const long long* seg_offset, const int* seg_n, int nseg, int Bq, int kin, int kg, int k1, float lam, int k,
                           float* out_scores, long long* out_idx, int* out_pos, void* stream);
 
+/* Result diversification: greedy maximal marginal relevance (MMR; Carbonell & Goldstein, SIGIR 1998) over a candidate list, with optional
+ * near-duplicate suppression. Per query, k times: the entry with the best mix of its score and its largest similarity to the entries
+ * already chosen goes out; an entry that is at least max_sim similar to a chosen one leaves for good.
+ *
+ * cor_diversify_mmr. The segment table is that of cor_expand_queries_sq: seg_rows / seg_scale / seg_offset / seg_n / seg_dtype are HOST
+ * arrays of nseg entries; segment s holds the rows with global ids [seg_offset[s], seg_offset[s] + seg_n[s]) at the DEVICE pointer
+ * seg_rows[s], contiguous [seg_n[s], C] in seg_dtype[s] (COR_F32 / COR_BF16 / COR_F16 / COR_I8, mixed freely); for a COR_I8 segment
+ * seg_scale[s] is the DEVICE pointer of its f32 [seg_n[s]] row scales, for a float segment the entry is ignored and seg_scale may be NULL
+ * when no segment is COR_I8. At most COR_DIVERSIFY_SEGMAX segments with pairwise disjoint id ranges. The launcher copies the table into a
+ * by-value kernel argument: no device allocation, no host-to-device copy, no host synchronisation; everything runs on `stream` and the call
+ * can be captured in a graph. scores f32 [Bq,kin] and idx i64 [Bq,kin], contiguous: lists as the searches, the merge or the re-scoring
+ * return them. out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_pos NULL or i32 [Bq,k], out_value NULL or f32 [Bq,k]. Rows 16-byte aligned as
+ * for the searches.
+ * Definition, per query b, fixed to the bit:
+ *   Presence. Entry j < kin is PRESENT if idx[b,j] lies in some segment's [seg_offset[s], seg_offset[s] + seg_n[s]); the range test runs
+ *   before any address is formed (unsigned difference behind id >= seg_offset[s]), so ids may be arbitrary 64-bit values. Every other
+ *   entry is MISSING: it is dropped and its score is never read. Ids may repeat; a repeat is an entry of its own, ranked by its position.
+ *   Row value. x(r)[c] of an fp32 row is the stored value; of a bf16 / fp16 row the stored value widened exactly; of an int8 row
+ *   (float)q[c] * scale[row], ONE rounded fp32 multiply (the rule of cor_expand_queries_sq).
+ *   Similarity. sim(r, r') is the fmaf chain of oracle/c/sim_chain.c over x(r) and x(r'): acc = +0; for chunk c = 0 .. C/8 - 1 and
+ *   i = 0 .. 3: acc = fmaf(x(r)[8c+i], x(r')[8c+i], acc), then acc = fmaf(x(r)[8c+4+i], x(r')[8c+4+i], acc). It is bitwise symmetric. For
+ *   int8 rows this is on purpose NOT the int32 score of the int8 searches: the result must not depend on which dtype stores equal values
+ *   or on how the rows are cut into segments.
+ *   State. m_j = +0 for every present entry; all present entries start ALIVE.
+ *   Step t = 0 .. k-1, while an entry is alive:
+ *     1. for every alive entry f_j = (lam * scores[b,j]) - ((1.0f - lam) * m_j): four separately rounded IEEE fp32 operations, never
+ *        contracted.
+ *     2. the winner w is the alive entry with the greatest f, compared as floats (-0.0 and +0.0 tie); then the smaller 64-bit id wins,
+ *        then the smaller position. The id is read only on a tie.
+ *     3. output slot t: out_scores = the winner's INPUT score bits, unchanged (the list still feeds cor_expand_queries /
+ *        cor_rerank_reciprocal); out_idx = its id; out_pos = its position j; out_value = f_w as computed.
+ *     4. w leaves the alive set. For every remaining alive entry j: v = sim(row_j, row_w); if v > m_j then m_j = v (strict: the penalty
+ *        is never negative and there is no +-0 ambiguity); if v >= max_sim the entry is SUPPRESSED and leaves the alive set for good.
+ *        max_sim = +inf turns suppression off.
+ *   Tail. Slots past the last winner hold (-inf, -1, -1, -inf).
+ *   Preconditions: present entries have finite scores and rows. (Otherwise the result is unspecified, but every access stays in bounds.)
+ * Consequences. lam = 1 with max_sim = +inf returns the present entries ordered by (score desc, id asc, position asc) with their score
+ * bits: a list as a search returns it comes back unchanged. lam = 1 with a finite max_sim is greedy near-duplicate suppression in score
+ * order. Several segments, or another storage dtype for the same values, give the bits of ONE fp32 segment over the concatenated widened
+ * rows. max_sim = -inf gives exactly one output per query that has a present entry.
+ * One launch, one block per query, max(64, min(npad, 256), npad / 4) threads (npad = kin rounded up to a power of two), one to four
+ * candidates per thread with their state in registers. Each step is one block-wide argmax (wave butterfly, then the waves' bests through
+ * LDS) and one similarity pass: the winner's row is widened into 1 KiB of LDS and every thread advances its alive candidates' chains
+ * against it. A table of one storage dtype stages the rows through LDS, a wave copying 8 rows x 128 bytes per load into an image of its
+ * own (9 KiB of dynamic LDS per wave) from which every lane reads its row back; a table of mixed dtypes gathers thread per candidate
+ * with 16-byte loads, up to four chains interleaved. k * kin chains per query at most; no Gram matrix, no global workspace, no scratch.
+ * COR_EINVAL: a null scores / idx / out_scores / out_idx, a null segment array (seg_rows, seg_offset, seg_n, seg_dtype) with nseg > 0,
+ * Bq < 0, kin < 1, k < 1, nseg < 0, C < 1, a negative seg_n, a null seg_rows[s] with seg_n[s] > 0, a null scale (entry or array) for a
+ * non-empty COR_I8 segment, lam NaN or outside [0, 1], max_sim NaN. COR_ENOSUPPORT: kin > COR_MERGE_NMAX, k > COR_TOPK_KMAX,
+ * nseg > COR_DIVERSIFY_SEGMAX, C > 256 or C % 16 != 0, an unknown seg_dtype. All of these are decided before any HIP call. Bq == 0 is a
+ * successful no-op; nseg == 0 is legal (every entry is missing). */
+#define COR_DIVERSIFY_SEGMAX 16
+int cor_diversify_mmr(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                      const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam,
+                      float max_sim, int k, float* out_scores, long long* out_idx, int* out_pos, float* out_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
