@@ -1,4 +1,4 @@
-// cor_amd — the device steps the one-block-per-query list kernels share (merge.hip, rescore.hip, rerank.hip) and the id -> segment lookup
+// cor_amd — the device steps the one-block-per-query list kernels share (merge.hip, rescore.hip, rescore_i8.hip, rerank.hip) and the id -> segment lookup
 // (expand.hip, rerank.hip, diversify.hip). Integer code only: the files that include this keep their own floating-point rules. Not for retrieval.hip,
 // whose block_sort_u64 / rank_key use another key layout.
 //
@@ -104,6 +104,64 @@ __device__ __forceinline__ void rank_fill_tail(int total, int k, long long out0,
     out_idx[out0 + t] = -1;
     if (third) third[out0 + t] = -1;
   }
+}
+
+// the id list of one query (the rescore kernels): kin global row ids, read by position and through a key's position
+struct RankIdList {
+  const long long* ids;
+  __device__ __forceinline__ long long operator()(unsigned pos) const { return ids[pos]; }
+  __device__ __forceinline__ long long at(u64 key) const { return ids[(unsigned)key & RANK_POS_MASK]; }
+};
+
+// Rank and place of the rescore kernels, by the whole block of T threads (rescore_i8.hip calls it; rescore.hip writes the same lines out,
+// see there). The thread hands in the score bits of its NI candidates (positions tid + j T) and whether each is present; every position
+// < npad becomes a key, the keys are sorted, the first of every run of equal ids is kept (the lowest position) and the first k survivors
+// are written, then the (-inf, -1, -1) tail. key [npad], keep [npad], s_present (zeroed behind a barrier by the caller) and s_wsum [16]
+// are the caller's LDS.
+template <int NI>
+__device__ __forceinline__ void rank_and_place(const unsigned (&bits)[NI], const bool (&has)[NI], const RankIdList L, u64* key,
+                                               unsigned char* keep, int* s_present, int* s_wsum, int npad, int k, long long out0,
+                                               unsigned* out_scores, long long* out_idx, int* out_pos) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    const int pos = tid + j * T;
+    if (pos < npad) {
+      unsigned hi = RANK_MISSING, lo = (unsigned)pos;
+      if (has[j]) {
+        const unsigned u = bits[j];
+        hi = rank_score_key(u);
+        if (u == 0x80000000u) lo |= RANK_NEGZERO;
+      }
+      mine += hi != RANK_MISSING;                // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
+      key[pos] = ((u64)hi << 32) | lo;
+    }
+  }
+  if (mine) atomicAdd(s_present, mine);
+  __syncthreads();
+  block_bitonic_sort(key, npad, RankBefore<RankIdList>{L});
+  const int present = *s_present;
+  for (int r = tid; r < npad; r += T) keep[r] = r < present && (r == 0 || L.at(key[r - 1]) != L.at(key[r]));
+  __syncthreads();
+  const KeepScan sc = rank_keep_scan(keep, npad, s_wsum);
+  int o = sc.slot;
+  for (int r = sc.lo; r < sc.hi && o < k; ++r)
+    if (keep[r]) {
+      const u64 kr = key[r];
+      out_scores[out0 + o] = rank_key_score(kr);
+      out_idx[out0 + o] = L.at(kr);
+      if (out_pos) out_pos[out0 + o] = (int)((unsigned)kr & RANK_POS_MASK);
+      ++o;
+    }
+  rank_fill_tail(sc.total, k, out0, out_scores, out_idx, out_pos);
+}
+
+// the list shapes cor_rescore_topk and cor_rescore_topk_i8 accept (also their workspace query: 0 bytes or the error)
+inline int rescore_shape_check(int Bq, int kin, int k) {
+  if (Bq < 0 || kin < 1 || k < 1 || k > COR_TOPK_KMAX) return COR_EINVAL;
+  if (kin > COR_MERGE_NMAX) return COR_ENOSUPPORT;
+  return 0;
 }
 
 // id -> on_hit(segment, local row) and true, or false: the id lies in no segment. Every segment is visited (the table sits in scalar

@@ -20,12 +20,6 @@ namespace {
 constexpr int RI_CMAX = 256;                   // embedding width limit of the searches
 constexpr int RI_NI = 4;                       // candidates per thread, loads interleaved
 
-struct RiList {
-  const long long* ids;   // this query's kin candidates
-  __device__ __forceinline__ long long operator()(unsigned pos) const { return ids[pos]; }
-  __device__ __forceinline__ long long at(u64 key) const { return ids[(unsigned)key & RANK_POS_MASK]; }
-};
-
 __global__ __launch_bounds__(1024) void rescore_topk_i8_kernel(const float* __restrict__ Q, const signed char* __restrict__ G,
                                                                const float* __restrict__ gscale, int Ng, int C, long long g_offset,
                                                                const long long* __restrict__ cand, int kin, int npad, int k,
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(1024) void rescore_topk_i8_kernel(const float* __re
   unsigned char* keep = ri_lds + 8 * (size_t)npad + RI_CMAX;       // [npad]
   const int tid = threadIdx.x, T = blockDim.x;
   const long long out0 = (long long)blockIdx.x * k;
-  const RiList L{cand + (long long)blockIdx.x * kin};
+  const RankIdList L{cand + (long long)blockIdx.x * kin};
 
   // 0. the query, quantised by the first wave (T >= 64)
   if (tid < 64) {
@@ -98,60 +92,23 @@ __global__ __launch_bounds__(1024) void rescore_topk_i8_kernel(const float* __re
     }
   }
 
-  // 2. keys and rank
-  int mine = 0;
+  // 2. rank and 3. place (ranklist.h)
+  unsigned bits[RI_NI]; bool has[RI_NI];
 #pragma unroll
-  for (int j = 0; j < RI_NI; ++j) {
-    const int pos = tid + j * T;
-    if (pos < npad) {
-      unsigned hi = RANK_MISSING, lo = (unsigned)pos;
-      if (row[j]) {
-        const float sc = ((float)d[j] * qscale) * gs[j];
-        const unsigned u = __float_as_uint(sc);
-        hi = rank_score_key(u);
-        if (u == 0x80000000u) lo |= RANK_NEGZERO;
-      }
-      mine += hi != RANK_MISSING;                // counted by the KEY: the first `present` ranks are exactly the keys below MISSING
-      key[pos] = ((u64)hi << 32) | lo;
-    }
-  }
-  if (mine) atomicAdd(&s_present, mine);
-  __syncthreads();
-  block_bitonic_sort(key, npad, RankBefore<RiList>{L});
-  const int present = s_present;
-
-  // 3. one entry per id (the first of every run of equal ids: the lowest position), the first k of them
-  for (int r = tid; r < npad; r += T) keep[r] = r < present && (r == 0 || L.at(key[r - 1]) != L.at(key[r]));
-  __syncthreads();
-  const KeepScan sc = rank_keep_scan(keep, npad, s_wsum);
-  int o = sc.slot;
-  for (int r = sc.lo; r < sc.hi && o < k; ++r)
-    if (keep[r]) {
-      const u64 kr = key[r];
-      out_scores[out0 + o] = rank_key_score(kr);
-      out_idx[out0 + o] = L.at(kr);
-      if (out_pos) out_pos[out0 + o] = (int)((unsigned)kr & RANK_POS_MASK);
-      ++o;
-    }
-  rank_fill_tail(sc.total, k, out0, out_scores, out_idx, out_pos);
-}
-
-int rescore_i8_shape_check(int Bq, int kin, int k) {
-  if (Bq < 0 || kin < 1 || k < 1 || k > COR_TOPK_KMAX) return COR_EINVAL;
-  if (kin > COR_MERGE_NMAX) return COR_ENOSUPPORT;
-  return 0;
+  for (int j = 0; j < RI_NI; ++j) { bits[j] = __float_as_uint(((float)d[j] * qscale) * gs[j]); has[j] = row[j] != nullptr; }
+  rank_and_place<RI_NI>(bits, has, L, key, keep, &s_present, s_wsum, npad, k, out0, out_scores, out_idx, out_pos);
 }
 
 }  // namespace
 
-extern "C" long cor_rescore_i8_workspace_bytes(int Bq, int kin, int k) { return rescore_i8_shape_check(Bq, kin, k); }
+extern "C" long cor_rescore_i8_workspace_bytes(int Bq, int kin, int k) { return rescore_shape_check(Bq, kin, k); }
 
 extern "C" int cor_rescore_topk_i8(const float* Q, const signed char* Gq, const float* gscale, int Bq, int Ng, int C, long long g_offset,
                                    const long long* cand, int kin, int k, float* out_scores, long long* out_idx, int* out_pos, void* workspace,
                                    void* stream) {
   (void)workspace;
   if (!Q || !cand || !out_scores || !out_idx || ((!Gq || !gscale) && Ng > 0) || Ng < 0 || C < 1) return COR_EINVAL;
-  const int rc = rescore_i8_shape_check(Bq, kin, k);
+  const int rc = rescore_shape_check(Bq, kin, k);
   if (rc) return rc;
   if (C > RI_CMAX || C % 16 != 0) return COR_ENOSUPPORT;
   if (Bq == 0) return 0;

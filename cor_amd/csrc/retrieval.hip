@@ -287,8 +287,6 @@ __global__ void __launch_bounds__(256, 1) sim_topk_v2(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-
-// ---------------------------------------------------------------------------------------------------------------------
 // v3 (16-bit galleries, C = 256, every shard size): threshold-and-append with EXACT re-scoring.
 // Per-lane sorted lists cost one divergent insertion bubble (~500 wave cycles) per accepted score, and a stream of n scores
 // accepts ~k ln(n/k) of them per lane: measured 9x the MFMA time. Instead, four launches (sim_prep + these three):
@@ -356,6 +354,89 @@ __device__ __forceinline__ float key2f_floor(unsigned key) {      // the smalles
   return __uint_as_float(u);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// SHARED SCAN STEPS: the one copy of what sim_scan (16-bit rows, C = 256), sim_wide_scan (fp32 rows or C != 256) and sim_i8_scan (int8 rows)
+// do alike around their tile loops. Forced inline, values by reference: the callers' register arrays stay in registers. They live in this
+// file because the fmaxf / fminf folding depends on its -fno-honor-nans (Makefile). DESIGN.md lists which kernel uses which step, and the
+// sites that keep their own lines because the shared form compiled to more registers there.
+// The filter rule (include/cor_amd.h): a query with label ql < 0 is unrestricted; otherwise COR_FILTER_EQ (ne == 0) allows the rows that
+// carry ql, COR_FILTER_NE the rows that do not. Callers keep their own outer terms (!FILTER, rlab == nullptr, the row-inside-the-shard tests).
+__device__ __forceinline__ bool label_allows(int label, int ql, int ne) { return ql < 0 || ((label == ql) != (ne != 0)); }
+// the same for row g of a label array: an unrestricted query reads no label (rlab may be null then)
+__device__ __forceinline__ bool row_allowed(const int* __restrict__ rlab, int g, int ql, int ne) { return ql < 0 || label_allows(rlab[g], ql, ne); }
+
+// p[row .. row + 3] of an array of Ng elements as one 16-byte load (row % 4 == 0, p 16-byte aligned); the ragged end element by element,
+// zero beyond Ng: nothing is read past the array. V4: the caller's 16-byte vector type.
+template <typename V4, typename T, typename I> __device__ __forceinline__ V4 load4_or_zero(const T* __restrict__ p, I row, int Ng) {
+  typedef T vec4 __attribute__((ext_vector_type(4)));
+  vec4 v;
+  if (row + 4 <= Ng) v = *(const vec4*)(p + row);
+  else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = row + e < Ng ? p[row + e] : T(0);
+  }
+  return __builtin_bit_cast(V4, v);
+}
+
+// The tiles slice `split` of nsplit walks, t = t0 .. t1 - 1 -> tile(t): a contiguous run of tiles_per_split tiles, or with FILTER the
+// interleaved tiles split, split + nsplit, ... (a class-sorted gallery spreads over every slice, stream and sample group).
+template <bool FILTER> struct SliceWalk {
+  int t0, t1, split, nsplit;
+  __device__ __forceinline__ SliceWalk(int split_, int nsplit_, int tiles_per_split, int ntiles) : split(split_), nsplit(nsplit_) {
+    t0 = FILTER ? 0 : split * tiles_per_split;
+    t1 = FILTER ? cdiv(ntiles - split, nsplit) : min(t0 + tiles_per_split, ntiles);
+  }
+  __device__ __forceinline__ int tile(int t) const { return FILTER ? split + t * nsplit : t; }
+};
+
+// FILTER SAMPLE: a sample group's four best allowed scores, descending. offer is branch-free (-inf, a masked score, changes nothing);
+// store writes the four keys to the group's four slots (16-byte aligned).
+struct Best4 {
+  float v[4];
+  __device__ __forceinline__ void clear() { v[0] = v[1] = v[2] = v[3] = -INFINITY; }
+  __device__ __forceinline__ void offer(float x) {
+    v[3] = fmaxf(v[3], fminf(v[2], x));
+    v[2] = fmaxf(v[2], fminf(v[1], x));
+    v[1] = fmaxf(v[1], fminf(v[0], x));
+    v[0] = fmaxf(v[0], x);
+  }
+  __device__ __forceinline__ void store(unsigned* sg4) const { *(uint4*)sg4 = make_uint4(f2key(v[0]), f2key(v[1]), f2key(v[2]), f2key(v[3])); }
+};
+// GROUP SAMPLE (the distinct routes): a sample group's NV best allowed scores, descending, each with the ROW behind it (NV = 1, or 4 with
+// FILTER). A masked / out-of-shard score is -inf and never kept; an empty slot holds (-inf, row 0). Offers are rare after warm-up: the
+// callers put one wave-uniform test of the tile maximum against v[NV - 1] in front. store: keys to sg, rows to sgrow, at the same index.
+template <int NV> struct BestRows {
+  float v[NV]; int row[NV];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { v[j] = -INFINITY; row[j] = 0; }
+  }
+  __device__ __forceinline__ void offer(float x, int r) {
+    if (x > v[NV - 1]) { v[NV - 1] = x; row[NV - 1] = r; }
+#pragma unroll
+    for (int j = NV - 1; j > 0; --j) {
+      const float s0 = v[j - 1], s1 = v[j];
+      const int i0 = row[j - 1], i1 = row[j];
+      const bool up = s1 > s0;
+      v[j - 1] = up ? s1 : s0; v[j] = up ? s0 : s1;
+      row[j - 1] = up ? i1 : i0; row[j] = up ? i0 : i1;
+    }
+  }
+  __device__ __forceinline__ void store(unsigned* sg, int* sgrow, long at) const {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { sg[at + j] = f2key(v[j]); sgrow[at + j] = row[j]; }
+  }
+};
+
+// APPEND of sim_wide_scan / sim_i8_scan. The threshold a lane compares with: tau_q, floored so that a masked -inf score stays out of the
+// lists when tau_q is -inf; a padding lane (not `real`: q >= Bq or an idle wave) gets +inf: it never appends and never reads tau.
+__device__ __forceinline__ float append_threshold(bool real, const float* tau, int q) { return real ? fmaxf(tau[q], -3.0e38f) : INFINITY; }
+// One (score bits, row) entry into the private list dst [cap] of a stream; n keeps counting past cap (the selection sees the overflow).
+__device__ __forceinline__ void append_entry(uint2* dst, int& n, int cap, float score, int row) {
+  if (n < cap) dst[n] = make_uint2(__float_as_uint(score), (unsigned)row);
+  ++n;
+}
+
 // WIDE (33 <= k <= 256, see the wide-k route below): SAMPLE stores every (slice, lane quarter) group maximum on its own, sg[q * Bqp + split * 4 + rq]
 // with Bqp = the group count (no super-group folding: tau needs >= k groups); APPEND reads tau_q from a.tau (sim_tau_wide ranked the groups).
 // FILTER (the filtered wide route, any k; implies WIDE): a disallowed score is -inf before every maximum and compare. Slice `split` walks the
@@ -396,14 +477,14 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   unsigned st_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) st_off[i] = (unsigned)(st_e * 512 + ((st_sl ^ ((8 * wave + 2 * i + st_e) & 15)) << 4));
-  // super-tiles of 64 rows (FILTER: t counts the slice's walked super-tiles, super-tile split + t * nsplit)
-  const int t0 = FILTER ? 0 : split * a.tiles_per_split, t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
-  auto walked = [&](int t) { return FILTER ? split + t * a.nsplit : t; };
+  // super-tiles of 64 rows (SliceWalk; FILTER: t counts the slice's walked super-tiles)
+  const SliceWalk<FILTER> walk(split, a.nsplit, a.tiles_per_split, a.ntiles);
+  const int t0 = walk.t0, t1 = walk.t1;
   auto issue = [&](int t) {
 #ifdef COR_PROBES
-    const long g0 = (long)((a.probe_same & 1) ? (walked(t) & 7) : walked(t)) * a.tile_stride * 64;
+    const long g0 = (long)((a.probe_same & 1) ? (walk.tile(t) & 7) : walk.tile(t)) * a.tile_stride * 64;
 #else
-    const long g0 = (long)walked(t) * a.tile_stride * 64;
+    const long g0 = (long)walk.tile(t) * a.tile_stride * 64;
 #endif
     const unsigned dst = lds0 + ((t - t0) % NS) * STILE + wbase;
     if (g0 + 64 <= a.Ng) {                             // (scalar) every row of the super-tile is inside the shard
@@ -436,11 +517,8 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   if constexpr (FILTER) {
     int* lab_w = (int*)(smem + NS * STILE);
     for (int i = tid; i < (t1 - t0) * 16; i += 512) {
-      const long row = (long)walked(t0 + (i >> 4)) * a.tile_stride * 64 + 4 * (i & 15);
-      int4 v;
-      if (row + 4 <= a.Ng) v = *(const int4*)(a.rlab + row);
-      else { v.x = row < a.Ng ? a.rlab[row] : 0; v.y = row + 1 < a.Ng ? a.rlab[row + 1] : 0; v.z = row + 2 < a.Ng ? a.rlab[row + 2] : 0; v.w = 0; }
-      *(int4*)(lab_w + 4 * i) = v;
+      const long row = (long)walk.tile(t0 + (i >> 4)) * a.tile_stride * 64 + 4 * (i & 15);
+      *(int4*)(lab_w + 4 * i) = load4_or_zero<int4>(a.rlab, row, a.Ng);
     }
     __syncthreads();
   }
@@ -480,9 +558,9 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   float tau[NQ], gmax[NQ];
   int ncand[NQ];
   int ql[NQ];                                          // FILTER: the lane's query labels (< 0: unrestricted)
-  float top4[NQ][4];                                   // FILTER SAMPLE: the group's four best allowed scores, descending
-  constexpr int NV = GROUP && FILTER ? 4 : 1;          // GROUP SAMPLE: the group's NV best allowed scores, descending, and their rows
-  float gv[NQ][NV]; int gr[NQ][NV];
+  Best4 top4[NQ];                                      // FILTER SAMPLE: the group's four best allowed scores (Best4)
+  constexpr int NV = GROUP && FILTER ? 4 : 1;          // GROUP SAMPLE: the group's NV best allowed scores and their rows (BestRows)
+  BestRows<NV> best[NQ];
   const int nstreams = a.nsplit * 4;                   // a stream = (query, gallery slice, lane quarter rq)
 #pragma unroll
   for (int qb = 0; qb < NQ; ++qb) {
@@ -495,13 +573,9 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
     gmax[qb] = -INFINITY; ncand[qb] = 0;
     if constexpr (FILTER) {
       ql[qb] = a.qlab[min(q0 + qb * 16 + n16, a.Bq - 1)];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) top4[qb][j] = -INFINITY;
+      top4[qb].clear();
     }
-    if constexpr (GROUP) {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) { gv[qb][j] = -INFINITY; gr[qb][j] = 0; }
-    }
+    if constexpr (GROUP) best[qb].clear();
   }
   // read address of 32-deep K-step kk, row block rb: row rb * 16 + n16, chunk (4 kk + rq) ^ n16 = ((kk ^ (n16 >> 2)) << 2) | (rq ^ (n16 & 3)): one XOR
   // per read. Conflict-free ds_read_b128: every 16-lane service group holds 16 different n16 (the two K quarters it mixes map onto disjoint slots).
@@ -537,6 +611,7 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
+            // label_allows, spelled out: as a call it changed the epilogue's code and spilled six VGPRs into the tile loop
             const bool allow = (ql[qb] < 0 || ((lr[rb][e] == ql[qb]) != (a.ne != 0))) && (lim >= 32 || 16 * rb + r4 + e < lim);
             acc[qb][rb][e] = allow ? acc[qb][rb][e] : -INFINITY;
             ok = ok || allow;
@@ -546,62 +621,32 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
       tmax = max3f(tmax, acc[qb][0][3], acc[qb][1][0]);
       tmax = max3f(tmax, acc[qb][1][1], acc[qb][1][2]);
       tmax = fmaxf(tmax, acc[qb][1][3]);
-      if constexpr (SAMPLE && GROUP) {                 // (score, row) into the sorted NV; rare after warm-up: one wave-uniform test skips it
-        if (__builtin_amdgcn_ballot_w64(tmax > gv[qb][NV - 1]) != 0) {
+      if constexpr (SAMPLE && GROUP) {                 // rare after warm-up: one wave-uniform test skips the offers
+        if (__builtin_amdgcn_ballot_w64(tmax > best[qb].v[NV - 1]) != 0) {
 #pragma unroll
           for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float x = acc[qb][rb][e];          // masked / out-of-shard scores are -inf: never stored
-              if (x > gv[qb][NV - 1]) { gv[qb][NV - 1] = x; gr[qb][NV - 1] = g0 + 16 * rb + r4 + e; }
-#pragma unroll
-              for (int j = NV - 1; j > 0; --j) {
-                const float s0 = gv[qb][j - 1], s1 = gv[qb][j];
-                const int i0 = gr[qb][j - 1], i1 = gr[qb][j];
-                const bool up = s1 > s0;
-                gv[qb][j - 1] = up ? s1 : s0; gv[qb][j] = up ? s0 : s1;
-                gr[qb][j - 1] = up ? i1 : i0; gr[qb][j] = up ? i0 : i1;
-              }
-            }
+            for (int e = 0; e < 4; ++e) best[qb].offer(acc[qb][rb][e], g0 + 16 * rb + r4 + e);      // masked / out-of-shard scores are -inf
         }
-      } else if (SAMPLE && FILTER) {                   // insertion of each allowed score into the sorted four (-inf: no change)
+      } else if (SAMPLE && FILTER) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float x = acc[qb][rb][e];
-            top4[qb][3] = fmaxf(top4[qb][3], fminf(top4[qb][2], x));
-            top4[qb][2] = fmaxf(top4[qb][2], fminf(top4[qb][1], x));
-            top4[qb][1] = fmaxf(top4[qb][1], fminf(top4[qb][0], x));
-            top4[qb][0] = fmaxf(top4[qb][0], x);
-          }
+          for (int e = 0; e < 4; ++e) top4[qb].offer(acc[qb][rb][e]);
       } else if (SAMPLE) {
         gmax[qb] = fmaxf(gmax[qb], tmax);
-      } else if (FILTER) {                             // the allow predicate decides (tau_q = -inf admits every ALLOWED row, never a masked one)
-        if (__builtin_amdgcn_ballot_w64(ok && tmax >= tau[qb]) != 0) {
-          int q = q0 + qb * 16 + n16;
-          asm volatile("" : "+v"(q));
-          if (ok && tmax >= tau[qb] && q < a.Bq) {
-            if (ncand[qb] < a.cap) {
-              const long rec = ((long)q * nstreams + split * 4 + rq) * a.cap + ncand[qb];
-              f32x4* dst = (f32x4*)(a.rec_s + rec * 8);
-              dst[0] = acc[qb][0]; dst[1] = acc[qb][1];  // masked slots are -inf: sim_final_wide skips them
-              a.rec_g[rec] = g0;
-            }
-            ++ncand[qb];
-          }
-        }
-      } else if (__builtin_amdgcn_ballot_w64(tmax >= tau[qb]) != 0) {
+      } else if (auto pass = [&] { return FILTER ? ok && tmax >= tau[qb] : tmax >= tau[qb]; }; __builtin_amdgcn_ballot_w64(pass()) != 0) {
         // Some lane of the wave has a candidate in this tile. Testing the registers one by one cost ~80 instructions per triggered tile
         // (70 us of a 270-us scan in round 2); instead a lane whose tile maximum passes appends its WHOLE 8-score column as one record
         // (2 x 16-byte stores + the tile's first row) to its private stream list, and sim_final filters the records against tau.
+        // FILTER: the allow predicate decides too (tau_q = -inf admits every ALLOWED row, never a masked one)
         int q = q0 + qb * 16 + n16;
         asm volatile("" : "+v"(q));                    // opaque: keeps the list address arithmetic HERE (hoisted out of the tile loop
-        if (tmax >= tau[qb] && q < a.Bq) {             // it was spilled, and a spill reload inside the loop drains the DMA ring)
+        if (pass() && q < a.Bq) {                      // it was spilled, and a spill reload inside the loop drains the DMA ring)
           if (ncand[qb] < a.cap) {
             const long rec = ((long)q * nstreams + split * 4 + rq) * a.cap + ncand[qb];
             f32x4* dst = (f32x4*)(a.rec_s + rec * 8);
-            dst[0] = acc[qb][0]; dst[1] = acc[qb][1];
+            dst[0] = acc[qb][0]; dst[1] = acc[qb][1];  // FILTER: masked slots are -inf, sim_final_wide skips them
             a.rec_g[rec] = g0;
           }
           ++ncand[qb];
@@ -662,7 +707,7 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
 #endif
     SC_STAMP(2);
     const char* buf = smem + ((t - t0) % NS) * STILE;
-    const int g0 = walked(t) * a.tile_stride * 64, lo = (t - t0) * 64;
+    const int g0 = walk.tile(t) * a.tile_stride * 64, lo = (t - t0) * 64;
     if (active) {
       if (late && g_pending >= 0) epilogue(g_pending, lo_pending);
       SC_STAMP(3);
@@ -685,14 +730,8 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
     for (int qb = 0; qb < NQ; ++qb) {
       const int q = q0 + qb * 16 + n16;
       if (q < a.Bq) {
-        if constexpr (SAMPLE && GROUP) {
-#pragma unroll
-          for (int j = 0; j < NV; ++j) {
-            const long at = (long)q * a.Bqp + (split * 4 + rq) * NV + j;
-            a.sg[at] = f2key(gv[qb][j]); a.sgrow[at] = gr[qb][j];
-          }
-        } else if (SAMPLE && FILTER)
-          *(uint4*)(a.sg + (long)q * a.Bqp + (split * 4 + rq) * 4) = make_uint4(f2key(top4[qb][0]), f2key(top4[qb][1]), f2key(top4[qb][2]), f2key(top4[qb][3]));
+        if constexpr (SAMPLE && GROUP) best[qb].store(a.sg, a.sgrow, (long)q * a.Bqp + (split * 4 + rq) * NV);
+        else if (SAMPLE && FILTER) top4[qb].store(a.sg + (long)q * a.Bqp + (split * 4 + rq) * 4);
         else if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
         else if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
         else a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb];
@@ -1920,7 +1959,7 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
                                  unsigned long long* keys, int* hist, float* out_s, long long* out_i, const int* rlab = nullptr, int ql = -1,
                                  int ne = 0) {
   brute_force_by<FILTER>([&](int g) { return chain_score_c<TG>(G, g, C, qs); },
-                         [&](int g) { return !FILTER || ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
+                         [&](int g) { return !FILTER || row_allowed(rlab, g, ql, ne); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
                          out_s, out_i);
 }
 
@@ -1929,7 +1968,7 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
 //   SAMPLE: tiles t * tile_stride of the slice; the group (slice, lane half h) keeps its maximum: sg[q * ngroups + split * 2 + h].
 //   APPEND: every tile of the slice; scores >= tau_q go to the private list of stream (q, slice, h) as (score bits, row) entries.
 //   FILTER: disallowed scores are -inf (never a group's best, never >= tau_q), slice `split` walks the tiles split, split + nsplit, ... and
-//   SAMPLE keeps the group's four best allowed scores, sg[q * ngroups + (split * 2 + h) * 4 + j] (ngroups counts the four), as sim_scan does.
+//   SAMPLE keeps the group's four best allowed scores (Best4), sg[q * ngroups + (split * 2 + h) * 4 + j] (ngroups counts the four).
 struct WideScanArgs {
   int Bq, Ng, C, nqt, nsplit, tiles_per_split, ntiles, tile_stride;
   unsigned* sg; int ngroups;
@@ -1937,7 +1976,7 @@ struct WideScanArgs {
   const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
   int* sgrow;                                        // GROUP SAMPLE: the shard row behind every stored sample value
 };
-//   GROUP (distinct-group route, SAMPLE only): NV = 1 (4 with FILTER) best allowed scores per group WITH their rows (a.sgrow), as sim_scan does.
+//   GROUP (distinct-group route, SAMPLE only): NV = 1 (4 with FILTER) best allowed scores per group WITH their rows (BestRows, a.sgrow).
 template <typename TG, bool SAMPLE, bool FILTER = false, bool GROUP = false>
 __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q, const TG* __restrict__ G, const WideScanArgs a) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -1959,22 +1998,19 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       else qf[c] = q_frag16<TG>(qrow, c, h);
     }
   }
-  // padding lanes (q >= Bq) never append; the floor keeps masked -inf scores out of the lists when tau_q is -inf
-  const float tq = SAMPLE ? 0.f : (q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
+  const float tq = SAMPLE ? 0.f : append_threshold(q < a.Bq, a.tau, q);
   const int stream = split * 2 + h, nstreams = 2 * a.nsplit;
   float gmax = -INFINITY;
   int n = 0;
   const int ql = FILTER ? a.qlab[min(q, a.Bq - 1)] : 0;
-  float top4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  Best4 top4;
+  top4.clear();
   constexpr int NV = GROUP && FILTER ? 4 : 1;
-  float gv[NV]; int gr[NV];
-  if constexpr (GROUP) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) { gv[j] = -INFINITY; gr[j] = 0; }
-  }
-  const int t0 = FILTER ? 0 : split * a.tiles_per_split, t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
-  for (int t = t0; t < t1; ++t) {
-    const int g0 = (FILTER ? split + t * a.nsplit : t) * a.tile_stride * 32;
+  BestRows<NV> best;
+  if constexpr (GROUP) best.clear();
+  const SliceWalk<FILTER> walk(split, a.nsplit, a.tiles_per_split, a.ntiles);
+  for (int t = walk.t0; t < walk.t1; ++t) {
+    const int g0 = walk.tile(t) * a.tile_stride * 32;
     const char* grow = (const char*)(G + (long)min(g0 + r, Ng - 1) * C) + 16 * h;
     f32x16 acc;
 #pragma unroll
@@ -2001,7 +2037,8 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       sc[e] = g0 + (e & 3) + 8 * (e >> 2) + 4 * h < Ng ? acc[e] : -INFINITY;
       tmax = fmaxf(tmax, sc[e]);
     }
-    if constexpr (FILTER) {                            // labels of rows g0 + 8 j + 4 h + i (score e = 4 j + i)
+    if constexpr (FILTER) {                            // labels of rows g0 + 8 j + 4 h + i (score e = 4 j + i). load4_or_zero and label_allows,
+                                                       // spelled out: the shared forms cost the FILTER instantiations four more VGPRs
       tmax = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -2018,46 +2055,26 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       }
     }
     if constexpr (SAMPLE && GROUP) {
-      if (__builtin_amdgcn_ballot_w64(tmax > gv[NV - 1]) != 0) {
+      if (__builtin_amdgcn_ballot_w64(tmax > best.v[NV - 1]) != 0) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          if (sc[e] > gv[NV - 1]) { gv[NV - 1] = sc[e]; gr[NV - 1] = g0 + (e & 3) + 8 * (e >> 2) + 4 * h; }
-#pragma unroll
-          for (int j = NV - 1; j > 0; --j) {
-            const float s0 = gv[j - 1], s1 = gv[j];
-            const int i0 = gr[j - 1], i1 = gr[j];
-            const bool up = s1 > s0;
-            gv[j - 1] = up ? s1 : s0; gv[j] = up ? s0 : s1;
-            gr[j - 1] = up ? i1 : i0; gr[j] = up ? i0 : i1;
-          }
-        }
+        for (int e = 0; e < 16; ++e) best.offer(sc[e], g0 + (e & 3) + 8 * (e >> 2) + 4 * h);
       }
     } else if (SAMPLE && FILTER) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        top4[3] = fmaxf(top4[3], fminf(top4[2], sc[e]));
-        top4[2] = fmaxf(top4[2], fminf(top4[1], sc[e]));
-        top4[1] = fmaxf(top4[1], fminf(top4[0], sc[e]));
-        top4[0] = fmaxf(top4[0], sc[e]);
-      }
+      for (int e = 0; e < 16; ++e) top4.offer(sc[e]);
     } else if (SAMPLE) {
       gmax = fmaxf(gmax, tmax);
     } else if (__builtin_amdgcn_ballot_w64(tmax >= tq) != 0) {
       uint2* dst = a.lst + ((long)q * nstreams + stream) * a.cap;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        if (sc[e] >= tq) {
-          if (n < a.cap) dst[n] = make_uint2(__float_as_uint(sc[e]), (unsigned)(g0 + (e & 3) + 8 * (e >> 2) + 4 * h));
-          ++n;
-        }
+        if (sc[e] >= tq) append_entry(dst, n, a.cap, sc[e], g0 + (e & 3) + 8 * (e >> 2) + 4 * h);
       }
     }
   }
   if (q < a.Bq) {
-    if constexpr (SAMPLE && GROUP) {
-#pragma unroll
-      for (int j = 0; j < NV; ++j) { a.sg[(long)q * a.ngroups + stream * NV + j] = f2key(gv[j]); a.sgrow[(long)q * a.ngroups + stream * NV + j] = gr[j]; }
-    } else if (SAMPLE && FILTER) *(uint4*)(a.sg + (long)q * a.ngroups + stream * 4) = make_uint4(f2key(top4[0]), f2key(top4[1]), f2key(top4[2]), f2key(top4[3]));
+    if constexpr (SAMPLE && GROUP) best.store(a.sg, a.sgrow, (long)q * a.ngroups + stream * NV);
+    else if (SAMPLE && FILTER) top4.store(a.sg + (long)q * a.ngroups + stream * 4);
     else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
     else a.cnt[(long)q * nstreams + stream] = n;
   }
@@ -2390,7 +2407,7 @@ __device__ void distinct_brute_force(const TG* __restrict__ G, int Ng, int C, co
                                      float* sl_s, int* sl_i, int* flag, unsigned long long* keys, unsigned long long* k2, unsigned* found, int* hist,
                                      float* out_s, long long* out_i, const int* __restrict__ rlab, int ql, int ne) {
   distinct_brute_force_by([&](int g) { return chain_score_c<TG>(G, g, C, qs); },
-                          [&](int g) { return rlab == nullptr || ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, grp, sl_s, sl_i, flag,
+                          [&](int g) { return rlab == nullptr || row_allowed(rlab, g, ql, ne); }, Ng, k, g_offset, grp, sl_s, sl_i, flag,
                           keys, k2, found, hist, out_s, out_i);
 }
 
@@ -2805,12 +2822,12 @@ constexpr int I8_TILE_SLOTS = 64 * 17;                 // 64 rows x the largest 
 // FILTER (cor_similarity_topk_i8_filtered): the tile's 64 row labels travel with its scales (threads 16..31 fetch them, four each, into the
 // same prefetch register; tile_gs[.][16 + i] holds labels 4 i .. 4 i + 3, 0 beyond Ng where the row test already masks), each lane keeps the
 // labels of its four queries, and a disallowed score is -inf: never among a group's best, never appended. The bound test needs no label
-// (it is >= every score of the four rows, allowed or not). SAMPLE keeps the group's four best allowed scores (sim_wide_scan's insertion;
+// (it is >= every score of the four rows, allowed or not). SAMPLE keeps the group's four best allowed scores (Best4's insertion;
 // sg[q * ngroups + stream * 4 + j], ngroups counts the four), and slice `split` walks the tiles split, split + nsplit, ...: the allowed rows
 // of a class-sorted gallery spread over every stream and every sample group.
 // GROUP (cor_similarity_topk_i8_distinct, SAMPLE only): every stored sample value travels with the ROW that produced it (a.sgrow, parallel
 // to sg): the lane-quarter group's maximum and its row, with FILTER its four best allowed scores and their rows through one insertion
-// network (sim_wide_scan's). Invariant: every sgrow entry written is a row in [0, Ng): a row is kept only behind `gr + e < Ng` (the ragged
+// network (BestRows's, written out here with Best4's: the structs cost these instantiations a VGPR). Invariant: every sgrow entry written is a row in [0, Ng): a row is kept only behind `gr + e < Ng` (the ragged
 // last tile's rows beyond Ng never are), and a slot that no score reached holds (-inf, row 0); sim_tau_distinct dereferences only the
 // rows behind values above key(-inf).
 template <bool SAMPLE, bool FULL, bool FILTER = false, bool GROUP = false>
@@ -2841,8 +2858,7 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
       if (active && (FULL || ks * 4 + rq < nch)) qf[j][ks] = *(const i32x4*)(qrow + ks * 64 + rq * 16);
     }
     qs[j] = active ? a.qscale[min(q, a.Bq - 1)] : 0.f;
-    // padding lanes (q >= Bq) never append; the floor keeps masked -inf scores out of the lists when tau_q is -inf
-    tq[j] = SAMPLE ? 0.f : (active && q < a.Bq ? fmaxf(a.tau[q], -3.0e38f) : INFINITY);
+    tq[j] = SAMPLE ? 0.f : append_threshold(active && q < a.Bq, a.tau, q);
     gmax[j] = -INFINITY;
     n[j] = 0;
     if constexpr (GROUP) {
@@ -2864,32 +2880,15 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
     const int i = tid + 512 * p, r = i / nch, ch = i - r * nch;
     slot[p] = r < 64 ? r * stride + (ch ^ (r & xmask)) : -1;
   }
-  // the slice's tiles: t0 .. t1 - 1 of the contiguous walk, tile(t) = t; FILTER: the interleaved walk, tile(t) = split + t * nsplit
-  const int t0 = FILTER ? 0 : split * a.tiles_per_split;
-  const int t1 = FILTER ? cdiv(a.ntiles - split, a.nsplit) : min(t0 + a.tiles_per_split, a.ntiles);
-  auto tile_of = [&](int t) { return FILTER ? split + t * a.nsplit : t; };
+  const SliceWalk<FILTER> walk(split, a.nsplit, a.tiles_per_split, a.ntiles);
+  const int t0 = walk.t0, t1 = walk.t1;
   uint4 pre[2];
   f32x4 pre_gs = {0.f, 0.f, 0.f, 0.f};
   auto fetch = [&](int t) {
-    t = tile_of(t);
+    t = walk.tile(t);
     const long base = (long)t * a.tile_stride * 64 * C;
-    if (tid < 16) {
-      const int gr = t * a.tile_stride * 64 + 4 * tid;
-      if (gr + 4 <= Ng) pre_gs = *(const f32x4*)(a.gscale + gr);
-      else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pre_gs[e] = gr + e < Ng ? a.gscale[gr + e] : 0.f;
-      }
-    } else if (FILTER && tid < 32) {
-      const int gr = t * a.tile_stride * 64 + 4 * (tid - 16);
-      i32x4 l = {0, 0, 0, 0};
-      if (gr + 4 <= Ng) l = *(const i32x4*)(a.rlab + gr);
-      else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) l[e] = gr + e < Ng ? a.rlab[gr + e] : 0;
-      }
-      pre_gs = __builtin_bit_cast(f32x4, l);
-    }
+    if (tid < 16) pre_gs = load4_or_zero<f32x4>(a.gscale, t * a.tile_stride * 64 + 4 * tid, Ng);
+    else if (FILTER && tid < 32) pre_gs = load4_or_zero<f32x4>(a.rlab, t * a.tile_stride * 64 + 4 * (tid - 16), Ng);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const long off = base + 16L * (tid + 512 * p);
@@ -2908,7 +2907,7 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
     __syncthreads();                                   // the other buffer was last read before this barrier: the next stores are safe
     if (t + 1 < t1) fetch(t + 1);
     if (!active) continue;
-    const int g0 = tile_of(t) * a.tile_stride * 64;
+    const int g0 = walk.tile(t) * a.tile_stride * 64;
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
       const int gr = g0 + 16 * sub + 4 * rq;           // the lane's rows gr .. gr + 3 of this 16-row block
@@ -2937,7 +2936,7 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
           float s[4], smax = -INFINITY;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const bool ok = gr + e < Ng && (ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0)));
+            const bool ok = gr + e < Ng && label_allows(lab[e], ql[j], a.ne);
             s[e] = ok ? ((float)acc[j][e] * qs[j]) * gs[e] : -INFINITY;
             smax = fmaxf(smax, s[e]);
           }
@@ -2965,7 +2964,7 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
           const i32x4 lab = __builtin_bit_cast(i32x4, buf_gs[16 + 4 * sub + rq]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const bool ok = gr + e < Ng && (ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0)));
+            const bool ok = gr + e < Ng && label_allows(lab[e], ql[j], a.ne);
             const float s = ok ? ((float)acc[j][e] * qs[j]) * gs[e] : -INFINITY;
             top4[j][3] = fmaxf(top4[j][3], fminf(top4[j][2], s));
             top4[j][2] = fmaxf(top4[j][2], fminf(top4[j][1], s));
@@ -2988,11 +2987,8 @@ __global__ void __launch_bounds__(512) sim_i8_scan(const signed char* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float s = ((float)acc[j][e] * qs[j]) * gs[e];
-              const bool ok = !FILTER || ql[j] < 0 || ((lab[e] == ql[j]) != (a.ne != 0));
-              if (gr + e < Ng && ok && s >= tq[j]) {
-                if (n[j] < a.cap) dst[n[j]] = make_uint2(__float_as_uint(s), (unsigned)(gr + e));
-                ++n[j];
-              }
+              const bool ok = !FILTER || label_allows(lab[e], ql[j], a.ne);
+              if (gr + e < Ng && ok && s >= tq[j]) append_entry(dst, n[j], a.cap, s, gr + e);
             }
           }
         }
@@ -3058,7 +3054,7 @@ __device__ __forceinline__ void i8_repair_body(const signed char* __restrict__ q
   auto score_at = [&](int g) { return i8_score_at(G, gscale, qv, qs, C, g); };
   if constexpr (FILTER) {
     const int ql = qlab[q];
-    brute_force_by<true>(score_at, [&](int g) { return ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
+    brute_force_by<true>(score_at, [&](int g) { return row_allowed(rlab, g, ql, ne); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
                          out_s + (long)q * k, out_i + (long)q * k);
   } else {
     brute_force_by<false>(score_at, [](int) { return true; }, Ng, k, g_offset, sl_s, sl_i, keys, hist, out_s + (long)q * k, out_i + (long)q * k);
@@ -3097,7 +3093,7 @@ __global__ void __launch_bounds__(256) sim_i8_repair_distinct(const signed char*
   const float qs = qscale[q];
   const int ql = rlab ? qlab[q] : -1;
   distinct_brute_force_by([&](int g) { return i8_score_at(G, gscale, qv, qs, C, g); },
-                          [&](int g) { return ql < 0 || ((rlab[g] == ql) != (ne != 0)); }, Ng, k, g_offset, grp, sl_s, sl_i, flag, keys, k2, found,
+                          [&](int g) { return row_allowed(rlab, g, ql, ne); }, Ng, k, g_offset, grp, sl_s, sl_i, flag, keys, k2, found,
                           hist, out_s + (long)q * k, out_i + (long)q * k);
 }
 

@@ -248,6 +248,28 @@ def _diversify(who, table, dev, scores, idx, k, lam, max_sim, return_pos):
         return ops.diversify_mmr(table, scores, idx, k, lam=lam, max_sim=max_sim, return_pos=return_pos)
 
 
+def _search(shard, who, fns, row_args, queries, k, query_labels, mode, distinct):
+    """The search of GalleryShard and QuantizedShard: fns = the (plain, filtered, distinct) ops, row_args = (rows,) or (rows, scales).
+    Both argument checks come before anything touches the device."""
+    if distinct and shard.groups is None:
+        raise ValueError(f"{who}: distinct=True but the shard has no group ids")
+    if query_labels is not None and shard.labels is None:
+        raise ValueError(f"{who}: query_labels given but the shard has no row labels")
+    q = queries.reshape(-1, queries.shape[-1]).to(shard.rows.device, torch.float32).contiguous()
+    if query_labels is not None:
+        query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
+    if shard.rows.shape[0] == 0:                     # an empty shard (more ranks than gallery rows): all-missing lists, like Ng < k
+        return _missing_lists(q.shape[0], k, q.device)
+    plain, filtered, distinct_fn = fns
+    with _on(shard.rows.device):
+        if distinct:
+            return distinct_fn(q, *row_args, k, shard.groups, None if query_labels is None else shard.labels, query_labels, mode=mode,
+                               g_offset=shard.offset)
+        if query_labels is None:
+            return plain(q, *row_args, k, g_offset=shard.offset)
+        return filtered(q, *row_args, k, shard.labels, query_labels, mode=mode, g_offset=shard.offset)
+
+
 class GalleryShard:
     """Rows [offset, offset + n) of a unit-norm gallery, resident in HBM as fp32 / bf16 / fp16. labels: optional int32[n], one label
     per row (a class, a dataset or a source image id: dataloader.gallery_labels), for filtered searches. groups: optional int32[n],
@@ -271,22 +293,8 @@ class GalleryShard:
         another label) are ranked (ops.similarity_topk_filtered); None: the whole shard.
         distinct: one row per group id of the shard's `groups`, the k best groups (ops.similarity_topk_distinct), with or without the
         filter; idx still names the winning ROW of each group."""
-        if distinct and self.groups is None:
-            raise ValueError("GalleryShard.search: distinct=True but the shard has no group ids")
-        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
-        if query_labels is not None:
-            if self.labels is None:
-                raise ValueError("GalleryShard.search: query_labels given but the shard has no row labels")
-            query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
-        if self.rows.shape[0] == 0:                  # an empty shard (more ranks than gallery rows): all-missing lists, like Ng < k
-            return _missing_lists(q.shape[0], k, q.device)
-        with torch.cuda.device(self.rows.device):
-            if distinct:
-                return ops.similarity_topk_distinct(q, self.rows, k, self.groups, None if query_labels is None else self.labels, query_labels,
-                                                    mode=mode, g_offset=self.offset)
-            if query_labels is None:
-                return ops.similarity_topk(q, self.rows, k, g_offset=self.offset)
-            return ops.similarity_topk_filtered(q, self.rows, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
+        return _search(self, "GalleryShard.search", (ops.similarity_topk, ops.similarity_topk_filtered, ops.similarity_topk_distinct), (self.rows,),
+                       queries, k, query_labels, mode, distinct)
 
     def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int | None = None, return_pos: bool = False):
         """The second stage of a two-stage search: queries f32[Bq,C], cand i64[Bq,kin] global row ids (a coarse search's idx, a union
@@ -417,22 +425,8 @@ class QuantizedShard:
         label, "ne": another label) are ranked (ops.similarity_topk_i8_filtered); ValueError if the shard has no labels.
         distinct: one row per group id of the shard's `groups`, the k best groups (ops.similarity_topk_i8_distinct), with or without the
         filter; idx still names the winning ROW of each group. ValueError if the shard has no group ids."""
-        if distinct and self.groups is None:
-            raise ValueError("QuantizedShard.search: distinct=True but the shard has no group ids")
-        if query_labels is not None and self.labels is None:
-            raise ValueError("QuantizedShard.search: query_labels given but the shard has no row labels")
-        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
-        if query_labels is not None:
-            query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
-        if self.rows.shape[0] == 0:                  # an empty shard: all-missing lists, like Ng < k
-            return _missing_lists(q.shape[0], k, q.device)
-        with _on(self.rows.device):
-            if distinct:
-                return ops.similarity_topk_i8_distinct(q, self.rows, self.scales, k, self.groups, None if query_labels is None else self.labels,
-                                                       query_labels, mode=mode, g_offset=self.offset)
-            if query_labels is None:
-                return ops.similarity_topk_i8(q, self.rows, self.scales, k, g_offset=self.offset)
-            return ops.similarity_topk_i8_filtered(q, self.rows, self.scales, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
+        return _search(self, "QuantizedShard.search", (ops.similarity_topk_i8, ops.similarity_topk_i8_filtered, ops.similarity_topk_i8_distinct),
+                       (self.rows, self.scales), queries, k, query_labels, mode, distinct)
 
     def gallery(self):
         """This shard as a QuantizedGallery over the SAME tensors (nothing is copied): the int8-only gallery with the list stages."""

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Same-process A/B between ANOTHER build of the library (the parent commit's libcor_amd.so) and this one, for changes that must leave
-results and speed as they are. Two case tables: `topk`, the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct), and
-`lists`, the list kernels (cor_merge_topk, cor_rescore_topk, cor_rerank_reciprocal, cor_knn_reciprocal, cor_expand_queries) at the shapes of
-their own bench tools.
+results and speed as they are. Two case tables: `topk`, the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct, and the
+same three over an int8 gallery, quantised once and shared by both builds), and `lists`, the list kernels (cor_merge_topk, cor_rescore_topk,
+cor_rescore_topk_i8, cor_rerank_reciprocal, cor_knn_reciprocal, cor_expand_queries) at the shapes of their own bench tools.
     python tools/topk_family_ab.py PARENT_LIB.so [ROUNDS=5] [OUT=profiles/topk_family_ab.jsonl] [TABLE=topk]
 "This one" is the library cor_amd loads (COR_AMD_LIB selects another build of it).
 Both sides are called through ctypes with preallocated outputs and workspace, so they carry the same host work. Per case: the results of
@@ -30,20 +30,31 @@ for name, sig in nat.SIGNATURES.items():
         getattr(parent, name).restype = C.c_long if name.endswith("_bytes") else C.c_int
 
 
-def caller(lib, route, Q, G, k, groups, own):
-    """(fn, scores, idx): fn() enqueues one search of `route` on the current stream"""
+def quantized(G):
+    """(Gq int8 [Ng,C], gscale f32 [Ng]) of G by this build's cor_quantize_rows_i8: one copy, searched by both builds"""
+    Gq, gs = torch.empty(G.shape, dtype=torch.int8, device=dev), torch.empty((G.shape[0],), device=dev)
+    rc = new.cor_quantize_rows_i8(G.data_ptr(), DT[G.dtype], G.shape[0], G.shape[1], Gq.data_ptr(), gs.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, rc
+    return Gq, gs
+
+
+def caller(lib, route, Q, G, k, groups, own, G8=None):
+    """(fn, scores, idx): fn() enqueues one search of `route` on the current stream; the i8_ routes search G8 = quantized(G)"""
     Bq, Ng, Cc = Q.shape[0], G.shape[0], Q.shape[1]
-    bytes_fn = {"wide": "cor_topk_workspace_bytes", "filtered_ne": "cor_topk_filtered_workspace_bytes", "distinct": "cor_topk_distinct_workspace_bytes"}[route]
-    ws = torch.empty((getattr(lib, bytes_fn)(Bq, Ng, k),), dtype=torch.uint8, device=dev)
+    i8, kind = route.startswith("i8"), route.removeprefix("i8_").replace("i8", "wide")
+    infix = ("i8_" if i8 else "") + {"wide": "", "filtered_ne": "filtered_", "distinct": "distinct_"}[kind]
+    ws = torch.empty((getattr(lib, f"cor_topk_{infix}workspace_bytes")(Bq, Ng, k),), dtype=torch.uint8, device=dev)
     s, i = torch.empty((Bq, k), device=dev), torch.empty((Bq, k), dtype=torch.int64, device=dev)
-    head = (Q.data_ptr(), G.data_ptr(), DT[G.dtype], Bq, Ng, Cc, k, 0)
+    rows = (G8[0].data_ptr(), G8[1].data_ptr()) if i8 else (G.data_ptr(), DT[G.dtype])
+    head = (Q.data_ptr(), *rows, Bq, Ng, Cc, k, 0)
     tail = (s.data_ptr(), i.data_ptr(), ws.data_ptr(), 0)
-    if route == "wide":
-        args, f = head + tail, lib.cor_similarity_topk
-    elif route == "filtered_ne":
-        args, f = head + (groups.data_ptr(), own.data_ptr(), nat.FILTER_NE) + tail, lib.cor_similarity_topk_filtered
+    if kind == "wide":
+        args = head + tail
+    elif kind == "filtered_ne":
+        args = head + (groups.data_ptr(), own.data_ptr(), nat.FILTER_NE) + tail
     else:
-        args, f = head + (groups.data_ptr(), None, None, nat.FILTER_EQ) + tail, lib.cor_similarity_topk_distinct
+        args = head + (groups.data_ptr(), None, None, nat.FILTER_EQ) + tail
+    f = getattr(lib, "cor_similarity_topk" + ("_" + infix[:-1] if infix else ""))
 
     def fn():
         rc = f(*args, torch.cuda.current_stream().cuda_stream)
@@ -126,9 +137,15 @@ def list_caller(lib, kernel, d, Bq, kin, k, variant):
     if kernel == "rescore":
         outs = _outputs(Bq, k, True)
         G = d["G"]
-        args = (d["Q"].data_ptr(), G.data_ptr(), DT[G.dtype], Bq, G.shape[0], G.shape[1], 0, d["idx"].data_ptr(), kin, k, outs[0].data_ptr(), outs[1].data_ptr(),
+        if variant == "i8":                                  # the int8 call over the same rows, quantised once for both builds
+            if "G8" not in d:
+                d["G8"] = quantized(G)
+            rows, f = (d["G8"][0].data_ptr(), d["G8"][1].data_ptr()), lib.cor_rescore_topk_i8
+        else:
+            rows, f = (G.data_ptr(), DT[G.dtype]), lib.cor_rescore_topk
+        args = (d["Q"].data_ptr(), *rows, Bq, G.shape[0], G.shape[1], 0, d["idx"].data_ptr(), kin, k, outs[0].data_ptr(), outs[1].data_ptr(),
                 outs[2].data_ptr(), None)
-        return _enqueue(lib.cor_rescore_topk, args, outs), outs
+        return _enqueue(f, args, outs), outs
     one_i, one_ll = (c.c_int * 1), (c.c_longlong * 1)
     if kernel == "expand":                                   # k is m here
         G = d["G"]
@@ -167,19 +184,24 @@ def ab(desc, fp, outs_p, fn, outs_n):
 
 CASES = [("wide", 512, 1000000, 100, 256, torch.bfloat16), ("wide", 512, 125000, 100, 256, torch.bfloat16), ("wide", 64, 20000, 50, 128, torch.float32),
          ("filtered_ne", 512, 1000000, 100, 256, torch.bfloat16), ("distinct", 512, 1000000, 100, 256, torch.bfloat16),
-         ("distinct", 512, 1000000, 10, 256, torch.bfloat16)]
+         ("distinct", 512, 1000000, 10, 256, torch.bfloat16),
+         ("i8", 512, 1000000, 100, 256, torch.bfloat16), ("i8_filtered_ne", 512, 1000000, 100, 256, torch.bfloat16),
+         ("i8_distinct", 512, 1000000, 100, 256, torch.bfloat16), ("i8_distinct", 512, 1000000, 10, 256, torch.bfloat16),
+         ("filtered_ne", 64, 20000, 50, 128, torch.float32), ("distinct", 64, 20000, 50, 128, torch.float32)]
 # (kernel, Bq, kin, k (expand: m), gallery dtype, variant)
 LIST_CASES = ([("merge", 512, kin, kin, None, v) for kin in (100, 256) for v in ("plain", "distinct")]
-              + [("rescore", 512, kin, 10, dt, "") for kin in (256, 4096) for dt in (torch.float32, torch.bfloat16)]
+              + [("rescore", 512, kin, 10, dt, v) for kin in (256, 4096) for dt in (torch.float32, torch.bfloat16) for v in (("", "i8") if dt == torch.float32 else ("",))]
               + [("rerank", 512, kin, 10, None, "") for kin in (256, 1024)] + [("knn", 0, 20, 20, None, "")]
               + [("expand", 512, 256, m, torch.bfloat16, "") for m in (10, 256)])
 rows, data = [], None
 for route, Bq, Ng, k, Cc, dt in CASES if TABLE == "topk" else []:
     if data is None or data[0] != (Bq, Ng, Cc, dt):
-        data = ((Bq, Ng, Cc, dt), gallery(Bq, Ng, Cc, dt))
+        data, G8 = ((Bq, Ng, Cc, dt), gallery(Bq, Ng, Cc, dt)), None
     Q, G, groups, own = data[1]
-    fp, sp, ip = caller(parent, route, Q, G, k, groups, own)
-    fn, sn, inn = caller(new, route, Q, G, k, groups, own)
+    if route.startswith("i8") and G8 is None:
+        G8 = quantized(G)
+    fp, sp, ip = caller(parent, route, Q, G, k, groups, own, G8)
+    fn, sn, inn = caller(new, route, Q, G, k, groups, own, G8)
     rows.append(ab(dict(route=route, Bq=Bq, Ng=Ng, k=k, C=Cc, dtype=str(dt)), fp, (sp, ip), fn, (sn, inn)))
 for kernel, Bq, kin, k, dt, variant in LIST_CASES if TABLE == "lists" else []:
     key = (kernel if kernel in ("merge", "rescore", "expand") else "graph", Bq, kin, dt)
