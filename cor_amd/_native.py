@@ -22,7 +22,11 @@ MERGE_NMAX = 4096    # most entries per query (P * kin) one cor_merge_topk launc
 EXPAND_SEGMAX = 16    # most gallery segments one cor_expand_queries launch reads (COR_EXPAND_SEGMAX)
 RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_reciprocal launch reads (COR_RERANK_SEGMAX)
 DIVERSIFY_SEGMAX = 16    # most gallery segments one cor_diversify_mmr launch reads (COR_DIVERSIFY_SEGMAX)
-ORDER_REVERSE = 1 << 30    # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
+FUSE_PMAX = 16    # most lists per query one cor_fuse_lists launch fuses (COR_FUSE_PMAX)
+FUSE_RRF, FUSE_SUM, FUSE_MAX = 0, 1, 2    # cor_fuse_lists modes (COR_FUSE_RRF / _SUM / _MAX)
+FUSE_NORM_NONE, FUSE_NORM_MINMAX = 0, 1    # ... score normalisation per list (COR_FUSE_NORM_*)
+FUSE_MISSING_ZERO, FUSE_MISSING_FLOOR = 0, 1    # ... what a list contributes to an id it does not hold (COR_FUSE_MISSING_*)
+ORDER_REVERSE = 1 << 30   # cor_gemm cfg / cor_layernorm act / cor_sam_attention variant: walk the work from the last item to the first
 GEMM_KERNEL_SCALAR, GEMM_KERNEL_MASK, GEMM_EPILOGUE_VEC = 32, 0xff, 1 << 8    # cor_gemm_kernel_id (COR_GEMM_KERNEL_SCALAR, ..._MASK, COR_GEMM_EPILOGUE_VEC)
 KERNEL_ROWLANE, KERNEL_FEWQ, KERNEL_FLASH_MFMA, KERNEL_FLASH_PIPELINED, KERNEL_WINDOW_BLOCK = 1, 2, 3, 4, 5
 import numpy as _np
@@ -95,12 +99,14 @@ SIGNATURES = {
     "cor_knn_reciprocal": [_p, _p, _p, _i, _i, _i, _p, _p],
     "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
     "cor_diversify_mmr": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p],
+    "cor_fuse_lists_workspace_bytes": [_i, _i, _i, _i],
+    "cor_fuse_lists": [_p, _p, _i, _i, _i, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,
             "cor_topk_i8_distinct_workspace_bytes": _l,
             "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l,
-            "cor_rescore_i8_workspace_bytes": _l}
+            "cor_rescore_i8_workspace_bytes": _l, "cor_fuse_lists_workspace_bytes": _l}
 
 _lib = None
 

@@ -6,6 +6,8 @@ kernel can reset the GPU). There is no CPU path: CPU tensors raise.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _native as nat
@@ -1016,6 +1018,70 @@ def diversify_mmr(segments, scores, idx, k, lam=0.5, max_sim=None, return_pos=Fa
                                            int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _p(out_v) or None, _s()),
                   "cor_diversify_mmr")
     return (out_s, out_i) + ((out_p,) if return_pos else ()) + ((out_v,) if return_value else ())
+
+
+_FUSE_MODES = {"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "max": nat.FUSE_MAX}
+_FUSE_NORMS = {"none": nat.FUSE_NORM_NONE, "minmax": nat.FUSE_NORM_MINMAX}
+_FUSE_MISSING = {"zero": nat.FUSE_MISSING_ZERO, "floor": nat.FUSE_MISSING_FLOOR}
+
+
+def fuse_args(who, P, k, weights=None, mode="rrf", rrf_c=60.0, normalize="none", missing="zero"):
+    """The checks of a fusion's host arguments (everything cor_fuse_lists refuses that does not depend on the lists), before anything touches
+    the device -> (weights as P floats, mode, normalize, missing as the C constants, rrf_c)."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if not 1 <= int(P) <= nat.FUSE_PMAX:
+        raise ValueError(f"{who}: {P} lists, one call fuses 1 to {nat.FUSE_PMAX}")
+    if mode not in _FUSE_MODES or normalize not in _FUSE_NORMS or missing not in _FUSE_MISSING:
+        raise ValueError(f"{who}: mode is one of {sorted(_FUSE_MODES)}, normalize of {sorted(_FUSE_NORMS)}, missing of {sorted(_FUSE_MISSING)}; "
+                         f"got {mode!r}, {normalize!r}, {missing!r}")
+    if mode == "rrf" and (normalize != "none" or missing != "zero"):
+        raise ValueError(f"{who}: reciprocal-rank fusion uses ranks alone: normalize and missing must be 'none' and 'zero'")
+    if mode == "max" and missing != "zero":
+        raise ValueError(f"{who}: mode 'max' ignores the lists that do not hold an id: missing must be 'zero'")
+    if isinstance(weights, torch.Tensor) and weights.device.type != "cpu":
+        raise ValueError(f"{who}: weights are host floats (they travel in the kernel arguments), not a device tensor")
+    w = [1.0] * int(P) if weights is None else [float(x) for x in weights]
+    if len(w) != int(P):
+        raise ValueError(f"{who}: {len(w)} weights for {P} lists")
+    w = [nat.C.c_float(x).value for x in w]                   # as the kernel receives them
+    if not all(math.isfinite(x) for x in w):
+        raise ValueError(f"{who}: the weights must be finite as float32, got {w}")
+    rrf_c = float(rrf_c)
+    if mode == "rrf" and not (math.isfinite(nat.C.c_float(rrf_c).value) and rrf_c >= 0.0):
+        raise ValueError(f"{who}: rrf_c must be finite and >= 0, got {rrf_c}")
+    return w, _FUSE_MODES[mode], _FUSE_NORMS[normalize], _FUSE_MISSING[missing], rrf_c
+
+
+def fuse_lists(scores, idx, k, weights=None, mode="rrf", rrf_c=60.0, normalize="none", missing="zero", return_count=False):
+    """Fuse P ranked lists per query on the device (cor_fuse_lists): scores f32 [P,Bq,kin], idx i64 [P,Bq,kin], P rankings of the same Bq
+    requests over the same global ids, stacked -> (scores f32[Bq,k], idx i64[Bq,k][, count i32[Bq,k]]): one entry per distinct id, ranked by
+    (fused score desc, id asc), then the (-inf, -1, -1) tail; count is the number of lists that hold the id. mode "rrf": the sum over the
+    lists that hold the id of w_p / (rrf_c + rank), rank = position + 1; "sum" (CombSUM): the sum of w_p * value; "max" (CombMAX): the
+    greatest w_p * value. normalize "minmax": a list's values are (s - min) / (max - min) over its valid entries (1 where they are all
+    equal) instead of the scores. missing "floor" (sum only): a list that does not hold the id contributes w_p * its least valid score (0
+    under minmax) instead of nothing. weights: a host sequence of P floats (default all 1), never a device tensor. An entry with idx < 0 or
+    a non-finite score is a hole; of an id repeated inside a list only the lowest position counts. include/cor_amd.h has the definition to
+    the bit. 1 <= P <= nat.FUSE_PMAX (16), P * kin <= nat.MERGE_NMAX (4096), 1 <= k <= 256, else ValueError. No host synchronisation;
+    capturable in a graph."""
+    who = "fuse_lists"
+    if not isinstance(scores, torch.Tensor) or not isinstance(idx, torch.Tensor) or scores.dim() != 3 or scores.shape[0] < 1 or scores.shape[2] < 1:
+        raise ValueError(f"{who}: scores must be a tensor [P, Bq, kin] with P, kin >= 1, got {tuple(getattr(scores, 'shape', ()))}")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"{who}: scores must be float32, got {scores.dtype}")
+    if idx.shape != scores.shape or idx.dtype != torch.int64:
+        raise ValueError(f"{who}: idx must be int64 of shape {tuple(scores.shape)}, got {idx.dtype} {tuple(idx.shape)}")
+    P, Bq, kin = scores.shape
+    w, c_mode, c_norm, c_missing, rrf_c = fuse_args(who, P, k, weights, mode, rrf_c, normalize, missing)
+    if P * kin > nat.MERGE_NMAX:
+        raise ValueError(f"{who}: {P} lists of {kin} are {P * kin} entries per query, one call fuses at most {nat.MERGE_NMAX}")
+    dev = _dev(scores, idx)
+    scores, idx = scores.contiguous(), idx.contiguous()
+    out_s, out_i, out_c = _list_outputs(Bq, int(k), dev, return_count)
+    if Bq:                                                    # (no queries: empty tensors have no address to pass)
+        nat.check(_lib().cor_fuse_lists(scores.data_ptr(), idx.data_ptr(), P, Bq, kin, (nat.C.c_float * P)(*w), c_mode, c_norm, c_missing, rrf_c,
+                                        int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_c) or None, None, _s()), "cor_fuse_lists")
+    return (out_s, out_i, out_c) if return_count else (out_s, out_i)
 
 
 def decoder_heads(hs, w01, b01, w2, b2):

@@ -135,6 +135,44 @@ def merge_topk_device(scores_parts, idx_parts, k: int, group_parts=None):
     return (out_s, out_i) if group_parts is None else (out_s, out_i, out_g)
 
 
+def fuse_lists_device(scores_parts, idx_parts, k: int, **fuse_kwargs):
+    """Fusion of P ranked lists per query on the GPU (ops.fuse_lists, cor_fuse_lists): parts are lists of device tensors [Bq, k_i] as the
+    stages return them, P rankings of the SAME Bq requests over the SAME global ids (several shots or views of a request, several
+    galleries over one id space) -> (scores f32[Bq,k], idx i64[Bq,k][, count i32[Bq,k] with return_count=True]): one entry per distinct id,
+    ranked by (fused score desc, id asc), on the device. fuse_kwargs: weights, mode ("rrf" / "sum" / "max"), rrf_c, normalize, missing,
+    return_count, as ops.fuse_lists takes them. Lists of unequal k_i are padded to the longest with missing entries (-inf, -1), which are
+    holes: they change no rank and no statistic. At most 16 lists and 4096 entries per query (P times the longest list), else ValueError:
+    there are no rounds as in merge_topk_device, because a fused list is not a list that can be fused again exactly (its ranks and
+    per-list statistics are those of the inputs). merge_topk_device is not this: it ranks entries and keeps a row that two lists name
+    twice. Nothing leaves the device and the host is not waited for."""
+    if len(scores_parts) == 0 or len(scores_parts) != len(idx_parts):
+        raise ValueError("fuse_lists_device: need one or more lists, and as many index lists as score lists")
+    P = len(scores_parts)
+    if P > ops.nat.FUSE_PMAX:
+        raise ValueError(f"fuse_lists_device: {P} lists, one fusion takes at most {ops.nat.FUSE_PMAX}")
+    for s, i in zip(scores_parts, idx_parts):
+        if s.dim() != 2 or s.shape[1] < 1 or i.shape != s.shape or s.shape[0] != scores_parts[0].shape[0]:
+            raise ValueError(f"fuse_lists_device: every list is scores and idx [Bq, k_i >= 1] of one Bq, got {tuple(s.shape)} and {tuple(i.shape)}")
+        if s.dtype != torch.float32 or i.dtype != torch.int64:
+            raise ValueError(f"fuse_lists_device: scores must be float32 and idx int64, got {s.dtype} and {i.dtype}")
+    kin = max(s.shape[1] for s in scores_parts)
+    if P * kin > ops.nat.MERGE_NMAX:
+        raise ValueError(f"fuse_lists_device: {P} lists padded to {kin} are {P * kin} entries per query, one fusion takes at most "
+                         f"{ops.nat.MERGE_NMAX} (there are no rounds: a fused list cannot be fused again exactly)")
+    ops.fuse_args("fuse_lists_device", P, k, **{a: v for a, v in fuse_kwargs.items() if a != "return_count"})
+    dev = scores_parts[0].device
+    with _on(dev):
+        if all(s.shape[1] == kin for s in scores_parts):
+            s, i = torch.stack(list(scores_parts)), torch.stack(list(idx_parts))
+        else:
+            s = torch.full((P, scores_parts[0].shape[0], kin), float("-inf"), dtype=torch.float32, device=dev)
+            i = torch.full((P, scores_parts[0].shape[0], kin), -1, dtype=torch.int64, device=dev)
+            for p, (sp, ip) in enumerate(zip(scores_parts, idx_parts)):
+                s[p, :, :sp.shape[1]] = sp
+                i[p, :, :ip.shape[1]] = ip
+        return ops.fuse_lists(s, i, int(k), **fuse_kwargs)
+
+
 def groups_of(idx, groups):
     """Global row ids -> group ids: idx i64[B,k] (as the searches return them; -1 = missing, stays -1), groups: one id per gallery
     row (the whole gallery, e.g. dataloader.gallery_labels(csv, column="Query_img")). Image-level Recall@K is then
@@ -748,6 +786,40 @@ def diversified_search(queries: torch.Tensor, gallery, k: int, k_coarse: int, la
         raise ValueError(f"diversified_search: lam must be in [0, 1] and max_sim not NaN, got lam={lam}, max_sim={max_sim}")
     s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
     return gallery.diversify(s, i, k=int(k), lam=lam, max_sim=max_sim)
+
+
+def fused_search(queries, gallery, k: int, k_each: int, weights=None, mode: str = "rrf", rrf_c: float = 60.0, normalize: str = "none",
+                 missing: str = "zero", **search_kwargs):
+    """Search with late fusion on one device: P searches at k_each and one fusion (fuse_lists_device) -> (scores f32[Bq,k], idx i64[Bq,k])
+    on the GPU, one entry per distinct gallery row, ranked by the fused score. queries: a sequence of P tensors [Bq,C] or one tensor
+    [P,Bq,C], the P shots or views of the same Bq requests (several (support image, mask, text) triplets of one target; the composed query,
+    its expanded form and the exact-query feat). gallery: one gallery, searched by every view, or a sequence of P galleries over the SAME
+    global id space, view p searching gallery p (the fp32 master rows and their augmented() copy; a QuantizedGallery and a bf16
+    GalleryShard); each a GalleryShard, a QuantizedShard, a QuantizedGallery or a GallerySet. weights, mode, rrf_c, normalize, missing as
+    ops.fuse_lists takes them; reciprocal-rank fusion is the default. 1 <= P <= 16, 1 <= k <= 256, 1 <= k_each <= 256, else ValueError
+    before anything runs. search_kwargs (query_labels, distinct; the filter's "eq" / "ne" goes as filter_mode, because mode names the
+    fusion) apply to EVERY search. Nothing leaves the device and the host is not waited for. distributed_search has no such option: ranks and per-list
+    statistics are per shard, so fusing before the merge is not the fusion of the global lists."""
+    if isinstance(queries, torch.Tensor):
+        if queries.dim() != 3:
+            raise ValueError(f"fused_search: queries must be a sequence of [Bq, C] tensors or one [P, Bq, C] tensor, got {tuple(queries.shape)}")
+        views = list(queries.unbind(0))
+    else:
+        views = list(queries)
+    P = len(views)
+    if not 1 <= int(k_each) <= ops.nat.TOPK_KMAX:
+        raise ValueError(f"fused_search: k_each must be in [1, {ops.nat.TOPK_KMAX}], got {k_each}")
+    ops.fuse_args("fused_search", P, k, weights, mode, rrf_c, normalize, missing)
+    galleries = list(gallery) if isinstance(gallery, (list, tuple)) else [gallery] * P
+    if len(galleries) != P:
+        raise ValueError(f"fused_search: {len(galleries)} galleries for {P} views: one gallery, or one per view")
+    if any(v.dim() != 2 or v.shape != views[0].shape for v in views):
+        raise ValueError(f"fused_search: the views must be [Bq, C] tensors of one shape, got {[tuple(v.shape) for v in views]}")
+    if "filter_mode" in search_kwargs:
+        search_kwargs["mode"] = search_kwargs.pop("filter_mode")
+    res = [g.search(v, int(k_each), **search_kwargs) for g, v in zip(galleries, views)]
+    return fuse_lists_device([r[0] for r in res], [r[1] for r in res], int(k), weights=weights, mode=mode, rrf_c=rrf_c, normalize=normalize,
+                             missing=missing)
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):

@@ -717,6 +717,64 @@ int cor_diversify_mmr(const void* const* seg_rows, const float* const* seg_scale
                       const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam,
                       float max_sim, int k, float* out_scores, long long* out_idx, int* out_pos, float* out_value, void* stream);
 
+/* Fusion of ranked lists: reciprocal-rank fusion (RRF; Cormack, Clarke & Buettcher, SIGIR 2009), CombSUM and CombMAX (Fox & Shaw, TREC-2
+ * 1994). Per query, P rankings of the SAME request over the SAME global id space (several shots or views of one request, or several
+ * galleries over one id space) become one ranking with one entry per distinct id. cor_merge_topk is not this: it ranks entries, not rows,
+ * and keeps a row that two lists name twice.
+ *
+ * cor_fuse_lists. scores f32 [P,Bq,kin] and idx i64 [P,Bq,kin], contiguous, stacked like cor_merge_topk's: lists as the searches, the merge,
+ * the re-scoring or any other stage return them. weights_host: P HOST floats, copied into a by-value kernel argument together with the
+ * switches: no device allocation, no host-to-device copy, no host synchronisation; everything runs on `stream` and the call can be
+ * captured in a graph. out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_count NULL or i32 [Bq,k].
+ * Definition, per query b, fixed to the bit: every + - * / below is ONE IEEE fp32 operation, separately rounded, never contracted.
+ *   Valid entries. Entry e of list p is a HOLE if idx[p,b,e] < 0 or its score is not finite (exponent bits all ones: +-inf and NaN; a
+ *   present entry with such a score is a hole too). Among the entries of ONE list that are no holes and carry the same id, only the one
+ *   at the lowest position is VALID; the others are repeats and count for nothing. The RANK of an entry is its 0-based position e + 1:
+ *   holes and repeats take ranks, so for lists as the stages return them this is the usual rank. Nothing is indexed with an id.
+ *   Statistics. mn_p and mx_p are the least and the greatest score over the valid entries of list p, a -0.0 counting as +0.0 (neither is
+ *   ever -0.0). A list with no valid entry has none and contributes nothing to any id, in any mode.
+ *   Value of a valid entry with score s: normalize == COR_FUSE_NORM_NONE: v = s. COR_FUSE_NORM_MINMAX: v = (s - mn_p) / (mx_p - mn_p), two
+ *   subtractions and one division; mx_p == mn_p: v = 1.0f.
+ *   Contribution c_p of list p to an id:
+ *     COR_FUSE_RRF: c = w_p / (rrf_c + (float)rank), one add and one divide, for a list that holds the id (has a valid entry with it);
+ *       any other list contributes nothing. normalize / missing must be NONE / ZERO.
+ *     COR_FUSE_SUM: c = w_p * v for a list that holds the id. A list that does not: nothing under COR_FUSE_MISSING_ZERO; under
+ *       COR_FUSE_MISSING_FLOOR c = w_p * f_p with f_p = mn_p (NORM_NONE) or 0.0f (NORM_MINMAX): the best score the absent row could still
+ *       have in a truncated sorted list.
+ *     COR_FUSE_MAX: c = w_p * v for the lists that hold the id; the others are ignored. missing must be ZERO.
+ *   Fused score. RRF and SUM: acc = +0.0f, then acc = acc + c_p for p = 0 .. P-1 in that order, over the lists that contribute.
+ *     MAX: acc = the c of the first list (lowest p) that holds the id, then `if (c_p > acc) acc = c_p` for the further holding lists in
+ *     ascending p: no fmaxf, so +-0 are decided by the order.
+ *   Output. One entry per distinct id that is valid in at least one list, ranked by (fused score desc, id asc) with cor_merge_topk's rules:
+ *   scores compare as floats, -0.0 ranks as +0.0 and its bits are preserved, ids compare as 64-bit values. The first k go out with the
+ *   fused bits as computed; out_count receives the number of lists that hold the id (CombMNZ is count * the SUM output). Positions past
+ *   the number of distinct ids hold (-inf, -1, -1). The order among ids whose fused score is NaN (weights large enough to overflow) is
+ *   unspecified.
+ * Consequences. P = 1, SUM, weight 1, NONE, ZERO returns a searched list as it is, except that a -0.0 score comes back as +0.0 (acc
+ * starts at +0.0). A fused list is not a list that can be fused again exactly (ranks and statistics are those of the inputs): there
+ * are no rounds, and everything must fit one launch.
+ * One launch, one block per query: a bitonic sort in LDS of 16-bit position keys by (id, position) with the 64-bit ids held in LDS,
+ * per-list min / max by wave reductions where the mode needs them, the thread at the head of every run of equal ids accumulating its run
+ * in list order, and cor_merge_topk's ranking (8-byte keys [fused score key | slot], the id read on ties) of the heads. 19 bytes of LDS
+ * per padded entry, 76 KB at 4096 entries; no scratch, no global workspace.
+ * COR_EINVAL: a null scores / idx / weights_host / out_scores / out_idx; P < 1, Bq < 0, kin < 1, k < 1; an unknown mode / normalize /
+ * missing; RRF with normalize != NONE or missing != ZERO; MAX with missing != ZERO; under RRF rrf_c not finite or < 0; a weight that
+ * is not finite (the weights are read once P <= COR_FUSE_PMAX is known). COR_ENOSUPPORT: P > COR_FUSE_PMAX, P*kin > COR_MERGE_NMAX,
+ * k > COR_TOPK_KMAX. All of these are decided before any HIP call. Bq == 0 is a successful no-op. cor_fuse_lists_workspace_bytes reports
+ * the shape errors as negative values; the kernel needs no scratch memory, so it returns 0 for every supported shape and `workspace` may
+ * then be NULL. */
+#define COR_FUSE_PMAX 16
+#define COR_FUSE_RRF 0
+#define COR_FUSE_SUM 1
+#define COR_FUSE_MAX 2
+#define COR_FUSE_NORM_NONE 0
+#define COR_FUSE_NORM_MINMAX 1
+#define COR_FUSE_MISSING_ZERO 0
+#define COR_FUSE_MISSING_FLOOR 1
+long cor_fuse_lists_workspace_bytes(int P, int Bq, int kin, int k);
+int cor_fuse_lists(const float* scores, const long long* idx, int P, int Bq, int kin, const float* weights_host, int mode, int normalize,
+                   int missing, float rrf_c, int k, float* out_scores, long long* out_idx, int* out_count, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
