@@ -333,6 +333,7 @@ struct ScanArgs {
   float* tau; int* cnt; float* rec_s; int* rec_g; int cap;           // APPEND: tau_q (written by the blocks of slice 0 for the selection kernel); record i of stream (q, slice, lane quarter): 8 scores + first row
   const int* rlab; const int* qlab; int ne;                           // FILTER: row / query labels, COR_FILTER_NE (filtered wide route only)
   int* sgrow;                                                         // GROUP SAMPLE: the shard row behind every stored sample value (distinct-group route only)
+  const float* rng_a; const float* rng_h; int* sure;                  // RANGE APPEND: the bounds A_q and H_q (sim_range_bounds; a.tau holds B_q) and the sure counts per stream
 };
 
 // One block = 8 waves = 256 * QB queries (wave w owns queries q0 + 32 * QB * w ..): with QB = 2 all 512 queries of an
@@ -446,7 +447,14 @@ __device__ __forceinline__ void append_entry(uint2* dst, int& n, int cap, float 
 // GROUP (the distinct-group route; SAMPLE only, implies WIDE; APPEND is the plain WIDE / FILTER instantiation): every stored sample value
 // keeps its ROW beside it (a.sgrow, same index as a.sg), NV = 1 (4 with FILTER) best allowed scores per (slice, lane quarter) group:
 // sim_tau_distinct needs the rows' group ids to count DISTINCT groups above the threshold.
-template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false, bool GROUP = false>
+// RANGE (cor_similarity_range; APPEND only, implies WIDE, no FILTER): a.tau holds B_q = thr_q - delta_q, the lowest score that matters, and
+// one wave-uniform test of the tile maximum against it guards everything else. Behind it a lane counts its scores >= H_q = thr_q + delta_q
+// (sure members: counted in registers, written next to cnt at the end of the slice, no atomics) and appends its column when it holds a
+// list candidate (>= A_q = max(tau_q, B_q)) or a band row (B_q <= s < H_q, for the chain to decide). A_q and H_q of the lane's NQ queries
+// share ONE register each: lane (n16, rq) keeps those of query block rq % NQ and the guarded branch fetches them across lanes; the sure
+// count shares ncand's register (low 16 bits; the records above them): make_wide keeps a slice at <= 4095 super-tiles = 65 520 scores per
+// lane. With a counter of its own per query block the QB = 2 instantiation spilled four registers.
+template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false, bool GROUP = false, bool RANGE = false>
 __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int C = 256, TILE = 32 * C * 2, STILE = 2 * TILE, NS = FILTER ? SCAN_NS - 1 : SCAN_NS, AHEAD = FILTER ? SCAN_AHEAD - 1 : SCAN_AHEAD;
@@ -557,6 +565,11 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
   uint4 qf[NQ][8];
   float tau[NQ], gmax[NQ];
   int ncand[NQ];
+  float pack_a = 0.f, pack_h = 0.f;                    // RANGE: A_q / H_q of query (block rq % NQ, n16)
+  if constexpr (RANGE) {
+    const int qp = min(q0 + (rq % NQ) * 16 + n16, a.Bq - 1);
+    pack_a = a.rng_a[qp]; pack_h = a.rng_h[qp];
+  }
   int ql[NQ];                                          // FILTER: the lane's query labels (< 0: unrestricted)
   Best4 top4[NQ];                                      // FILTER SAMPLE: the group's four best allowed scores (Best4)
   constexpr int NV = GROUP && FILTER ? 4 : 1;          // GROUP SAMPLE: the group's NV best allowed scores and their rows (BestRows)
@@ -635,6 +648,35 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
           for (int e = 0; e < 4; ++e) top4[qb].offer(acc[qb][rb][e]);
       } else if (SAMPLE) {
         gmax[qb] = fmaxf(gmax[qb], tmax);
+      } else if (RANGE) {
+        if (__builtin_amdgcn_ballot_w64(tmax >= tau[qb]) != 0) {      // tau[qb] = B_q: some lane holds a score that counts or is appended
+          const float aq = __shfl(pack_a, qb * 16 + n16, 64), hq = __shfl(pack_h, qb * 16 + n16, 64);   // (every lane takes part)
+          int q = q0 + qb * 16 + n16;
+          asm volatile("" : "+v"(q));                  // opaque, as below
+          if (tmax >= tau[qb] && q < a.Bq) {
+            int ns = 0;
+            bool keep = tmax >= aq;                    // a list candidate; or a band row (B_q >= -3e38: never a masked -inf)
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float sc = acc[qb][rb][e];
+                ns += sc >= hq ? 1 : 0;
+                keep = keep || (sc >= tau[qb] && sc < hq);
+              }
+            ncand[qb] += ns;
+            if (keep) {
+              const int nrec = ncand[qb] >> 16;
+              if (nrec < a.cap) {
+                const long rec = ((long)q * nstreams + split * 4 + rq) * a.cap + nrec;
+                f32x4* dst = (f32x4*)(a.rec_s + rec * 8);
+                dst[0] = acc[qb][0]; dst[1] = acc[qb][1];
+                a.rec_g[rec] = g0;
+              }
+              ncand[qb] += 1 << 16;
+            }
+          }
+        }
       } else if (auto pass = [&] { return FILTER ? ok && tmax >= tau[qb] : tmax >= tau[qb]; }; __builtin_amdgcn_ballot_w64(pass()) != 0) {
         // Some lane of the wave has a candidate in this tile. Testing the registers one by one cost ~80 instructions per triggered tile
         // (70 us of a 270-us scan in round 2); instead a lane whose tile maximum passes appends its WHOLE 8-score column as one record
@@ -734,7 +776,10 @@ __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, con
         else if (SAMPLE && FILTER) top4[qb].store(a.sg + (long)q * a.Bqp + (split * 4 + rq) * 4);
         else if (SAMPLE && WIDE) a.sg[(long)q * a.Bqp + split * 4 + rq] = f2key(gmax[qb]);                  // one writer per group: no atomic
         else if (SAMPLE) atomicMax(a.sg + (long)((split * 4 + rq) & 31) * a.Bqp + q, f2key(gmax[qb]));    // (a group without a tile: key(-inf) > 0 = empty)
-        else a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb];
+        else if (RANGE) {
+          a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb] >> 16;
+          a.sure[(long)q * nstreams + split * 4 + rq] = ncand[qb] & 0xffff;
+        } else a.cnt[(long)q * nstreams + split * 4 + rq] = ncand[qb];
       }
     }
   }
@@ -1962,6 +2007,28 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
                          [&](int g) { return !FILTER || row_allowed(rlab, g, ql, ne); }, Ng, k, g_offset, sl_s, sl_i, keys, hist,
                          out_s, out_i);
 }
+// The fallback of cor_similarity_range for one query: a chain pass over the shard counts the rows at or above the floor, wide_brute_force
+// ranks into LDS (tmp_s / tmp_i [k], outside the buffers it works in), and the ranked rows below the floor leave as tail. Six chain passes.
+template <typename TG>
+__device__ void range_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float thr, float* sl_s,
+                                  int* sl_i, unsigned long long* keys, int* hist, float* tmp_s, long long* tmp_i, float* out_s, long long* out_i,
+                                  int* out_count) {
+  __shared__ int members;
+  const int tid = threadIdx.x;
+  if (tid == 0) members = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int g = tid; g < Ng; g += 256) mine += chain_score_c<TG>(G, g, C, qs) >= thr ? 1 : 0;
+  if (mine) atomicAdd(&members, mine);
+  wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, tmp_s, tmp_i);
+  __syncthreads();
+  for (int j = tid; j < k; j += 256) {
+    const bool in = j < Ng && tmp_s[j] >= thr;         // (the first min(k, Ng) slots hold rows)
+    out_s[j] = in ? tmp_s[j] : -INFINITY;
+    out_i[j] = in ? tmp_i[j] : -1LL;
+  }
+  if (tid == 0) *out_count = members;
+}
 
 // The tile loop of sim_topk_partial (fp32 galleries: the chain on the f32 MFMA; 16-bit: the 16-bit MFMA; any C <= 256, C % 16 == 0)
 // with the epilogues of the wide route. One wave = 32 queries x a slice of 32-row tiles; lane (r, h) holds 16 scores of query r per tile.
@@ -1975,9 +2042,12 @@ struct WideScanArgs {
   const float* tau; int* cnt; uint2* lst; int cap;
   const int* rlab; const int* qlab; int ne;          // FILTER: row / query labels, COR_FILTER_NE
   int* sgrow;                                        // GROUP SAMPLE: the shard row behind every stored sample value
+  const float* rng_a; const float* rng_h; int* sure; // RANGE APPEND: A_q and H_q (sim_range_bounds; tau holds B_q), the sure counts per stream
 };
 //   GROUP (distinct-group route, SAMPLE only): NV = 1 (4 with FILTER) best allowed scores per group WITH their rows (BestRows, a.sgrow).
-template <typename TG, bool SAMPLE, bool FILTER = false, bool GROUP = false>
+//   RANGE (cor_similarity_range, APPEND only): tau holds B_q = thr_q - delta_q; behind one test of the tile maximum against it a lane counts
+//   its scores >= H_q (sure members, a register counter) and appends the list candidates (>= A_q) and the band rows (B_q <= s < H_q).
+template <typename TG, bool SAMPLE, bool FILTER = false, bool GROUP = false, bool RANGE = false>
 __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q, const TG* __restrict__ G, const WideScanArgs a) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2001,7 +2071,8 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
   const float tq = SAMPLE ? 0.f : append_threshold(q < a.Bq, a.tau, q);
   const int stream = split * 2 + h, nstreams = 2 * a.nsplit;
   float gmax = -INFINITY;
-  int n = 0;
+  int n = 0, nsure = 0;
+  const float ra = RANGE ? a.rng_a[min(q, a.Bq - 1)] : 0.f, rh = RANGE ? a.rng_h[min(q, a.Bq - 1)] : 0.f;
   const int ql = FILTER ? a.qlab[min(q, a.Bq - 1)] : 0;
   Best4 top4;
   top4.clear();
@@ -2068,7 +2139,12 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       uint2* dst = a.lst + ((long)q * nstreams + stream) * a.cap;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        if (sc[e] >= tq) append_entry(dst, n, a.cap, sc[e], g0 + (e & 3) + 8 * (e >> 2) + 4 * h);
+        if constexpr (RANGE) {                         // tq = B_q (a padding lane: +inf, nothing passes)
+          if (sc[e] >= tq) {
+            nsure += sc[e] >= rh ? 1 : 0;
+            if (sc[e] >= ra || sc[e] < rh) append_entry(dst, n, a.cap, sc[e], g0 + (e & 3) + 8 * (e >> 2) + 4 * h);
+          }
+        } else if (sc[e] >= tq) append_entry(dst, n, a.cap, sc[e], g0 + (e & 3) + 8 * (e >> 2) + 4 * h);
       }
     }
   }
@@ -2076,7 +2152,10 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
     if constexpr (SAMPLE && GROUP) best.store(a.sg, a.sgrow, (long)q * a.ngroups + stream * NV);
     else if (SAMPLE && FILTER) top4.store(a.sg + (long)q * a.ngroups + stream * 4);
     else if (SAMPLE) a.sg[(long)q * a.ngroups + stream] = f2key(gmax);
-    else a.cnt[(long)q * nstreams + stream] = n;
+    else {
+      a.cnt[(long)q * nstreams + stream] = n;
+      if constexpr (RANGE) a.sure[(long)q * nstreams + stream] = nsure;
+    }
   }
 }
 
@@ -2209,6 +2288,175 @@ __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ 
     out_s[(long)q * k + j] = j < m ? rank_key_score(keys[j]) : -INFINITY;
     out_i[(long)q * k + j] = j < m ? (long long)(unsigned)keys[j] + g_offset : -1LL;
   }
+}
+
+// The selection of cor_similarity_range: sim_final_wide without a filter, with the floor. (A kernel of its own: as one body shared with
+// sim_final_wide the existing instantiations compiled to a different instruction order.) r carries the floors, the bounds the APPEND pass
+// used and its sure counts. The candidates are the scores >= A_q; the rows of the band scores (B_q <= s < H_q) are collected in LDS
+// (band_i, BAND_MAX rows) and re-scored by the chain, one row per thread, and counted if at or above the floor (re-scored where the gather
+// met them, one lane of a wave at a time, 830 band rows per query cost 1.2 ms at 512 x 1M); count = the streams' sure counts + those band
+// rows; ranked rows below the floor become tail. An overflow (of the lists, as before: a stream that lost records may have lost band
+// rows; or more band rows than band_i holds) sends the query to range_brute_force, which ranks AND counts over the chain; with
+// no_fallback it leaves index -2 in every slot and count -2.
+constexpr int BAND_MAX = 16384;                        // band rows per query held in LDS (64 KiB: still one block per CU, as sim_final_wide)
+constexpr size_t FINAL_RANGE_LDS = FINAL_WIDE_LDS + (size_t)BAND_MAX * 4;
+struct RangeFinal { const float* thr; const float* ra; const float* rb; const float* rh; const int* sure; int* out_count; };
+template <typename TG, bool RECORDS>
+__global__ void __launch_bounds__(256) sim_final_range(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C, int k, long long g_offset,
+                                                       const int* __restrict__ cnt, int nstreams, int cap, const float* __restrict__ rec_s,
+                                                       const int* __restrict__ rec_g, const uint2* __restrict__ lst, float* out_s, long long* out_i,
+                                                       int no_fallback, const RangeFinal r) {
+  extern __shared__ __attribute__((aligned(16))) char fwraw[];
+  float* cs = (float*)fwraw; int* ci = (int*)(cs + FSW);
+  float* sl_s = (float*)(ci + FSW); int* sl_i = (int*)(sl_s + SLW);
+  float* qs = (float*)(sl_i + SLW); int* hist = (int*)(qs + 256);
+  int* band_i = hist + 256;                            // rows of the band scores
+  unsigned long long* keys = (unsigned long long*)fwraw;   // the candidate buffer, dead once the short list is built (SLW * 8 B <= 64 KiB)
+  __shared__ int ovf, total, nsl, sel_bin, k_rem;
+  __shared__ float qn2[4];
+  constexpr bool F32 = sizeof(TG) == 4;
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int rcount, nband;                        // sure counts + band rows at or above the floor; band rows met
+  const float thr = r.thr[q], rb = r.rb[q], rh = r.rh[q];
+  if ((__float_as_uint(thr) & 0x7fffffffu) > 0x7f800000u) {        // a NaN floor (by its bits: the file is built with -fno-honor-nans): the empty set
+    for (int j = tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -1LL; }
+    if (tid == 0) r.out_count[q] = 0;
+    return;
+  }
+  if (tid == 0) { ovf = 0; total = 0; nsl = 0; rcount = 0; nband = 0; }
+  const float qv = tid < C ? round_to<TG>(Q[(long)q * C + tid]) : 0.f;   // the query as the scan saw it
+  if (tid < C) qs[tid] = qv;
+  const float part = wave_sum(qv * qv);
+  if (lane == 0) qn2[wave] = part;
+  __syncthreads();
+  const float delta = F32 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(qn2[0] + qn2[1] + qn2[2] + qn2[3]));
+  // 1. gather the candidates into LDS (thread <-> stream)
+  const float tq = r.ra[q];                            // A_q
+  int mine = 0;                                        // this thread's share of the count
+  auto band = [&](float s, int row) {                  // 16-bit rows: the chain decides a band row, below (fp32: B_q = H_q, no band)
+    if constexpr (!F32) {
+      if (s >= rb && s < rh) {
+        const int p = atomicAdd(&nband, 1);
+        if (p < BAND_MAX) band_i[p] = row;
+      }
+    }
+  };
+  for (int st = tid; st < nstreams; st += 256) {
+    const int c = cnt[(long)q * nstreams + st];
+    if (c > cap) ovf = 1;
+    mine += r.sure[(long)q * nstreams + st];
+    const int nrec = min(c, cap);
+    const long rec0 = ((long)q * nstreams + st) * cap;
+    for (int j = 0; j < nrec; ++j) {
+      if (RECORDS) {                                   // score [g][i] of lane quarter st & 3 is row g0 + 16 g + 4 (st & 3) + i
+        const f32x4* sj = (const f32x4*)(rec_s + (rec0 + j) * 8);
+        const f32x4 v[2] = {sj[0], sj[1]};
+        const int g0 = rec_g[rec0 + j], r4 = 4 * (st & 3);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) band(v[g][i], g0 + i + 16 * g + r4);
+        int np = 0;
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) np += (v[g][i] >= tq && v[g][i] > -INFINITY) ? 1 : 0;
+        if (np == 0) continue;
+        int p = atomicAdd(&total, np);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (v[g][i] >= tq && v[g][i] > -INFINITY) {
+              if (p < FSW) { cs[p] = v[g][i]; ci[p] = g0 + i + 16 * g + r4; }
+              ++p;
+            }
+      } else {
+        const uint2 e = lst[rec0 + j];
+        band(__uint_as_float(e.x), (int)e.y);
+        if (__uint_as_float(e.x) < tq) continue;       // a band row below A_q: counted above, no list candidate
+        const int p = atomicAdd(&total, 1);
+        if (p < FSW) { cs[p] = __uint_as_float(e.x); ci[p] = (int)e.y; }
+      }
+    }
+  }
+  __syncthreads();
+  if (total > FSW || nband > BAND_MAX) ovf = 1;
+  const int n = min(total, FSW);
+  if constexpr (!F32) {
+    if (nband <= BAND_MAX)
+      for (int j = tid; j < nband; j += 256) mine += chain_score_c<TG>(G, band_i[j], C, qs) >= thr ? 1 : 0;
+  }
+  if (mine) atomicAdd(&rcount, mine);
+  __syncthreads();
+  // 2. T = the k-th best scan score, exactly (every row of the scan's top-k is a candidate); n <= k: every candidate is in
+  float T = -INFINITY;
+  if (!ovf && n > k) T = key2f_floor(block_kth_key([&](int i) { return f2key(cs[i]); }, n, k, hist, &sel_bin, &k_rem));
+  // 3. short list: scan score >= T - delta (fp32: the rows >= T, ties at T included)
+  if (!ovf) {
+    const float cut = T - delta;
+    for (int i = tid; i < n; i += 256) {
+      if (cs[i] >= cut) {
+        const int p = atomicAdd(&nsl, 1);
+        if (p < SLW) { sl_s[p] = cs[i]; sl_i[p] = ci[i]; }
+      }
+    }
+  }
+  __syncthreads();
+  if (nsl > SLW) ovf = 1;
+  __syncthreads();
+  if (ovf) {
+    if (no_fallback) {                                 // tests: expose the raw overflow marker
+      for (int j = tid; j < k; j += 256) { out_s[(long)q * k + j] = -INFINITY; out_i[(long)q * k + j] = -2LL; }
+      if (tid == 0) r.out_count[q] = -2;
+      return;
+    }
+    range_brute_force<TG>(G, Ng, C, qs, k, g_offset, thr, sl_s, sl_i, keys, hist, (float*)ci, (long long*)(ci + 256), out_s + (long)q * k,
+                          out_i + (long)q * k, r.out_count + q);
+    return;
+  }
+  if (tid == 0) r.out_count[q] = rcount;
+  const int m = nsl;
+  // 4. exact re-scoring (16-bit): the chain of oracle/c/sim_chain.c over the stored values
+  if (!F32)
+    for (int j = tid; j < m; j += 256) sl_s[j] = chain_score_c<TG>(G, sl_i[j], C, qs);
+  __syncthreads();
+  // 5. rank by (chain score desc, index asc): one bitonic sort; entries beyond the short list (Ng < k) are (-inf, -1)
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int j = tid; j < P; j += 256) keys[j] = j < m ? rank_key(sl_s[j], sl_i[j]) : ~0ull;
+  __syncthreads();
+  block_sort_u64(keys, P);
+  for (int j = tid; j < k; j += 256) {
+    const bool in = j < m && rank_key_score(keys[j]) >= thr;   // below the floor: tail (a suffix of the ranked rows)
+    out_s[(long)q * k + j] = in ? rank_key_score(keys[j]) : -INFINITY;
+    out_i[(long)q * k + j] = in ? (long long)(unsigned)keys[j] + g_offset : -1LL;
+  }
+}
+
+// The floors of cor_similarity_range as the APPEND pass and the selection use them, one block per query behind sim_tau_wide:
+//   B_q = thr_q - delta_q, H_q = thr_q + delta_q, A_q = max(tau_q, B_q), each floored at -3e38 so that a masked -inf score never passes.
+// delta_q is sim_tau_wide's (0 for fp32 rows: no band). SIM_DELTA is twice the bound of |scan - chain|, so scan >= H_q implies chain >= thr_q
+// and scan < B_q implies chain < thr_q, the rounding of the two sums included. A NaN floor (told by its bits) gives +inf three times:
+// nothing counts, nothing is appended.
+template <typename TG>
+__global__ void __launch_bounds__(256) sim_range_bounds(const float* __restrict__ Q, int C, const float* __restrict__ thr, const float* __restrict__ tau,
+                                                        float* ra, float* rb, float* rh) {
+  __shared__ float part[4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  float n2 = 0.f;
+  if (sizeof(TG) != 4 && tid < C) { const float x = round_to<TG>(Q[(long)q * C + tid]); n2 = x * x; }
+  n2 = wave_sum(n2);
+  if ((tid & 63) == 0) part[tid >> 6] = n2;
+  __syncthreads();
+  if (tid != 0) return;
+  const float delta = sizeof(TG) == 4 ? 0.f : SIM_DELTA * fmaxf(1.f, sqrtf(part[0] + part[1] + part[2] + part[3]));
+  const float t = thr[q];
+  float b = INFINITY, h = INFINITY, a = INFINITY;
+  if ((__float_as_uint(t) & 0x7fffffffu) <= 0x7f800000u) {
+    b = fmaxf(t - delta, -3.0e38f); h = fmaxf(t + delta, -3.0e38f); a = fmaxf(tau[q], b);
+  }
+  ra[q] = a; rb[q] = b; rh[q] = h;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2559,6 +2807,7 @@ struct WidePlan {
   int s_stride, s_tiles, s_nsplit, s_tiles_per_split, ngroups;       // SAMPLE (ngroups == 0: no sample, tau = -inf)
   size_t off_img, off_sg, off_dq, off_tau, off_flags, off_ovf, off_cnt, off_recs, off_recg, bytes;
   size_t off_sgrow;                  // group: the rows of the sample values
+  size_t off_rng, off_sure;          // range: A_q, B_q, H_q (three f32 [Bq]) and the sure counts per stream
 };
 // group = the distinct-group route (any k): the sample keeps NV = 1 (filter: 4) values WITH rows per group, and the capacity plan below.
 // i8 = the int8 route (cor_similarity_topk_i8; scan must be set): the scan form's 64-row tiles and lane-quarter streams, query groups of
@@ -2567,7 +2816,10 @@ struct WidePlan {
 // i8 + group (cor_similarity_topk_i8_distinct): the group capacity numbers as they are (stride <= 1024 / k, expect = 6 k stride: the sampled
 // values are maxima of the same disjoint row classes, rows 4 rq .. 4 rq + 3 of every 16 of a slice). Without the clamp the sample has at
 // most 256 slices for every Ng, so ngroups <= 4 streams x 256 x 4 values = TAU_DISTINCT_MAX with the filter and the stride never widens.
-inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false) {
+// range = cor_similarity_range (any k, no filter, no groups): the streams also take the band rows (scan within delta_q of the floor: about
+// 2 delta_q * Ng * the score density at the floor per query, some 830 rows over ~1000 streams at 1M unit rows of C = 256 and a floor of 0), so
+// every stream gets 6 more places; the bounds and the sure counts sit behind the other buffers.
+inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false, bool range = false) {
   WidePlan p{};
   p.scan = scan;
   const int rows = scan ? 64 : 32;                     // rows per tile of the scan kernel
@@ -2586,6 +2838,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   if (want < 1) want = 1;
   p.tiles_per_split = cdiv(p.ntiles, want);
   if (filter && scan && !i8 && p.tiles_per_split > 128) p.tiles_per_split = 128;
+  if (range && scan && p.tiles_per_split > 4095) p.tiles_per_split = 4095;   // sim_scan RANGE counts a lane's sure rows in 16 bits
   p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
   const int per_tile = scan ? 4 : 2;                   // streams per slice: lane quarters (scan) / lane halves (tiles)
   p.nstreams = per_tile * p.nsplit;
@@ -2626,7 +2879,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
     p.ngroups = per_tile * p.s_nsplit * (filter ? 4 : 1);
     const long expect = (group ? 6L : 3L) * k * p.s_stride;   // candidates per query, ~2x slack
     // per stream: Poisson with mean ~ expect / nstreams; +10 keeps P(overflow) per search small
-    p.cap = (int)(2 * expect / p.nstreams) + 10;
+    p.cap = (int)(2 * expect / p.nstreams) + 10 + (range ? 6 : 0);
     if (p.cap > stream_max) p.cap = stream_max;
   }
   const int Bqp = scan && !i8 ? p.nqg * 256 * p.qb : 0;
@@ -2643,6 +2896,8 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   p.off_recs = take((size_t)Bq * p.nstreams * p.cap * (scan && !i8 ? 32 : 8));   // a record = 8 scores; an entry = (score, row)
   p.off_recg = take(scan && !i8 ? (size_t)Bq * p.nstreams * p.cap * 4 : 0);
   p.off_sgrow = take(group ? (size_t)Bq * p.ngroups * 4 + 4 : 0);
+  p.off_rng = take(range ? (size_t)Bq * 12 : 0);
+  p.off_sure = take(range ? (size_t)Bq * p.nstreams * 4 : 0);
   p.bytes = o;
   return p;
 }
@@ -2654,10 +2909,11 @@ struct WideCall {
   const int* grp; const int* rlab; const int* qlab; int ne;
   float* out_s; long long* out_i; char* w; int flags; hipStream_t s;
   const float* gscale;                               // the int8 route: the gallery rows' scales
+  const float* thr; int* out_count;                  // the range call: the floors and the member counts
 };
 
 // tau_q from the sample values. GROUP: reduced to one value per group first (sim_tau_distinct, with the rows behind the values).
-template <typename TG, bool GROUP>
+template <typename TG, bool GROUP, bool RANGE = false>
 int launch_wide_tau(const WideCall& c, const WidePlan& p) {
   const unsigned* sg = (const unsigned*)(c.w + p.off_sg); float* tau = (float*)(c.w + p.off_tau);
   if constexpr (GROUP)
@@ -2665,18 +2921,29 @@ int launch_wide_tau(const WideCall& c, const WidePlan& p) {
   else
     hipLaunchKernelGGL((sim_tau_wide<TG>), dim3(c.Bq), dim3(256), 0, c.s, c.Q, c.C, sg, p.ngroups, c.k, tau);
   COR_CHECK_LAUNCH();
+  if constexpr (RANGE) {                               // the floors beside tau_q: A_q, B_q, H_q
+    float* rng = (float*)(c.w + p.off_rng);
+    hipLaunchKernelGGL((sim_range_bounds<TG>), dim3(c.Bq), dim3(256), 0, c.s, c.Q, c.C, c.thr, tau, rng, rng + c.Bq, rng + 2 * (size_t)c.Bq);
+    COR_CHECK_LAUNCH();
+  }
   return 0;
 }
 
 // the selection over the APPEND pass's streams: records (scan form) or entry lists (tile form). GROUP: one row per group (sim_final_distinct).
-template <typename TG, bool RECORDS, bool FILTER, bool GROUP>
+template <typename TG, bool RECORDS, bool FILTER, bool GROUP, bool RANGE = false>
 int launch_wide_final(const TG* G, const WideCall& c, const WidePlan& p) {
   static DevOnce once;
   const float* tau = (const float*)(c.w + p.off_tau); const int* cnt = (const int*)(c.w + p.off_cnt);
   const float* rec_s = RECORDS ? (const float*)(c.w + p.off_recs) : nullptr; const int* rec_g = RECORDS ? (const int*)(c.w + p.off_recg) : nullptr;
   const uint2* lst = RECORDS ? nullptr : (const uint2*)(c.w + p.off_recs);
   const int no_fallback = (c.flags & COR_TOPK_NO_FALLBACK) ? 1 : 0;
-  if constexpr (GROUP) {
+  if constexpr (RANGE) {
+    const float* rng = (const float*)(c.w + p.off_rng);
+    const RangeFinal r{c.thr, rng, rng + c.Bq, rng + 2 * (size_t)c.Bq, (const int*)(c.w + p.off_sure), c.out_count};
+    cor_max_dyn_lds((const void*)sim_final_range<TG, RECORDS>, (int)FINAL_RANGE_LDS, once);
+    hipLaunchKernelGGL((sim_final_range<TG, RECORDS>), dim3(c.Bq), dim3(256), FINAL_RANGE_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, cnt, p.nstreams,
+                       p.cap, rec_s, rec_g, lst, c.out_s, c.out_i, no_fallback, r);
+  } else if constexpr (GROUP) {
     cor_max_dyn_lds((const void*)sim_final_distinct<TG, RECORDS>, (int)FINAL_DISTINCT_LDS, once);
     hipLaunchKernelGGL((sim_final_distinct<TG, RECORDS>), dim3(c.Bq), dim3(256), FINAL_DISTINCT_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, tau, cnt,
                        p.nstreams, p.cap, rec_s, rec_g, lst, c.grp, c.out_s, c.out_i, no_fallback, c.rlab, c.qlab, c.ne);
@@ -2692,12 +2959,13 @@ int launch_wide_final(const TG* G, const WideCall& c, const WidePlan& p) {
 // The scan form (16-bit, C = 256): sim_prep, SAMPLE, tau, APPEND, selection. GROUP changes the sample (it keeps the rows, sgrow), the
 // threshold and the selection; the APPEND scan is the wide / filtered instantiation unchanged (it appends scores >= tau_q whatever the
 // groups are).
-template <typename TG, int QB, bool FILTER, bool GROUP>
+// RANGE: the APPEND scan takes B_q for tau_q, counts and keeps the band (sim_scan RANGE); the selection is sim_final_range.
+template <typename TG, int QB, bool FILTER, bool GROUP, bool RANGE = false>
 int launch_wide_scan(const TG* G, const WideCall& c, const WidePlan& p) {
   constexpr size_t lds = (size_t)SCAN_NS * 64 * 256 * 2;
   static DevOnce once_s, once_a;
   cor_max_dyn_lds((const void*)sim_scan<TG, QB, true, true, FILTER, GROUP>, (int)lds, once_s);
-  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER>, (int)lds, once_a);
+  cor_max_dyn_lds((const void*)sim_scan<TG, QB, false, true, FILTER, false, RANGE>, (int)lds, once_a);
   unsigned* sg = (unsigned*)(c.w + p.off_sg);
   uint4* qimg = (uint4*)(c.w + p.off_img);
   const int Bqp = p.nqg * 256 * QB;
@@ -2713,17 +2981,21 @@ int launch_wide_scan(const TG* G, const WideCall& c, const WidePlan& p) {
     hipLaunchKernelGGL((sim_scan<TG, QB, true, true, FILTER, GROUP>), dim3(p.nqg * p.s_nsplit), dim3(512), lds, c.s, G, a);
     COR_CHECK_LAUNCH();
   }
-  if (const int e = launch_wide_tau<TG, GROUP>(c, p)) return e;
+  if (const int e = launch_wide_tau<TG, GROUP, RANGE>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.k = c.k; a.tau = (float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.rec_s = (float*)(c.w + p.off_recs);
   a.rec_g = (int*)(c.w + p.off_recg); a.cap = p.cap; a.tau_add = 0.f;
-  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER>), dim3(p.nqg * p.nsplit), dim3(512), lds, c.s, G, a);
+  if constexpr (RANGE) {
+    float* rng = (float*)(c.w + p.off_rng);
+    a.rng_a = rng; a.tau = rng + c.Bq; a.rng_h = rng + 2 * (size_t)c.Bq; a.sure = (int*)(c.w + p.off_sure);
+  }
+  hipLaunchKernelGGL((sim_scan<TG, QB, false, true, FILTER, false, RANGE>), dim3(p.nqg * p.nsplit), dim3(512), lds, c.s, G, a);
   COR_CHECK_LAUNCH();
-  return launch_wide_final<TG, true, FILTER, GROUP>(G, c, p);
+  return launch_wide_final<TG, true, FILTER, GROUP, RANGE>(G, c, p);
 }
 
 // the tile form (fp32, or C != 256): the same steps on sim_wide_scan and its entry lists, without a query image
-template <typename TG, bool FILTER, bool GROUP>
+template <typename TG, bool FILTER, bool GROUP, bool RANGE = false>
 int launch_wide_tiles(const TG* G, const WideCall& c, const WidePlan& p) {
   WideScanArgs a{};
   a.Bq = c.Bq; a.Ng = c.Ng; a.C = c.C; a.nqt = p.nqt; a.sg = (unsigned*)(c.w + p.off_sg); a.ngroups = p.ngroups;
@@ -2734,12 +3006,16 @@ int launch_wide_tiles(const TG* G, const WideCall& c, const WidePlan& p) {
     hipLaunchKernelGGL((sim_wide_scan<TG, true, FILTER, GROUP>), dim3(cdiv((long)p.nqt * p.s_nsplit, 4)), dim3(256), 0, c.s, c.Q, G, a);
     COR_CHECK_LAUNCH();
   }
-  if (const int e = launch_wide_tau<TG, GROUP>(c, p)) return e;
+  if (const int e = launch_wide_tau<TG, GROUP, RANGE>(c, p)) return e;
   a.nsplit = p.nsplit; a.tiles_per_split = p.tiles_per_split; a.ntiles = p.ntiles; a.tile_stride = 1;
   a.tau = (float*)(c.w + p.off_tau); a.cnt = (int*)(c.w + p.off_cnt); a.lst = (uint2*)(c.w + p.off_recs); a.cap = p.cap;
-  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, c.s, c.Q, G, a);
+  if constexpr (RANGE) {
+    float* rng = (float*)(c.w + p.off_rng);
+    a.rng_a = rng; a.tau = rng + c.Bq; a.rng_h = rng + 2 * (size_t)c.Bq; a.sure = (int*)(c.w + p.off_sure);
+  }
+  hipLaunchKernelGGL((sim_wide_scan<TG, false, FILTER, false, RANGE>), dim3(cdiv((long)p.nqt * p.nsplit, 4)), dim3(256), 0, c.s, c.Q, G, a);
   COR_CHECK_LAUNCH();
-  return launch_wide_final<TG, false, FILTER, GROUP>(G, c, p);
+  return launch_wide_final<TG, false, FILTER, GROUP, RANGE>(G, c, p);
 }
 
 // The three routes of the wide family: wide (33 <= k <= COR_TOPK_KMAX), filtered (FILTER, every k) and distinct groups (GROUP, every k,
@@ -2754,6 +3030,18 @@ int launch_wide(const TG* G, const WideCall& c) {
     }
   }
   return launch_wide_tiles<TG, FILTER, GROUP>(G, c, make_wide(c.Bq, c.Ng, c.k, false, FILTER, GROUP));
+}
+// cor_similarity_range: the wide route's two forms with the RANGE scan and selection, for every k
+template <typename TG>
+int launch_range(const TG* G, const WideCall& c) {
+  if constexpr (sizeof(TG) == 2) {
+    if (c.C == 256) {
+      const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, false, false, false, true);
+      if (p.qb == 2) return launch_wide_scan<TG, 2, false, false, true>(G, c, p);
+      return launch_wide_scan<TG, 1, false, false, true>(G, c, p);
+    }
+  }
+  return launch_wide_tiles<TG, false, false, true>(G, c, make_wide(c.Bq, c.Ng, c.k, false, false, false, false, true));
 }
 
 template <typename TG>
@@ -3171,7 +3459,7 @@ inline long i8_distinct_bytes(int Bq, int Ng, int k) {
 inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
 
 constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
-enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED, ROUTE_I8_DISTINCT };
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED, ROUTE_I8_DISTINCT, ROUTE_RANGE };
 
 // The argument checks of the search entry points, in the order (and with the codes) of the ABI. What differs by route: the
 // pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither; int8: the row scales, and
@@ -3179,6 +3467,7 @@ enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILT
 // (the plain call only at k > 32) and the distinct routes' sample bound.
 int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
   const bool own_ptrs = route == ROUTE_TOPK       ? true
+                        : route == ROUTE_RANGE    ? c.thr && c.out_count
                         : route == ROUTE_I8       ? c.gscale != nullptr
                         : route == ROUTE_I8_FILTERED ? c.gscale && c.rlab && c.qlab
                         : route == ROUTE_I8_DISTINCT ? c.gscale && c.grp && (c.rlab == nullptr) == (c.qlab == nullptr)
@@ -3188,7 +3477,8 @@ int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mo
   if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
   if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
   if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
-  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED || route == ROUTE_I8_DISTINCT) && (c.flags & ~COR_TOPK_NO_FALLBACK)) return COR_ENOSUPPORT;   // one route: no A/B partner
+  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED || route == ROUTE_I8_DISTINCT || route == ROUTE_RANGE) && (c.flags & ~COR_TOPK_NO_FALLBACK))
+    return COR_ENOSUPPORT;                             // one route: no A/B partner
   if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
   if (route == ROUTE_I8_DISTINCT && i8_distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;
   if ((((uintptr_t)c.Q | (uintptr_t)G | (uintptr_t)c.grp | (uintptr_t)c.rlab | (uintptr_t)c.gscale) & 15) || ((uintptr_t)c.w & 255)) return COR_EINVAL;
@@ -3225,6 +3515,21 @@ extern "C" int cor_similarity_topk(const float* Q, const void* G, int g_dtype, i
   const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream};
   if (const int e = check_topk_call(ROUTE_TOPK, c, G, COR_FILTER_EQ)) return e;
   return by_dtype(g_dtype, G, [&](auto* g) { return launch_topk(Q, g, Bq, Ng, C, k, g_offset, out_scores, out_idx, workspace, flags, c.s); });
+}
+
+extern "C" long cor_range_workspace_bytes(int Bq, int Ng, int k) {
+  if (!topk_shape_ok(Bq, Ng, k)) return COR_EINVAL;
+  return (long)std::max(make_wide(Bq, Ng, k, true, false, false, false, true).bytes, make_wide(Bq, Ng, k, false, false, false, false, true).bytes);
+}
+
+// range calls always take the wide route (every k): rows at or above a per-query floor, and how many there are (include/cor_amd.h)
+extern "C" int cor_similarity_range(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, const float* thresholds, int k,
+                                    long long g_offset, float* out_scores, long long* out_idx, int* out_count, void* workspace, int flags,
+                                    void* stream) {
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream, nullptr,
+                   thresholds, out_count};
+  if (const int e = check_topk_call(ROUTE_RANGE, c, G, COR_FILTER_EQ)) return e;
+  return by_dtype(g_dtype, G, [&](auto* g) { return launch_range(g, c); });
 }
 
 extern "C" long cor_topk_filtered_workspace_bytes(int Bq, int Ng, int k) {

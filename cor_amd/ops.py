@@ -529,6 +529,51 @@ def similarity_topk_filtered(Q, G, k, row_labels, query_labels, mode="eq", g_off
     return scores, idx
 
 
+def _range_floors(thresholds, Bq, who):
+    """The shape and dtype checks of the floors of a range search (nothing moves): a Python number, or an f32 tensor [Bq]."""
+    if isinstance(thresholds, (int, float)) and not isinstance(thresholds, bool):
+        return float(thresholds)
+    if not isinstance(thresholds, torch.Tensor):
+        raise ValueError(f"{who}: thresholds must be a float or an f32 tensor [{Bq}], got {type(thresholds).__name__}")
+    if thresholds.dim() != 1 or thresholds.shape[0] != Bq:
+        raise ValueError(f"{who}: thresholds must have shape ({Bq},), got {tuple(thresholds.shape)}")
+    if thresholds.dtype != torch.float32:
+        raise ValueError(f"{who}: thresholds must be float32, got {thresholds.dtype}")
+    return thresholds
+
+
+def similarity_range(Q, G, thresholds, k, g_offset=0, flags=0):
+    """Threshold search: per query b the rows whose score is at least thresholds[b], and how many there are.
+    Returns (scores f32[Bq,k], idx i64[Bq,k], count i32[Bq]). The score is similarity_topk's fmaf-chain score (oracle/c/sim_chain.c; 16-bit
+    rows widened exactly, the query rounded to the gallery dtype); membership is the IEEE `score >= floor` (a NaN floor: no row; -inf:
+    every row; +0.0 and -0.0 are one floor). count[b] is the EXACT number of members for any gallery size; the lists hold the first k
+    members by (score desc, index asc) and then the (-inf, -1) tail, i.e. similarity_topk's lists with every entry below the floor
+    turned into tail. Scores, indices and counts are bit-identical to that definition on the CPU for fp32 / bf16 / fp16 rows, every C
+    and 1 <= k <= 256.
+    thresholds: a Python float (broadcast by a device fill, no host scalar assignment) or an f32 tensor [Bq] on Q's device.
+    Route (include/cor_amd.h): the wide route's sample and threshold, then one full scan that appends the list candidates, counts the
+    rows at least delta_q above the floor in registers and appends the rows within delta_q of it for the chain to decide; delta_q is
+    twice the bound of |scan score - chain score|, so neither decision can differ from the chain's. No allocation inside the call, no
+    host synchronisation, capturable in a graph. A candidate overflow is repaired on the device by a chain pass that ranks and counts.
+    flags: nat.TOPK_NO_FALLBACK (tests: an overflowed query carries index -2 in every slot and count -2)."""
+    who = "similarity_range"
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if isinstance(Q, torch.Tensor) and Q.dim() == 2:
+        thresholds = _range_floors(thresholds, Q.shape[0], who)
+    Bq, Ng, C = _topk_front(who, Q, G, k)
+    if isinstance(thresholds, float):
+        thr = torch.full((Bq,), thresholds, dtype=torch.float32, device=Q.device)
+    else:
+        _dev(thresholds)
+        thr = thresholds.contiguous()
+    ws, scores, idx = _topk_buffers("cor_range_workspace_bytes", Q, Bq, Ng, k)
+    count = torch.empty((Bq,), dtype=torch.int32, device=Q.device)
+    nat.check(_lib().cor_similarity_range(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, thr.data_ptr(), k, int(g_offset), scores.data_ptr(),
+                                          idx.data_ptr(), count.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_range")
+    return scores, idx, count
+
+
 def similarity_topk_distinct(Q, G, k, row_groups, row_labels=None, query_labels=None, mode="eq", g_offset=0, flags=0):
     """Top-k DISTINCT groups: row_groups int32[Ng] gives every gallery row a group id (the source image of a region; a negative id
     makes the row a group of its own). Per query, each group's representative is its best allowed row by (chain score desc, index

@@ -334,6 +334,22 @@ class GalleryShard:
         return _search(self, "GalleryShard.search", (ops.similarity_topk, ops.similarity_topk_filtered, ops.similarity_topk_distinct), (self.rows,),
                        queries, k, query_labels, mode, distinct)
 
+    def range_search(self, queries: torch.Tensor, min_score, k: int):
+        """Threshold search (ops.similarity_range): queries f32[Bq,C] -> (scores f32[Bq,k], global idx i64[Bq,k], count i32[Bq]) on the
+        GPU. count[b] is the exact number of rows of this shard whose chain score is at least min_score (a float, or an f32 tensor [Bq]
+        of per-query floors), whatever the shard's size; the lists hold the first k of them by (score desc, index asc), then the
+        (-inf, -1) tail. Open-set retrieval accepts a query when count > 0; ingest-time de-duplication asks with the new rows as
+        queries and a floor near 1. An empty shard: all-missing lists and zero counts."""
+        q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
+        if self.rows.shape[0] == 0:
+            if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
+                raise ValueError(f"GalleryShard.range_search: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
+            return (*_missing_lists(q.shape[0], k, q.device), torch.zeros((q.shape[0],), dtype=torch.int32, device=q.device))
+        if isinstance(min_score, torch.Tensor):
+            min_score = min_score.reshape(-1).to(q.device)
+        with _on(self.rows.device):
+            return ops.similarity_range(q, self.rows, min_score, k, g_offset=self.offset)
+
     def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int | None = None, return_pos: bool = False):
         """The second stage of a two-stage search: queries f32[Bq,C], cand i64[Bq,kin] global row ids (a coarse search's idx, a union
         of lists, the ids of known rows; at most 4096 per query) -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]) on the GPU: the
@@ -648,6 +664,30 @@ class GallerySet:
             if distinct:
                 return merge_topk_device([r[0] for r in res], [r[1] for r in res], k, [_entry_groups(sh, r[1]) for sh, r in zip(live, res)])[:2]
             return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
+
+    def range_search(self, queries: torch.Tensor, min_score, k: int):
+        """GalleryShard.range_search over all segments: (scores f32[Bq,k], global idx i64[Bq,k], count i32[Bq]) on the GPU. One call per
+        non-empty segment; the lists are merged on the device (merge_topk_device: every list holds only rows at or above the floor, so
+        the merged list does) and the counts are added there: the segments' row ranges are disjoint, so the sum is the exact count over
+        the set. No segment with rows: all-missing lists and zero counts. An int8 segment raises ValueError: the range search has no
+        int8 form yet (QuantizedShard has no range_search)."""
+        live = self._live()
+        for sh in live:
+            if isinstance(sh, QuantizedShard):
+                raise ValueError("GallerySet.range_search: the segment at offset %d holds int8 rows; the range search covers fp32 / bf16 / "
+                                 "fp16 segments only (no int8 range search yet)" % int(sh.offset))
+        if not live:
+            if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
+                raise ValueError(f"GallerySet.range_search: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
+            B = queries.reshape(-1, queries.shape[-1]).shape[0]
+            dev = self._segments[0].rows.device if self._segments else queries.device
+            return (*_missing_lists(B, k, dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+        res = [sh.range_search(queries, min_score, k) for sh in live]
+        if len(live) == 1:
+            return res[0]
+        with torch.cuda.device(live[0].rows.device):
+            scores, idx = merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
+            return scores, idx, torch.stack([r[2] for r in res]).sum(0, dtype=torch.int32)
 
     def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int):
         """GalleryShard.rescore over all segments: (scores f32[Bq,k], global idx i64[Bq,k]) on the GPU. Every non-empty segment

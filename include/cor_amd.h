@@ -342,6 +342,32 @@ int cor_similarity_topk_filtered(const float* Q, const void* G, int g_dtype, int
                                  const int* row_labels, const int* query_labels, int filter_mode, float* out_scores, long long* out_idx,
                                  void* workspace, int flags, void* stream);
 
+/* Threshold (range) search: per query b, the rows that score at least thresholds[b], and how many there are.
+ *   score(b, g)  = the fp32 fmaf-chain score of cor_similarity_topk (oracle/c/sim_chain.c; 16-bit rows widened exactly, the query rounded
+ *                  to the gallery dtype), for COR_F32 / COR_BF16 / COR_F16 and every C that call takes.
+ *   In(b)        = { g < Ng : score(b, g) >= thresholds[b] } by the IEEE comparison: a NaN floor gives the empty set, -inf every row,
+ *                  +0.0 and -0.0 are the same floor. thresholds: device f32 [Bq].
+ *   out_count[b] = |In(b)| (device i32 [Bq]), EXACT for every Ng: COR_TOPK_KMAX caps the listed rows only.
+ *   out_scores / out_idx [Bq,k], 1 <= k <= COR_TOPK_KMAX: the first k members of In(b) by (score desc, global index asc), indices
+ *                  g + g_offset, then the (-inf, -1) tail: cor_similarity_topk's lists with every entry below the floor turned into tail.
+ * Scores, indices and counts are bit-identical to that definition evaluated on the CPU, for every dtype, C and k.
+ * Route: every call, whatever k, takes the wide route of cor_similarity_topk (sample pass, tau_q by sim_tau_wide). With delta_q the bound
+ * of |scan score - chain score| that route already uses (0 for fp32 rows), the full scan sorts every scan score s into: s >= max(tau_q,
+ * thr_q - delta_q): a list candidate, appended as before; s >= thr_q + delta_q: a sure member, counted in a register of its stream and
+ * written once per slice (no atomics); thr_q - delta_q <= s < thr_q + delta_q: a band row, appended so that the chain decides it. delta_q
+ * is twice the bound, so s >= thr_q + delta_q implies chain >= thr_q and s < thr_q - delta_q implies chain < thr_q (rows of unit norm, as
+ * for the lists). The selection kernel ranks the candidates, drops ranked rows whose chain score is below the floor, re-scores the band
+ * rows and adds those at or above the floor to the summed sure counts. A candidate overflow (which may have lost band rows), or more than
+ * 16 384 band rows of one query, sends the query to a chain pass over the shard that ranks AND counts in the same block (exact; slow;
+ * rare: ~4 ms per query at 1M rows).
+ * Argument checks and codes in cor_similarity_topk's order; a null thresholds or out_count: COR_EINVAL. Flags: COR_TOPK_NO_FALLBACK keeps
+ * its meaning (an overflowed query returns index -2 in every slot and count -2); every other flag: COR_ENOSUPPORT.
+ * workspace >= cor_range_workspace_bytes(Bq, Ng, k) (>= cor_topk_workspace_bytes at k >= 33). No allocation, no host synchronisation;
+ * capturable in a graph. */
+long cor_range_workspace_bytes(int Bq, int Ng, int k);
+int cor_similarity_range(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, const float* thresholds, int k, long long g_offset,
+                         float* out_scores, long long* out_idx, int* out_count, void* workspace, int flags, void* stream);
+
 /* Distinct-group top-k: every gallery row g has an int32 group id row_groups[g] (shard-local row g; 16-byte aligned; typically the source
  * image of a region); a negative id makes the row a group of its own. Per query b, among the rows ALLOWED for b, each group's
  * representative is its best row by (chain score desc, global index asc), and the result is the k best representatives ordered the same
