@@ -78,6 +78,8 @@ SIGNATURES = {
     "cor_similarity_topk_filtered": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _i, _p, _p, _p, _i, _p],
     "cor_range_workspace_bytes": [_i, _i, _i],
     "cor_similarity_range": [_p, _p, _i, _i, _i, _i, _p, _i, _ll, _p, _p, _p, _p, _i, _p],
+    "cor_range_filtered_workspace_bytes": [_i, _i, _i],
+    "cor_similarity_range_filtered": [_p, _p, _i, _i, _i, _i, _p, _i, _ll, _p, _p, _i, _p, _p, _p, _p, _i, _p],
     "cor_topk_distinct_workspace_bytes": [_i, _i, _i],
     "cor_topk_distinct_sample_values": [_i, _i, _i],
     "cor_similarity_topk_distinct": [_p, _p, _i, _i, _i, _i, _i, _ll, _p, _p, _p, _i, _p, _p, _p, _i, _p],
@@ -105,8 +107,8 @@ SIGNATURES = {
     "cor_fuse_lists": [_p, _p, _i, _i, _i, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
-            "cor_range_workspace_bytes": _l, "cor_topk_i8_workspace_bytes": _l, "cor_topk_i8_filtered_workspace_bytes": _l,
-            "cor_topk_i8_distinct_workspace_bytes": _l,
+            "cor_range_workspace_bytes": _l, "cor_range_filtered_workspace_bytes": _l, "cor_topk_i8_workspace_bytes": _l,
+            "cor_topk_i8_filtered_workspace_bytes": _l, "cor_topk_i8_distinct_workspace_bytes": _l,
             "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l,
             "cor_rescore_i8_workspace_bytes": _l, "cor_fuse_lists_workspace_bytes": _l}
 

@@ -454,6 +454,10 @@ __device__ __forceinline__ void append_entry(uint2* dst, int& n, int cap, float 
 // share ONE register each: lane (n16, rq) keeps those of query block rq % NQ and the guarded branch fetches them across lanes; the sure
 // count shares ncand's register (low 16 bits; the records above them): make_wide keeps a slice at <= 4095 super-tiles = 65 520 scores per
 // lane. With a counter of its own per query block the QB = 2 instantiation spilled four registers.
+// FILTER + RANGE (cor_similarity_range_filtered): the label mask first, then the RANGE branch on the masked scores; B_q, A_q and H_q are
+// >= -3e38, so a masked -inf is never counted, never a band row and never appended. Instantiated with QB = 1 only: QB = 2 (254 VGPRs
+// without the filter) needs the lane's query labels and row labels as well and came out of the compiler with 256 VGPRs, four spilled
+// registers and 20 bytes of scratch per lane; make_wide plans the filtered range with QB = 1 for every Bq (170 VGPRs, no spill).
 template <typename TG, int QB, bool SAMPLE, bool WIDE = false, bool FILTER = false, bool GROUP = false, bool RANGE = false>
 __global__ void __launch_bounds__(512, 2) sim_scan(const TG* __restrict__ G, const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2009,21 +2013,27 @@ __device__ void wide_brute_force(const TG* __restrict__ G, int Ng, int C, const 
 }
 // The fallback of cor_similarity_range for one query: a chain pass over the shard counts the rows at or above the floor, wide_brute_force
 // ranks into LDS (tmp_s / tmp_i [k], outside the buffers it works in), and the ranked rows below the floor leave as tail. Six chain passes.
-template <typename TG>
+// FILTER (cor_similarity_range_filtered): only the rows allowed for the query (label ql, COR_FILTER_NE if ne) are counted and ranked.
+template <typename TG, bool FILTER = false>
 __device__ void range_brute_force(const TG* __restrict__ G, int Ng, int C, const float* qs, int k, long long g_offset, float thr, float* sl_s,
                                   int* sl_i, unsigned long long* keys, int* hist, float* tmp_s, long long* tmp_i, float* out_s, long long* out_i,
-                                  int* out_count) {
+                                  int* out_count, const int* rlab = nullptr, int ql = -1, int ne = 0) {
   __shared__ int members;
   const int tid = threadIdx.x;
   if (tid == 0) members = 0;
   __syncthreads();
   int mine = 0;
-  for (int g = tid; g < Ng; g += 256) mine += chain_score_c<TG>(G, g, C, qs) >= thr ? 1 : 0;
+  if constexpr (FILTER) {
+    for (int g = tid; g < Ng; g += 256) mine += row_allowed(rlab, g, ql, ne) && chain_score_c<TG>(G, g, C, qs) >= thr ? 1 : 0;
+  } else {
+    for (int g = tid; g < Ng; g += 256) mine += chain_score_c<TG>(G, g, C, qs) >= thr ? 1 : 0;
+  }
   if (mine) atomicAdd(&members, mine);
-  wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, tmp_s, tmp_i);
+  if constexpr (FILTER) wide_brute_force<TG, true>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, tmp_s, tmp_i, rlab, ql, ne);
+  else wide_brute_force<TG>(G, Ng, C, qs, k, g_offset, sl_s, sl_i, keys, hist, tmp_s, tmp_i);
   __syncthreads();
   for (int j = tid; j < k; j += 256) {
-    const bool in = j < Ng && tmp_s[j] >= thr;         // (the first min(k, Ng) slots hold rows)
+    const bool in = j < Ng && tmp_s[j] >= thr;         // (the first min(k, Ng, allowed rows) slots hold rows; the others are (-inf, -1) already)
     out_s[j] = in ? tmp_s[j] : -INFINITY;
     out_i[j] = in ? tmp_i[j] : -1LL;
   }
@@ -2115,7 +2125,10 @@ __global__ void __launch_bounds__(256) sim_wide_scan(const float* __restrict__ Q
       for (int j = 0; j < 4; ++j) {
         const int row = g0 + 8 * j + 4 * h;
         int4 l;
-        if (row + 4 <= Ng) l = *(const int4*)(a.rlab + row);
+        if constexpr (RANGE) {                         // branch-free (a row past the shard is -inf already, whatever label it reads): the two-way
+          l.x = a.rlab[min(row, Ng - 1)]; l.y = a.rlab[min(row + 1, Ng - 1)];      // load held exec masks in SGPRs the fp32 RANGE form lacks
+          l.z = a.rlab[min(row + 2, Ng - 1)]; l.w = a.rlab[min(row + 3, Ng - 1)];
+        } else if (row + 4 <= Ng) l = *(const int4*)(a.rlab + row);
         else { l.x = row < Ng ? a.rlab[row] : 0; l.y = row + 1 < Ng ? a.rlab[row + 1] : 0; l.z = row + 2 < Ng ? a.rlab[row + 2] : 0; l.w = 0; }
         const int lv[4] = {l.x, l.y, l.z, l.w};
 #pragma unroll
@@ -2300,8 +2313,13 @@ __global__ void __launch_bounds__(256) sim_final_wide(const float* __restrict__ 
 // no_fallback it leaves index -2 in every slot and count -2.
 constexpr int BAND_MAX = 16384;                        // band rows per query held in LDS (64 KiB: still one block per CU, as sim_final_wide)
 constexpr size_t FINAL_RANGE_LDS = FINAL_WIDE_LDS + (size_t)BAND_MAX * 4;
-struct RangeFinal { const float* thr; const float* ra; const float* rb; const float* rh; const int* sure; int* out_count; };
-template <typename TG, bool RECORDS>
+struct RangeFinal {
+  const float* thr; const float* ra; const float* rb; const float* rh; const int* sure; int* out_count;
+  const int* rlab; const int* qlab; int ne;            // FILTER: the labels, for the fallback
+};
+// FILTER (cor_similarity_range_filtered): the scans stored and counted allowed scores only (a masked record slot is -inf: below A_q and
+// B_q, neither candidate nor band row), so only the fallback differs: it counts and ranks the rows r.rlab / r.qlab / r.ne allow.
+template <typename TG, bool RECORDS, bool FILTER = false>
 __global__ void __launch_bounds__(256) sim_final_range(const float* __restrict__ Q, const TG* __restrict__ G, int Ng, int C, int k, long long g_offset,
                                                        const int* __restrict__ cnt, int nstreams, int cap, const float* __restrict__ rec_s,
                                                        const int* __restrict__ rec_g, const uint2* __restrict__ lst, float* out_s, long long* out_i,
@@ -2411,8 +2429,12 @@ __global__ void __launch_bounds__(256) sim_final_range(const float* __restrict__
       if (tid == 0) r.out_count[q] = -2;
       return;
     }
-    range_brute_force<TG>(G, Ng, C, qs, k, g_offset, thr, sl_s, sl_i, keys, hist, (float*)ci, (long long*)(ci + 256), out_s + (long)q * k,
-                          out_i + (long)q * k, r.out_count + q);
+    if constexpr (FILTER)
+      range_brute_force<TG, true>(G, Ng, C, qs, k, g_offset, thr, sl_s, sl_i, keys, hist, (float*)ci, (long long*)(ci + 256), out_s + (long)q * k,
+                                  out_i + (long)q * k, r.out_count + q, r.rlab, r.qlab[q], r.ne);
+    else
+      range_brute_force<TG>(G, Ng, C, qs, k, g_offset, thr, sl_s, sl_i, keys, hist, (float*)ci, (long long*)(ci + 256), out_s + (long)q * k,
+                            out_i + (long)q * k, r.out_count + q);
     return;
   }
   if (tid == 0) r.out_count[q] = rcount;
@@ -2819,6 +2841,8 @@ struct WidePlan {
 // range = cor_similarity_range (any k, no filter, no groups): the streams also take the band rows (scan within delta_q of the floor: about
 // 2 delta_q * Ng * the score density at the floor per query, some 830 rows over ~1000 streams at 1M unit rows of C = 256 and a floor of 0), so
 // every stream gets 6 more places; the bounds and the sure counts sit behind the other buffers.
+// filter + range = cor_similarity_range_filtered: the filtered plan (interleaved slices, four sample values per group, the 128 clamp, which
+// satisfies the 4095 bound) with the range plan's extra places and buffers; the scan form always with qb = 1 (query groups of 256).
 inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false, bool group = false, bool i8 = false, bool range = false) {
   WidePlan p{};
   p.scan = scan;
@@ -2826,7 +2850,7 @@ inline WidePlan make_wide(int Bq, int Ng, int k, bool scan, bool filter = false,
   p.ntiles = cdiv(Ng, rows);
   int want;
   if (scan) {
-    p.qb = i8 || Bq > 256 ? 2 : 1;
+    p.qb = (i8 || Bq > 256) && !(filter && range) ? 2 : 1;   // (filter + range: sim_scan<QB = 2> cannot hold labels and range state, see there)
     p.nqg = cdiv(Bq, 256 * p.qb);
     want = device_cus() / p.nqg;                       // one resident block per CU
     if (want > 256) want = 256;
@@ -2939,10 +2963,10 @@ int launch_wide_final(const TG* G, const WideCall& c, const WidePlan& p) {
   const int no_fallback = (c.flags & COR_TOPK_NO_FALLBACK) ? 1 : 0;
   if constexpr (RANGE) {
     const float* rng = (const float*)(c.w + p.off_rng);
-    const RangeFinal r{c.thr, rng, rng + c.Bq, rng + 2 * (size_t)c.Bq, (const int*)(c.w + p.off_sure), c.out_count};
-    cor_max_dyn_lds((const void*)sim_final_range<TG, RECORDS>, (int)FINAL_RANGE_LDS, once);
-    hipLaunchKernelGGL((sim_final_range<TG, RECORDS>), dim3(c.Bq), dim3(256), FINAL_RANGE_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, cnt, p.nstreams,
-                       p.cap, rec_s, rec_g, lst, c.out_s, c.out_i, no_fallback, r);
+    const RangeFinal r{c.thr, rng, rng + c.Bq, rng + 2 * (size_t)c.Bq, (const int*)(c.w + p.off_sure), c.out_count, c.rlab, c.qlab, c.ne};
+    cor_max_dyn_lds((const void*)sim_final_range<TG, RECORDS, FILTER>, (int)FINAL_RANGE_LDS, once);
+    hipLaunchKernelGGL((sim_final_range<TG, RECORDS, FILTER>), dim3(c.Bq), dim3(256), FINAL_RANGE_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, cnt,
+                       p.nstreams, p.cap, rec_s, rec_g, lst, c.out_s, c.out_i, no_fallback, r);
   } else if constexpr (GROUP) {
     cor_max_dyn_lds((const void*)sim_final_distinct<TG, RECORDS>, (int)FINAL_DISTINCT_LDS, once);
     hipLaunchKernelGGL((sim_final_distinct<TG, RECORDS>), dim3(c.Bq), dim3(256), FINAL_DISTINCT_LDS, c.s, c.Q, G, c.Ng, c.C, c.k, c.g_offset, tau, cnt,
@@ -3031,17 +3055,19 @@ int launch_wide(const TG* G, const WideCall& c) {
   }
   return launch_wide_tiles<TG, FILTER, GROUP>(G, c, make_wide(c.Bq, c.Ng, c.k, false, FILTER, GROUP));
 }
-// cor_similarity_range: the wide route's two forms with the RANGE scan and selection, for every k
-template <typename TG>
+// cor_similarity_range: the wide route's two forms with the RANGE scan and selection, for every k. FILTER: cor_similarity_range_filtered,
+// the filtered plan and sample with the RANGE scan behind the label mask.
+template <bool FILTER, typename TG>
 int launch_range(const TG* G, const WideCall& c) {
   if constexpr (sizeof(TG) == 2) {
     if (c.C == 256) {
-      const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, false, false, false, true);
-      if (p.qb == 2) return launch_wide_scan<TG, 2, false, false, true>(G, c, p);
-      return launch_wide_scan<TG, 1, false, false, true>(G, c, p);
+      const WidePlan p = make_wide(c.Bq, c.Ng, c.k, true, FILTER, false, false, true);
+      if constexpr (!FILTER)                           // (the filtered range plan has qb = 1 for every Bq)
+        if (p.qb == 2) return launch_wide_scan<TG, 2, false, false, true>(G, c, p);
+      return launch_wide_scan<TG, 1, FILTER, false, true>(G, c, p);
     }
   }
-  return launch_wide_tiles<TG, false, false, true>(G, c, make_wide(c.Bq, c.Ng, c.k, false, false, false, false, true));
+  return launch_wide_tiles<TG, FILTER, false, true>(G, c, make_wide(c.Bq, c.Ng, c.k, false, FILTER, false, false, true));
 }
 
 template <typename TG>
@@ -3459,7 +3485,7 @@ inline long i8_distinct_bytes(int Bq, int Ng, int k) {
 inline bool topk_shape_ok(int Bq, int Ng, int k) { return Bq > 0 && Ng > 0 && k > 0 && k <= COR_TOPK_KMAX; }
 
 constexpr int K32_ONLY_FLAGS = COR_TOPK_FORCE_LISTS | COR_TOPK_WAVE_FINAL;   // the register-list / one-wave kernels: k <= 32, never the wide family
-enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED, ROUTE_I8_DISTINCT, ROUTE_RANGE };
+enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILTERED, ROUTE_I8_DISTINCT, ROUTE_RANGE, ROUTE_RANGE_FILTERED };
 
 // The argument checks of the search entry points, in the order (and with the codes) of the ABI. What differs by route: the
 // pointers it needs (filtered: both label vectors; distinct: the group ids, and the labels both or neither; int8: the row scales, and
@@ -3468,6 +3494,7 @@ enum Route { ROUTE_TOPK, ROUTE_FILTERED, ROUTE_DISTINCT, ROUTE_I8, ROUTE_I8_FILT
 int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mode) {
   const bool own_ptrs = route == ROUTE_TOPK       ? true
                         : route == ROUTE_RANGE    ? c.thr && c.out_count
+                        : route == ROUTE_RANGE_FILTERED ? c.thr && c.out_count && c.rlab && c.qlab
                         : route == ROUTE_I8       ? c.gscale != nullptr
                         : route == ROUTE_I8_FILTERED ? c.gscale && c.rlab && c.qlab
                         : route == ROUTE_I8_DISTINCT ? c.gscale && c.grp && (c.rlab == nullptr) == (c.qlab == nullptr)
@@ -3477,7 +3504,8 @@ int check_topk_call(Route route, const WideCall& c, const void* G, int filter_mo
   if (filter_mode != COR_FILTER_EQ && filter_mode != COR_FILTER_NE) return COR_EINVAL;
   if (c.k > COR_TOPK_KMAX || c.C > 256 || (c.C & 15)) return COR_ENOSUPPORT;
   if ((route != ROUTE_TOPK || c.k > 32) && (c.flags & K32_ONLY_FLAGS)) return COR_ENOSUPPORT;
-  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED || route == ROUTE_I8_DISTINCT || route == ROUTE_RANGE) && (c.flags & ~COR_TOPK_NO_FALLBACK))
+  if ((route == ROUTE_I8 || route == ROUTE_I8_FILTERED || route == ROUTE_I8_DISTINCT || route == ROUTE_RANGE || route == ROUTE_RANGE_FILTERED) &&
+      (c.flags & ~COR_TOPK_NO_FALLBACK))
     return COR_ENOSUPPORT;                             // one route: no A/B partner
   if (route == ROUTE_DISTINCT && distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;   // (the plan keeps it: sim_tau_distinct's LDS sort)
   if (route == ROUTE_I8_DISTINCT && i8_distinct_sample_values(c.Bq, c.Ng, c.k) > TAU_DISTINCT_MAX) return COR_ENOSUPPORT;
@@ -3529,7 +3557,24 @@ extern "C" int cor_similarity_range(const float* Q, const void* G, int g_dtype, 
   const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, nullptr, nullptr, 0, out_scores, out_idx, (char*)workspace, flags, (hipStream_t)stream, nullptr,
                    thresholds, out_count};
   if (const int e = check_topk_call(ROUTE_RANGE, c, G, COR_FILTER_EQ)) return e;
-  return by_dtype(g_dtype, G, [&](auto* g) { return launch_range(g, c); });
+  return by_dtype(g_dtype, G, [&](auto* g) { return launch_range<false>(g, c); });
+}
+
+extern "C" long cor_range_filtered_workspace_bytes(int Bq, int Ng, int k) {
+  if (!topk_shape_ok(Bq, Ng, k)) return COR_EINVAL;
+  // (the scan form's plan has qb = 1 where the filtered top-k's has 2, so fewer slices and streams: not below that call's size all the same)
+  return std::max(wide_bytes(Bq, Ng, k, true, false), (long)std::max(make_wide(Bq, Ng, k, true, true, false, false, true).bytes,
+                                                                     make_wide(Bq, Ng, k, false, true, false, false, true).bytes));
+}
+
+// filtered range calls: the range route with the filter inside its sample, scan and fallback (launch_range<true>)
+extern "C" int cor_similarity_range_filtered(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, const float* thresholds, int k,
+                                             long long g_offset, const int* row_labels, const int* query_labels, int filter_mode,
+                                             float* out_scores, long long* out_idx, int* out_count, void* workspace, int flags, void* stream) {
+  const WideCall c{Q, Bq, Ng, C, k, g_offset, nullptr, row_labels, query_labels, filter_mode == COR_FILTER_NE ? 1 : 0, out_scores, out_idx,
+                   (char*)workspace, flags, (hipStream_t)stream, nullptr, thresholds, out_count};
+  if (const int e = check_topk_call(ROUTE_RANGE_FILTERED, c, G, filter_mode)) return e;
+  return by_dtype(g_dtype, G, [&](auto* g) { return launch_range<true>(g, c); });
 }
 
 extern "C" long cor_topk_filtered_workspace_bytes(int Bq, int Ng, int k) {

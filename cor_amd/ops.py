@@ -542,6 +542,22 @@ def _range_floors(thresholds, Bq, who):
     return thresholds
 
 
+def _range_front(who, Q, G, thresholds, k, mode="eq"):
+    """The argument checks the range wrappers share, before anything touches the device (k, the floors, then _topk_front), and the floors
+    as a device vector: (Bq, Ng, C, thr f32 [Bq])."""
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if isinstance(Q, torch.Tensor) and Q.dim() == 2:
+        thresholds = _range_floors(thresholds, Q.shape[0], who)
+    Bq, Ng, C = _topk_front(who, Q, G, k, mode)
+    if isinstance(thresholds, float):
+        thr = torch.full((Bq,), thresholds, dtype=torch.float32, device=Q.device)
+    else:
+        _dev(thresholds)
+        thr = thresholds.contiguous()
+    return Bq, Ng, C, thr
+
+
 def similarity_range(Q, G, thresholds, k, g_offset=0, flags=0):
     """Threshold search: per query b the rows whose score is at least thresholds[b], and how many there are.
     Returns (scores f32[Bq,k], idx i64[Bq,k], count i32[Bq]). The score is similarity_topk's fmaf-chain score (oracle/c/sim_chain.c; 16-bit
@@ -556,21 +572,32 @@ def similarity_range(Q, G, thresholds, k, g_offset=0, flags=0):
     twice the bound of |scan score - chain score|, so neither decision can differ from the chain's. No allocation inside the call, no
     host synchronisation, capturable in a graph. A candidate overflow is repaired on the device by a chain pass that ranks and counts.
     flags: nat.TOPK_NO_FALLBACK (tests: an overflowed query carries index -2 in every slot and count -2)."""
-    who = "similarity_range"
-    if not 1 <= int(k) <= nat.TOPK_KMAX:
-        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
-    if isinstance(Q, torch.Tensor) and Q.dim() == 2:
-        thresholds = _range_floors(thresholds, Q.shape[0], who)
-    Bq, Ng, C = _topk_front(who, Q, G, k)
-    if isinstance(thresholds, float):
-        thr = torch.full((Bq,), thresholds, dtype=torch.float32, device=Q.device)
-    else:
-        _dev(thresholds)
-        thr = thresholds.contiguous()
+    Bq, Ng, C, thr = _range_front("similarity_range", Q, G, thresholds, k)
     ws, scores, idx = _topk_buffers("cor_range_workspace_bytes", Q, Bq, Ng, k)
     count = torch.empty((Bq,), dtype=torch.int32, device=Q.device)
     nat.check(_lib().cor_similarity_range(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, thr.data_ptr(), k, int(g_offset), scores.data_ptr(),
                                           idx.data_ptr(), count.data_ptr(), ws.data_ptr(), int(flags), _s()), "cor_similarity_range")
+    return scores, idx, count
+
+
+def similarity_range_filtered(Q, G, thresholds, k, row_labels, query_labels, mode="eq", g_offset=0, flags=0):
+    """similarity_range over the ALLOWED rows only (the rule of similarity_topk_filtered: query_labels[b] < 0 is unrestricted, mode "eq"
+    keeps the rows that carry the query's label, "ne" the rows that do not). Returns (scores f32[Bq,k], idx i64[Bq,k], count i32[Bq]):
+    count[b] is the EXACT number of allowed rows whose chain score is at least thresholds[b]; the lists are similarity_topk_filtered's
+    with every entry below the floor turned into (-inf, -1) tail; a query with no allowed row gets count 0 and only the tail. Bit-identical
+    to that definition for fp32 / bf16 / fp16 rows, every C and 1 <= k <= 256. Typical use: mode "ne" with the query's own image id asks
+    "does this region already exist in ANOTHER image" (count > 0). thresholds as in similarity_range; labels as in
+    similarity_topk_filtered (int32, int64 is converted). No allocation inside the call, no host synchronisation when floors and labels
+    already live on the device, capturable in a graph. flags: nat.TOPK_NO_FALLBACK (tests: index -2 in every slot and count -2)."""
+    who = "similarity_range_filtered"
+    Bq, Ng, C, thr = _range_front(who, Q, G, thresholds, k, mode)
+    rl = _labels(row_labels, Ng, "row_labels", Q.device, who)
+    qlab = _labels(query_labels, Bq, "query_labels", Q.device, who)
+    ws, scores, idx = _topk_buffers("cor_range_filtered_workspace_bytes", Q, Bq, Ng, k)
+    count = torch.empty((Bq,), dtype=torch.int32, device=Q.device)
+    nat.check(_lib().cor_similarity_range_filtered(Q.data_ptr(), G.data_ptr(), _dt(G), Bq, Ng, C, thr.data_ptr(), k, int(g_offset), rl.data_ptr(),
+                                                   qlab.data_ptr(), _FILTER_MODES[mode], scores.data_ptr(), idx.data_ptr(), count.data_ptr(),
+                                                   ws.data_ptr(), int(flags), _s()), "cor_similarity_range_filtered")
     return scores, idx, count
 
 

@@ -334,12 +334,16 @@ class GalleryShard:
         return _search(self, "GalleryShard.search", (ops.similarity_topk, ops.similarity_topk_filtered, ops.similarity_topk_distinct), (self.rows,),
                        queries, k, query_labels, mode, distinct)
 
-    def range_search(self, queries: torch.Tensor, min_score, k: int):
+    def range_search(self, queries: torch.Tensor, min_score, k: int, query_labels=None, mode: str = "eq"):
         """Threshold search (ops.similarity_range): queries f32[Bq,C] -> (scores f32[Bq,k], global idx i64[Bq,k], count i32[Bq]) on the
         GPU. count[b] is the exact number of rows of this shard whose chain score is at least min_score (a float, or an f32 tensor [Bq]
         of per-query floors), whatever the shard's size; the lists hold the first k of them by (score desc, index asc), then the
         (-inf, -1) tail. Open-set retrieval accepts a query when count > 0; ingest-time de-duplication asks with the new rows as
-        queries and a floor near 1. An empty shard: all-missing lists and zero counts."""
+        queries and a floor near 1. An empty shard: all-missing lists and zero counts.
+        query_labels (int32[Bq], < 0 = unrestricted) and mode as in search: only the rows the shard's labels allow are counted and
+        listed (ops.similarity_range_filtered), e.g. mode "ne" with the query's own image id; None: the whole shard."""
+        if query_labels is not None and self.labels is None:
+            raise ValueError("GalleryShard.range_search: query_labels given but the shard has no row labels")
         q = queries.reshape(-1, queries.shape[-1]).to(self.rows.device, torch.float32).contiguous()
         if self.rows.shape[0] == 0:
             if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
@@ -348,7 +352,10 @@ class GalleryShard:
         if isinstance(min_score, torch.Tensor):
             min_score = min_score.reshape(-1).to(q.device)
         with _on(self.rows.device):
-            return ops.similarity_range(q, self.rows, min_score, k, g_offset=self.offset)
+            if query_labels is None:
+                return ops.similarity_range(q, self.rows, min_score, k, g_offset=self.offset)
+            query_labels = torch.as_tensor(query_labels).reshape(-1).to(q.device)
+            return ops.similarity_range_filtered(q, self.rows, min_score, k, self.labels, query_labels, mode=mode, g_offset=self.offset)
 
     def rescore(self, queries: torch.Tensor, cand: torch.Tensor, k: int | None = None, return_pos: bool = False):
         """The second stage of a two-stage search: queries f32[Bq,C], cand i64[Bq,kin] global row ids (a coarse search's idx, a union
@@ -665,12 +672,15 @@ class GallerySet:
                 return merge_topk_device([r[0] for r in res], [r[1] for r in res], k, [_entry_groups(sh, r[1]) for sh, r in zip(live, res)])[:2]
             return merge_topk_device([r[0] for r in res], [r[1] for r in res], k)
 
-    def range_search(self, queries: torch.Tensor, min_score, k: int):
+    def range_search(self, queries: torch.Tensor, min_score, k: int, query_labels=None, mode: str = "eq"):
         """GalleryShard.range_search over all segments: (scores f32[Bq,k], global idx i64[Bq,k], count i32[Bq]) on the GPU. One call per
         non-empty segment; the lists are merged on the device (merge_topk_device: every list holds only rows at or above the floor, so
         the merged list does) and the counts are added there: the segments' row ranges are disjoint, so the sum is the exact count over
         the set. No segment with rows: all-missing lists and zero counts. An int8 segment raises ValueError: the range search has no
-        int8 form yet (QuantizedShard has no range_search)."""
+        int8 form yet (QuantizedShard has no range_search). query_labels / mode: the filter of GalleryShard.range_search, applied in
+        every segment (allowed rows only, in lists and counts)."""
+        if query_labels is not None and self._segments and self.labels is None:
+            raise ValueError("GallerySet.range_search: query_labels given but the segments have no row labels")
         live = self._live()
         for sh in live:
             if isinstance(sh, QuantizedShard):
@@ -682,7 +692,10 @@ class GallerySet:
             B = queries.reshape(-1, queries.shape[-1]).shape[0]
             dev = self._segments[0].rows.device if self._segments else queries.device
             return (*_missing_lists(B, k, dev), torch.zeros((B,), dtype=torch.int32, device=dev))
-        res = [sh.range_search(queries, min_score, k) for sh in live]
+        if query_labels is None:
+            res = [sh.range_search(queries, min_score, k) for sh in live]
+        else:
+            res = [sh.range_search(queries, min_score, k, query_labels=query_labels, mode=mode) for sh in live]
         if len(live) == 1:
             return res[0]
         with torch.cuda.device(live[0].rows.device):
@@ -927,7 +940,7 @@ class PendingSearch:
     """A search whose lists are still on their way to the host (distributed_search(..., defer=True)): the ONE device-to-host copy
     went to pinned memory behind an event, so the caller can enqueue the next step's forward first and call result() afterwards -
     the GPU never waits for the host merge. result() -> (scores, idx) CPU tensors on `dst` (every rank for dst=None), (None, None)
-    elsewhere; idempotent."""
+    elsewhere ((scores, idx, count) and (None, None, None) for a range search, min_score); idempotent."""
 
     def __init__(self, finish=None, event=None, value=None):
         self._finish, self._event, self._value = finish, event, value
@@ -953,7 +966,7 @@ def _to_host_async(t: torch.Tensor):
 
 def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int, group=None, max_local: int | None = None,
                        dst: int | None = 0, timing: list | None = None, always_collective: bool = False, defer: bool = False,
-                       query_labels=None, filter_mode: str = "eq", distinct: bool = False, merge: str = "host"):
+                       query_labels=None, filter_mode: str = "eq", distinct: bool = False, merge: str = "host", min_score=None):
     """All ranks call this with their own queries [B_local, C] and their gallery shard.
 
     Two collectives in all, as BASELINE.json's north_star describes it:
@@ -991,19 +1004,48 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     per-rank counts instead of `world` lists per slot, and the host only drops the slots beyond each rank's count. Same results,
     bitwise; defer, dst=None, query_labels and distinct work as before; the single-rank shortcut's lists are final either way.
     shard: a GalleryShard, or a GallerySet for a rank that owns several segments (anything with .search, .rows.device, .groups and
-    either .offset or an entry_groups(idx) method)."""
+    either .offset or an entry_groups(idx) method).
+    min_score: None (default) leaves payloads, calls and the return value exactly as described above. A float, or an f32 tensor [B_local]
+    of per-query floors, turns the call into a RANGE search over all shards (shard.range_search, with query_labels / filter_mode when
+    labels are given): the result is (scores, idx, count), count int64 [B_total] = the sum of the shards' exact member counts, on the
+    merging rank(s), (None, None, None) elsewhere; the lists are the first k members over all shards. Still two collectives and one
+    device-to-host copy: the floors travel bit-cast in one more column of the all-gather block (beside the label column when there is
+    one; a padding slot gets +inf, so it has no member and no band row) and each slot's count travels as one more int32 behind its packed
+    list ([slots, 3 k + 1]) in the second collective. dst=None, defer and both merges work as before. distinct=True with min_score, or
+    a shard without range_search (int8 rows: QuantizedShard, or a set with an int8 segment) raise ValueError on every rank before any
+    collective."""
     import torch.distributed as dist
     if merge not in ("host", "device"):
         raise ValueError(f"distributed_search: merge must be 'host' or 'device', got {merge!r}")
     if distinct and getattr(shard, "groups", None) is None:
         raise ValueError("distributed_search: distinct=True but the shard has no group ids")
+    ranged = min_score is not None
+    if ranged:
+        if distinct:
+            raise ValueError("distributed_search: min_score and distinct=True do not go together (the range search has no distinct form)")
+        if not hasattr(shard, "range_search") or any(isinstance(sh, QuantizedShard) for sh in getattr(shard, "segments", ())):
+            raise ValueError("distributed_search: min_score needs a shard with range_search; int8 rows (QuantizedShard) have no range "
+                             "search yet")
+        if not (isinstance(min_score, (int, float)) and not isinstance(min_score, bool)) and not (
+                isinstance(min_score, torch.Tensor) and min_score.dtype == torch.float32):
+            raise ValueError("distributed_search: min_score must be a float or an f32 tensor [B_local]")
 
-    def search(q, labels):                                       # the three call forms the docstring promises
+    def search(q, labels, floors=None):                          # the call forms the docstring promises
+        if ranged:
+            if query_labels is None:
+                return shard.range_search(q, floors, k)
+            return shard.range_search(q, floors, k, query_labels=labels, mode=filter_mode)
         if distinct:
             return shard.search(q, k, query_labels=labels, mode=filter_mode, distinct=True)
         return shard.search(q, k) if query_labels is None else shard.search(q, k, query_labels=labels, mode=filter_mode)
 
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not always_collective):
+        if ranged:
+            s, i, c = search(local_queries, query_labels, min_score)
+            if defer:                                            # one copy: the packed lists with each query's count behind them
+                both, ev = _to_host_async(torch.cat([_pack_lists(s, i).reshape(s.shape[0], -1), c.reshape(-1, 1).to(torch.int32)], dim=1))
+                return PendingSearch(lambda: (*_unpack_lists(both[:, :-1].reshape(s.shape + (3,))), both[:, -1].to(torch.int64)), ev)
+            return s.cpu(), i.cpu(), c.cpu().to(torch.int64)
         s, i = search(local_queries, query_labels)
         if defer:
             both, ev = _to_host_async(_pack_lists(s, i))         # one copy instead of two
@@ -1020,7 +1062,8 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     if host_coll and merge == "device":                          # (the same on every rank: nobody is left waiting in a collective)
         raise ValueError("distributed_search: merge='device' needs a device backend (nccl / RCCL); under gloo the gathered lists are host copies")
     cdev = torch.device("cpu") if host_coll else dev
-    width = C if query_labels is None else C + 1                  # filtered: column C carries each query's label (int32 bits)
+    fcol = C if query_labels is None else C + 1                   # filtered: column C carries each query's label (int32 bits)
+    width = fcol + 1 if ranged else fcol                          # range search: the last column carries each query's floor
     block = torch.zeros((cap + 1, width), dtype=torch.float32, device=cdev)
     block[:b_local, :C] = q.to(cdev)
     if query_labels is not None:
@@ -1028,6 +1071,14 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         if ql.shape[0] != b_local:
             raise ValueError(f"distributed_search: {ql.shape[0]} query labels for {b_local} local queries")
         block[:b_local, C] = ql.to(cdev, torch.int32).view(torch.float32)
+    if ranged:                                                   # padding slots: +inf, no member and no band row (a zero query against a floor
+        block[:, fcol].fill_(float("inf"))                       # of 0 would make every row a band row and take the fallback)
+        if isinstance(min_score, torch.Tensor):
+            if min_score.reshape(-1).shape[0] != b_local:
+                raise ValueError(f"distributed_search: {min_score.reshape(-1).shape[0]} floors for {b_local} local queries")
+            block[:b_local, fcol] = min_score.reshape(-1).to(cdev)
+        else:
+            block[:b_local, fcol].fill_(float(min_score))
     block[cap, :1].fill_(float(b_local))                         # (a fill kernel; `block[cap, 0] = x` copies a host scalar: the host would wait for the stream)
     allb = torch.empty((world * (cap + 1), width), dtype=torch.float32, device=cdev)
     marks = _Marks(dev, host_coll) if timing is not None else None
@@ -1039,8 +1090,12 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     allb = allb.view(world, cap + 1, width)
     slots = allb[:, :cap, :C].reshape(world * cap, C).to(dev)    # every slot is scored; counts stay where they are
     slot_labels = None if query_labels is None else allb[:, :cap, C].contiguous().view(torch.int32).reshape(world * cap).to(dev)
-    s, i = search(slots, slot_labels)                            # local shard vs ALL query slots
-    packed = _pack_lists(s, i)
+    if ranged:                                                   # [slots, 3 k + 1]: each slot's packed list, then its count
+        s, i, c = search(slots, slot_labels, allb[:, :cap, fcol].reshape(world * cap).to(dev))
+        packed = torch.cat([_pack_lists(s, i).reshape(world * cap, 3 * k), c.reshape(-1, 1).to(torch.int32)], dim=1)
+    else:
+        s, i = search(slots, slot_labels)                        # local shard vs ALL query slots
+        packed = _pack_lists(s, i)
     if distinct:                                                 # [slots,k,4]: + the entry's group id
         eg = shard.entry_groups(i) if hasattr(shard, "entry_groups") else _entry_groups(shard, i)    # (a GallerySet looks up its segments)
         packed = torch.cat([packed, eg.unsqueeze(-1)], dim=-1)
@@ -1059,11 +1114,14 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
         if marks:
             marks.mark(); timing.append(marks)
         if rank != dst:
-            return PendingSearch(value=(None, None)) if defer else (None, None)
+            none = (None, None, None) if ranged else (None, None)
+            return PendingSearch(value=none) if defer else none
         parts = torch.stack(glist, dim=0)
     # the ONE device-to-host copy: lists of all shards + the per-rank counts (as int32) in one buffer
     counts_i = allb[:, cap, 0].to(torch.int32)
     if merge == "device":
+        if ranged:
+            return _finish_device_merge(parts[..., :3 * k].reshape(world, world * cap, k, 3), counts_i, k, cap, False, defer, parts[..., 3 * k])
         return _finish_device_merge(parts, counts_i, k, cap, distinct, defer)
     flat = torch.cat([parts.reshape(-1), counts_i.to(parts.device)])
     pshape = tuple(parts.shape)
@@ -1071,6 +1129,9 @@ def distributed_search(local_queries: torch.Tensor, shard: GalleryShard, k: int,
     def finish(host):
         keep = _kept_slots(host, world, cap)
         lists = host[:-world].view(pshape)
+        if ranged:                                               # [world(shard), world*cap(slot), 3 k + 1]
+            ps, pi = _unpack_lists(lists[..., :3 * k].reshape(world, world * cap, k, 3))
+            return (*merge_topk_host(list(ps[:, keep]), list(pi[:, keep]), k), lists[..., 3 * k].to(torch.int64).sum(0)[keep])
         ps, pi = _unpack_lists(lists[..., :3])                   # [world(shard), world*cap(slot), k]
         if distinct:
             return merge_topk_distinct_host(list(ps[:, keep]), list(pi[:, keep]), list(lists[..., 3][:, keep]), k)
@@ -1090,18 +1151,23 @@ def _kept_slots(host, world, cap):
     return torch.cat([torch.arange(r * cap, r * cap + counts[r]) for r in range(world)])
 
 
-def _finish_device_merge(parts, counts_i, k, cap, distinct, defer):
+def _finish_device_merge(parts, counts_i, k, cap, distinct, defer, members=None):
     """distributed_search(merge="device") on a merging rank: parts int32 [world, slots, k, 3|4] (the gathered packed lists, on the GPU) are
-    merged there for every slot; ONE copy takes [slots, k] indices and scores and the per-rank counts (all as int32) to the host."""
-    world, n = parts.shape[0], parts.shape[1] * k
+    merged there for every slot; ONE copy takes [slots, k] indices and scores and the per-rank counts (all as int32) to the host.
+    members (a range search): int32 [world, slots], every shard's member count per slot; their int64 sums over the shards ride in the same
+    copy and the result gains them as a third tensor."""
+    world, slots, n = parts.shape[0], parts.shape[1], parts.shape[1] * k
     ps, pi = _unpack_lists(parts[..., :3])
     with torch.cuda.device(parts.device):
         ms, mi, _ = _merge_stacked(ps, pi, parts[..., 3].contiguous() if distinct else None, k)
-    flat = torch.cat([mi.view(torch.int32).reshape(-1), ms.view(torch.int32).reshape(-1), counts_i.to(parts.device)])   # (the 8-byte indices first: aligned)
+    total = [] if members is None else [members.to(torch.int64).sum(0).view(torch.int32).reshape(-1)]
+    m = 2 * slots if total else 0                                # (the 8-byte indices and sums first: aligned)
+    flat = torch.cat([mi.view(torch.int32).reshape(-1), *total, ms.view(torch.int32).reshape(-1), counts_i.to(parts.device)])
 
     def finish(host):
         keep = _kept_slots(host, world, cap)
-        return host[2 * n:3 * n].view(torch.float32).view(-1, k)[keep], host[:2 * n].view(torch.int64).view(-1, k)[keep]
+        lists = host[2 * n + m:3 * n + m].view(torch.float32).view(-1, k)[keep], host[:2 * n].view(torch.int64).view(-1, k)[keep]
+        return lists if members is None else (*lists, host[2 * n:2 * n + m].view(torch.int64)[keep])
 
     if defer:
         host, ev = _to_host_async(flat)

@@ -368,6 +368,35 @@ long cor_range_workspace_bytes(int Bq, int Ng, int k);
 int cor_similarity_range(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, const float* thresholds, int k, long long g_offset,
                          float* out_scores, long long* out_idx, int* out_count, void* workspace, int flags, void* stream);
 
+/* Filtered threshold search: cor_similarity_range over the rows a query is allowed to see.
+ *   score(b, g)  = the chain score of cor_similarity_topk, as above.
+ *   Allowed(b)   = the rule of cor_similarity_topk_filtered: query_labels[b] < 0 is unrestricted; COR_FILTER_EQ allows the rows whose label
+ *                  equals the query's, COR_FILTER_NE the rows whose label differs (row_labels int32 [Ng], 16-byte aligned; query_labels
+ *                  int32 [Bq]; both on the device).
+ *   In(b)        = { g in Allowed(b) : score(b, g) >= thresholds[b] } by the IEEE comparison (NaN: the empty set; -inf: every allowed row;
+ *                  +0.0 and -0.0 are one floor).
+ *   out_count[b] = |In(b)|, EXACT for every Ng; out_scores / out_idx [Bq,k]: the first k members by (score desc, global index asc), then
+ *                  the (-inf, -1) tail: cor_similarity_topk_filtered's lists with every entry below the floor turned into tail. A query
+ *                  with no allowed row gets count 0 and only the tail.
+ * Scores, indices and counts are bit-identical to that definition for COR_F32 / COR_BF16 / COR_F16 rows, every C the top-k takes and
+ * 1 <= k <= COR_TOPK_KMAX.
+ * Route: the filtered plan of cor_similarity_topk_filtered (interleaved slices, four sample values per group, slices of <= 128 super-tiles,
+ * so tau_q is a bound over ALLOWED rows) with the range call's six extra places per stream, bounds and sure counts. The scans mask a
+ * disallowed score to -inf first and sort the masked scores as cor_similarity_range does; the bounds are floored at -3e38, so a masked
+ * score is never counted, never a band row and never appended. The selection is the range call's; its fallback (candidate overflow, or
+ * more than 16 384 band rows) counts and ranks the allowed rows only, over the chain. The 16-bit scan (C = 256) runs with query groups of
+ * 256 (QB = 1) for every Bq: the 512-query form cannot hold labels and range state in registers together (it spilled), so a batch of more
+ * than 256 queries streams the gallery once per 256 queries.
+ * Argument checks before any HIP call, in cor_similarity_range's order and with its codes; the label checks are those of
+ * cor_similarity_topk_filtered (a null label pointer, a bad filter_mode, row_labels not 16-byte aligned: COR_EINVAL). Flags:
+ * COR_TOPK_NO_FALLBACK keeps its meaning (index -2 in every slot and count -2); every other flag: COR_ENOSUPPORT.
+ * workspace >= cor_range_filtered_workspace_bytes(Bq, Ng, k) (positive for Ng up to 2^31 - 1; >= cor_topk_filtered_workspace_bytes at the
+ * same arguments). No allocation, no host synchronisation; capturable in a graph. */
+long cor_range_filtered_workspace_bytes(int Bq, int Ng, int k);
+int cor_similarity_range_filtered(const float* Q, const void* G, int g_dtype, int Bq, int Ng, int C, const float* thresholds, int k,
+                                  long long g_offset, const int* row_labels, const int* query_labels, int filter_mode, float* out_scores,
+                                  long long* out_idx, int* out_count, void* workspace, int flags, void* stream);
+
 /* Distinct-group top-k: every gallery row g has an int32 group id row_groups[g] (shard-local row g; 16-byte aligned; typically the source
  * image of a region); a negative id makes the row a group of its own. Per query b, among the rows ALLOWED for b, each group's
  * representative is its best row by (chain score desc, global index asc), and the result is the k best representatives ordered the same
