@@ -22,7 +22,8 @@ MERGE_NMAX = 4096    # most entries per query (P * kin) one cor_merge_topk launc
 EXPAND_SEGMAX = 16    # most gallery segments one cor_expand_queries launch reads (COR_EXPAND_SEGMAX)
 RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_reciprocal launch reads (COR_RERANK_SEGMAX)
 DIVERSIFY_SEGMAX = 16    # most gallery segments one cor_diversify_mmr launch reads (COR_DIVERSIFY_SEGMAX)
-FUSE_PMAX = 16    # most lists per query one cor_fuse_lists launch fuses (COR_FUSE_PMAX)
+DIFFUSE_NMAX, DIFFUSE_KDMAX, DIFFUSE_SEGMAX = 256, 32, 16    # cor_rerank_diffusion: candidates per query, graph neighbours per candidate, gallery segments (COR_DIFFUSE_*)
+FUSE_PMAX = 16   # most lists per query one cor_fuse_lists launch fuses (COR_FUSE_PMAX)
 FUSE_RRF, FUSE_SUM, FUSE_MAX = 0, 1, 2    # cor_fuse_lists modes (COR_FUSE_RRF / _SUM / _MAX)
 FUSE_NORM_NONE, FUSE_NORM_MINMAX = 0, 1    # ... score normalisation per list (COR_FUSE_NORM_*)
 FUSE_MISSING_ZERO, FUSE_MISSING_FLOOR = 0, 1    # ... what a list contributes to an id it does not hold (COR_FUSE_MISSING_*)
@@ -103,6 +104,7 @@ SIGNATURES = {
     "cor_knn_reciprocal": [_p, _p, _p, _i, _i, _i, _p, _p],
     "cor_rerank_reciprocal": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p],
     "cor_diversify_mmr": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p],
+    "cor_rerank_diffusion": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p, _p, _p],
     "cor_fuse_lists_workspace_bytes": [_i, _i, _i, _i],
     "cor_fuse_lists": [_p, _p, _i, _i, _i, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p],
 }

@@ -1031,6 +1031,46 @@ def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
+def _row_segments(who, segments, segmax):
+    """The gallery-row segments of diversify_mmr / rerank_diffusion, offsets as ints: each (rows, offset) or (rows_i8, scales, offset), at most segmax."""
+    segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
+    if any(len(seg) not in (2, 3) for seg in segments):
+        raise ValueError(f"{who}: a segment is (rows, offset) or (rows_i8, scales, offset)")
+    if len(segments) > segmax:
+        raise ValueError(f"{who}: {len(segments)} segments, one call reads at most {segmax}")
+    return segments
+
+
+def _row_segments_width(who, segments):
+    """The checks of such segments' tensors (one width C, a multiple of 16 up to 256; dtypes; scales; disjoint id ranges) -> C."""
+    C = segments[0][0].shape[-1] if segments and segments[0][0].dim() == 2 else 16    # (no segment: every entry is missing, any width will do)
+    if C < 16 or C > 256 or C % 16 != 0:
+        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
+    for seg in segments:
+        r = seg[0]
+        if len(seg) == 3:
+            if r.dim() != 2 or r.shape[1] != C or r.dtype != torch.int8 or r.shape[0] >= 2 ** 31:
+                raise ValueError(f"{who}: a segment with scales must be int8 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+            if seg[1].dtype != torch.float32 or seg[1].dim() != 1 or seg[1].shape[0] != r.shape[0]:
+                raise ValueError(f"{who}: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
+        elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
+            raise ValueError(f"{who}: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+    _disjoint_spans(who, segments)
+    return C
+
+
+def _row_table(segments):
+    """Checked segments on the device -> ((seg_rows, seg_scale, seg_offset, seg_n, seg_dtype) as ctypes arrays, nseg, the tensors they point to)."""
+    rows = [seg[0].contiguous() for seg in segments]
+    rows = [r.clone() if r.data_ptr() % 16 else r for r in rows]   # a view into a larger tensor: the kernel loads 16 B at a time
+    scales = [seg[1].contiguous() if len(seg) == 3 else None for seg in segments]
+    n = len(segments)
+    seg_rows, seg_off, seg_n = _seg_arrays([seg[-1] for seg in segments], rows)
+    seg_sc = (nat.C.c_void_p * max(n, 1))(*[_p(t) or None for t in scales])
+    seg_dt = (nat.C.c_int * max(n, 1))(*[nat.I8 if len(seg) == 3 else _dt(r) for seg, r in zip(segments, rows)])
+    return (seg_rows, seg_sc, seg_off, seg_n, seg_dt), n, (rows, scales)
+
+
 def diversify_mmr(segments, scores, idx, k, lam=0.5, max_sim=None, return_pos=False, return_value=False):
     """Diversified lists on the device (cor_diversify_mmr): greedy maximal marginal relevance with optional near-duplicate suppression.
     segments as expand_queries takes them: a list of (rows, offset), rows [n,C] fp32 / bf16 / fp16 holding the global ids
@@ -1047,11 +1087,7 @@ def diversify_mmr(segments, scores, idx, k, lam=0.5, max_sim=None, return_pos=Fa
     1 <= k <= 256, kin <= nat.MERGE_NMAX (4096; beyond that NativeError), C <= 256 and C % 16 == 0. No host synchronisation; capturable
     in a graph."""
     who = "diversify_mmr"
-    segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
-    if any(len(seg) not in (2, 3) for seg in segments):
-        raise ValueError(f"{who}: a segment is (rows, offset) or (rows_i8, scales, offset)")
-    if len(segments) > nat.DIVERSIFY_SEGMAX:
-        raise ValueError(f"{who}: {len(segments)} segments, one call reads at most {nat.DIVERSIFY_SEGMAX}")
+    segments = _row_segments(who, segments, nat.DIVERSIFY_SEGMAX)
     Bq, kin = _list_front(who, scores, idx)
     if not 1 <= int(k) <= nat.TOPK_KMAX:
         raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
@@ -1061,35 +1097,55 @@ def diversify_mmr(segments, scores, idx, k, lam=0.5, max_sim=None, return_pos=Fa
     max_sim = float("inf") if max_sim is None else float(max_sim)
     if max_sim != max_sim:
         raise ValueError(f"{who}: max_sim must not be NaN")
-    C = segments[0][0].shape[-1] if segments and segments[0][0].dim() == 2 else 16    # (no segment: every entry is missing, any width will do)
-    if C < 16 or C > 256 or C % 16 != 0:
-        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
-    for seg in segments:
-        r = seg[0]
-        if len(seg) == 3:
-            if r.dim() != 2 or r.shape[1] != C or r.dtype != torch.int8 or r.shape[0] >= 2 ** 31:
-                raise ValueError(f"{who}: a segment with scales must be int8 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
-            if seg[1].dtype != torch.float32 or seg[1].dim() != 1 or seg[1].shape[0] != r.shape[0]:
-                raise ValueError(f"{who}: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
-        elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
-            raise ValueError(f"{who}: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
-    _disjoint_spans(who, segments)
+    C = _row_segments_width(who, segments)
     dev = _dev(scores, idx, *[t for seg in segments for t in seg[:-1]])
     scores, idx = scores.contiguous(), idx.contiguous()
-    rows = [seg[0].contiguous() for seg in segments]
-    rows = [r.clone() if r.data_ptr() % 16 else r for r in rows]   # a view into a larger tensor: the kernel loads 16 B at a time
-    scales = [seg[1].contiguous() if len(seg) == 3 else None for seg in segments]
-    n = len(segments)
-    seg_rows, seg_off, seg_n = _seg_arrays([seg[-1] for seg in segments], rows)
-    seg_sc = (nat.C.c_void_p * max(n, 1))(*[_p(t) or None for t in scales])
-    seg_dt = (nat.C.c_int * max(n, 1))(*[nat.I8 if len(seg) == 3 else _dt(r) for seg, r in zip(segments, rows)])
+    table, n, _keep = _row_table(segments)
     out_s, out_i, out_p = _list_outputs(Bq, int(k), dev, return_pos)
     out_v = torch.empty((Bq, int(k)), dtype=torch.float32, device=dev) if return_value else None
     if Bq:                                                    # (no queries: empty tensors have no address to pass)
-        nat.check(_lib().cor_diversify_mmr(seg_rows, seg_sc, seg_off, seg_n, seg_dt, n, scores.data_ptr(), idx.data_ptr(), Bq, kin, C, lam, max_sim,
+        nat.check(_lib().cor_diversify_mmr(*table, n, scores.data_ptr(), idx.data_ptr(), Bq, kin, C, lam, max_sim,
                                            int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None, _p(out_v) or None, _s()),
                   "cor_diversify_mmr")
     return (out_s, out_i) + ((out_p,) if return_pos else ()) + ((out_v,) if return_value else ())
+
+
+def rerank_diffusion(segments, scores, idx, k, kd=8, kq=None, gamma=3, alpha=0.9, iters=20, return_pos=False):
+    """Diffusion re-ranking of lists on the device (cor_rerank_diffusion): manifold ranking on the mutual kd-nearest-neighbour graph of
+    each query's candidates. segments as diversify_mmr takes them: a list of (rows, offset), rows [n,C] fp32 / bf16 / fp16 holding the
+    global ids [offset, offset + n), or of (rows_i8, scales, offset); at most nat.DIFFUSE_SEGMAX (16), pairwise disjoint, dtypes free to
+    differ. scores f32 [Bq,kin] and idx i64 [Bq,kin] as a search, the merge or the re-scoring return them, kin <= nat.DIFFUSE_NMAX (256;
+    beyond that NativeError) -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]). Per query: the affinity of two present entries is
+    their chain similarity (that of diversify_mmr), clipped at 0, to the power gamma; every entry keeps its kd best neighbours and an
+    edge stays if both ends keep each other; the edges are scaled by 1 / sqrt(degree) of both ends; y holds score ** gamma for the kq
+    first present entries (kq None: all) and 0 for the rest; f starts as y and `iters` times becomes alpha * S f + (1 - alpha) * y; the
+    present entries go out ranked by (f desc, id asc, position asc) with f as their score. include/cor_amd.h has the definition to the
+    bit. An id of no segment (-1, another shard's, any 64-bit value) is dropped and its score is not read; a repeated id is an entry of
+    its own. Fewer than k present: the (-inf, -1, -1) tail. alpha = 0 returns y. 1 <= k <= 256, 1 <= kd <= nat.DIFFUSE_KDMAX (32),
+    kq >= 1, 1 <= gamma <= 4, 0 <= alpha < 1, 1 <= iters <= 64, C <= 256 and C % 16 == 0. No host synchronisation; capturable in a graph."""
+    who = "rerank_diffusion"
+    segments = _row_segments(who, segments, nat.DIFFUSE_SEGMAX)
+    Bq, kin = _list_front(who, scores, idx)
+    if not 1 <= int(k) <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    kq = nat.DIFFUSE_NMAX if kq is None else kq
+    if not 1 <= int(kd) <= nat.DIFFUSE_KDMAX or int(kq) < 1:
+        raise ValueError(f"{who}: kd must be in [1, {nat.DIFFUSE_KDMAX}] and kq at least 1, got kd={kd}, kq={kq}")
+    if not 1 <= int(gamma) <= 4 or not 1 <= int(iters) <= 64:
+        raise ValueError(f"{who}: gamma must be in [1, 4] and iters in [1, 64], got gamma={gamma}, iters={iters}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha < 1.0:
+        raise ValueError(f"{who}: alpha must be in [0, 1), got {alpha}")
+    C = _row_segments_width(who, segments)
+    dev = _dev(scores, idx, *[t for seg in segments for t in seg[:-1]])
+    scores, idx = scores.contiguous(), idx.contiguous()
+    table, n, _keep = _row_table(segments)
+    out_s, out_i, out_p = _list_outputs(Bq, int(k), dev, return_pos)
+    if Bq:                                                    # (no queries: empty tensors have no address to pass)
+        nat.check(_lib().cor_rerank_diffusion(*table, n, scores.data_ptr(), idx.data_ptr(), Bq, kin, C, int(kd), min(int(kq), 2 ** 31 - 1),
+                                              int(gamma), alpha, int(iters), int(k), out_s.data_ptr(), out_i.data_ptr(), _p(out_p) or None,
+                                              _s()), "cor_rerank_diffusion")
+    return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
 _FUSE_MODES = {"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "max": nat.FUSE_MAX}

@@ -286,6 +286,14 @@ def _diversify(who, table, dev, scores, idx, k, lam, max_sim, return_pos):
         return ops.diversify_mmr(table, scores, idx, k, lam=lam, max_sim=max_sim, return_pos=return_pos)
 
 
+def _diffuse(who, table, dev, scores, idx, k, kd, kq, gamma, alpha, iters, return_pos):
+    if idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be [Bq, kin], got {tuple(idx.shape)}")
+    k = min(idx.shape[1], ops.nat.TOPK_KMAX) if k is None else k
+    with _on(dev):
+        return ops.rerank_diffusion(table, scores, idx, k, kd=kd, kq=kq, gamma=gamma, alpha=alpha, iters=iters, return_pos=return_pos)
+
+
 def _search(shard, who, fns, row_args, queries, k, query_labels, mode, distinct):
     """The search of GalleryShard and QuantizedShard: fns = the (plain, filtered, distinct) ops, row_args = (rows,) or (rows, scales).
     Both argument checks come before anything touches the device."""
@@ -424,6 +432,16 @@ class GalleryShard:
         defaults to min(kin, 256). Entries this shard does not hold are dropped; fewer than k chosen: the (-inf, -1[, -1]) tail."""
         return _diversify("GalleryShard.diversify", [(self.rows, self.offset)], self.rows.device, scores, idx, k, lam, max_sim, return_pos)
 
+    def diffuse(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, kd: int = 8, kq: int | None = None, gamma: int = 3,
+                alpha: float = 0.9, iters: int = 20, return_pos: bool = False):
+        """Diffusion re-ranking of lists over this shard's rows (ops.rerank_diffusion): scores / idx [Bq,kin <= 256] as search, rescore,
+        two_stage_search or rerank return them -> (scores f32[Bq,k], idx i64[Bq,k][, pos i32[Bq,k]]) on the GPU: manifold ranking on the
+        mutual kd-nearest-neighbour graph of each query's candidates (affinity: chain similarity clipped at 0, to the power gamma), the
+        kq first entries (None: all) injecting score ** gamma, `iters` steps f <- alpha S f + (1 - alpha) y; the entries come back ranked
+        by f, with f as their score. A row far from the query but linked to it through a chain of mutually close rows rises. k defaults
+        to min(kin, 256). Entries this shard does not hold are dropped; fewer than k present: the (-inf, -1[, -1]) tail."""
+        return _diffuse("GalleryShard.diffuse", [(self.rows, self.offset)], self.rows.device, scores, idx, k, kd, kq, gamma, alpha, iters, return_pos)
+
     def quantized(self):
         """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
         coarse stage of two_stage_search over these rows. This shard is left untouched. The labels and the group ids are carried (the same
@@ -434,7 +452,7 @@ class GalleryShard:
 class QuantizedShard:
     """Rows [offset, offset + n) of a gallery as int8 with one fp32 scale per row (ops.quantize_rows_i8), scanned on the i8 matrix cores
     (ops.similarity_topk_i8): half the bytes of a 16-bit copy and scores that are defined to the bit. This class only SEARCHES: it is the
-    coarse copy that stands beside real rows, and it has no rescore, expand, rerank or diversify. Its subclass QuantizedGallery (below; gallery()
+    coarse copy that stands beside real rows, and it has no rescore, expand, rerank, diversify or diffuse. Its subclass QuantizedGallery (below; gallery()
     turns one into the other without copying) is the int8-ONLY gallery, which takes every list stage over the quantised rows alone. Use a
     QuantizedShard wherever a coarse search is taken: `coarse` of two_stage_search, a segment of a GallerySet (where the set itself
     carries the list stages for it), `neighbours` of GalleryShard.augmented / neighbour_graph (search only; GalleryShard.augmented then
@@ -497,7 +515,7 @@ class QuantizedShard:
 class QuantizedGallery(QuantizedShard):
     """An int8-ONLY gallery: a QuantizedShard (the same constructor, from_rows and searches) that is a gallery in its own right. Beside
     the searches it takes every list stage a GalleryShard takes, over the quantised rows alone: rescore (ops.rescore_topk_i8, the int8
-    score), expand (ops.expand_queries over rows whose value is float(q) * scale), neighbour_graph, rerank, diversify and augmented; no float copy of
+    score), expand (ops.expand_queries over rows whose value is float(q) * scale), neighbour_graph, rerank, diversify, diffuse and augmented; no float copy of
     the rows has to be resident. dequantized() gives the float rows it stands for. Use it as `coarse`, `fine` or both of two_stage_search,
     as the gallery of expanded_search / reranked_search, as a segment of a GallerySet beside float segments, as `neighbours` of
     GalleryShard.augmented (which then sums over THIS gallery's rows) / neighbour_graph."""
@@ -540,6 +558,14 @@ class QuantizedGallery(QuantizedShard):
         dequantized()'s fp32 rows."""
         return _diversify("QuantizedGallery.diversify", [(self.rows, self.scales, self.offset)], self.rows.device, scores, idx, k, lam, max_sim,
                           return_pos)
+
+    def diffuse(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, kd: int = 8, kq: int | None = None, gamma: int = 3,
+                alpha: float = 0.9, iters: int = 20, return_pos: bool = False):
+        """GalleryShard.diffuse over the int8 rows (ops.rerank_diffusion with an int8 segment): a row's value is float(q) * scale and the
+        similarity is the fp32 chain over those values (not the int8 search score), so the result equals bitwise the diffusion over
+        dequantized()'s fp32 rows."""
+        return _diffuse("QuantizedGallery.diffuse", [(self.rows, self.scales, self.offset)], self.rows.device, scores, idx, k, kd, kq, gamma, alpha,
+                        iters, return_pos)
 
     def dequantized(self, dtype: torch.dtype = torch.float32):
         """A GalleryShard (same offset, labels and groups) of the rows this shard stands for, float(q) * scale in fp32, rounded again to
@@ -742,6 +768,16 @@ class GallerySet:
         table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
         return _diversify("GallerySet.diversify", table, live[0].rows.device if live else scores.device, scores, idx, k, lam, max_sim, return_pos)
 
+    def diffuse(self, scores: torch.Tensor, idx: torch.Tensor, k: int | None = None, kd: int = 8, kq: int | None = None, gamma: int = 3,
+                alpha: float = 0.9, iters: int = 20, return_pos: bool = False):
+        """GalleryShard.diffuse over all segments in ONE launch: the kernel looks every listed id up in the table of the live segments
+        (at most 16; their dtypes may differ, int8 segments, a plain QuantizedShard included, with their row scales). The result equals
+        bitwise that of a single fp32 GalleryShard over the concatenated widened / dequantised rows."""
+        live = self._live()
+        table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
+        return _diffuse("GallerySet.diffuse", table, live[0].rows.device if live else scores.device, scores, idx, k, kd, kq, gamma, alpha, iters,
+                        return_pos)
+
     def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
         """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new
         GallerySet of new segments; this set and its segments are left untouched. An int8 segment becomes a new int8 segment
@@ -839,6 +875,26 @@ def diversified_search(queries: torch.Tensor, gallery, k: int, k_coarse: int, la
         raise ValueError(f"diversified_search: lam must be in [0, 1] and max_sim not NaN, got lam={lam}, max_sim={max_sim}")
     s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
     return gallery.diversify(s, i, k=int(k), lam=lam, max_sim=max_sim)
+
+
+def diffused_search(queries: torch.Tensor, gallery, k: int, k_coarse: int, kd: int = 8, kq: int | None = None, gamma: int = 3, alpha: float = 0.9,
+                    iters: int = 20, **search_kwargs):
+    """Search with diffusion re-ranking on one device: gallery.search(queries, k_coarse, **search_kwargs) followed by
+    gallery.diffuse(scores, idx, k=k, kd=kd, kq=kq, gamma=gamma, alpha=alpha, iters=iters) -> (scores f32[Bq,k], idx i64[Bq,k]) on the GPU:
+    the k_coarse best re-ranked by manifold ranking on their mutual kd-nearest-neighbour graph, the scores being the diffused values.
+    gallery: a GalleryShard, a QuantizedGallery (an int8-only gallery) or a GallerySet of either. 1 <= k <= k_coarse <= 256,
+    1 <= kd <= 32, kq >= 1 or None, 1 <= gamma <= 4, 0 <= alpha < 1, 1 <= iters <= 64, else ValueError before anything runs.
+    search_kwargs (query_labels, mode, distinct) go to the search. Nothing leaves the device and the host is not waited for.
+    distributed_search has no such option: a candidate's row lives on the rank that owns it."""
+    if not 1 <= int(k) <= int(k_coarse) <= ops.nat.DIFFUSE_NMAX:
+        raise ValueError(f"diffused_search: need 1 <= k <= k_coarse <= {ops.nat.DIFFUSE_NMAX}, got k={k}, k_coarse={k_coarse}")
+    if not 1 <= int(kd) <= ops.nat.DIFFUSE_KDMAX or (kq is not None and int(kq) < 1) or not 1 <= int(gamma) <= 4 or not 1 <= int(iters) <= 64:
+        raise ValueError(f"diffused_search: need 1 <= kd <= {ops.nat.DIFFUSE_KDMAX}, kq >= 1, 1 <= gamma <= 4, 1 <= iters <= 64, "
+                         f"got kd={kd}, kq={kq}, gamma={gamma}, iters={iters}")
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError(f"diffused_search: alpha must be in [0, 1), got {alpha}")
+    s, i = gallery.search(queries, int(k_coarse), **search_kwargs)
+    return gallery.diffuse(s, i, k=int(k), kd=kd, kq=kq, gamma=gamma, alpha=alpha, iters=iters)
 
 
 def fused_search(queries, gallery, k: int, k_each: int, weights=None, mode: str = "rrf", rrf_c: float = 60.0, normalize: str = "none",

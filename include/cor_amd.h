@@ -772,6 +772,61 @@ int cor_diversify_mmr(const void* const* seg_rows, const float* const* seg_scale
                       const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam,
                       float max_sim, int k, float* out_scores, long long* out_idx, int* out_pos, float* out_value, void* stream);
 
+/* Diffusion re-ranking: manifold ranking (Zhou et al., NIPS 2003; Iscen et al., CVPR 2017, "Efficient diffusion on region manifolds") on the
+ * mutual k-nearest-neighbour graph of a query's candidates. The scores of the query's best entries are spread along chains of mutually
+ * close rows, so a row that is far from the query but linked to it through such a chain (another view or crop of the same object) rises.
+ *
+ * cor_rerank_diffusion. The segment table is exactly that of cor_diversify_mmr: seg_rows / seg_scale / seg_offset / seg_n / seg_dtype are
+ * HOST arrays of nseg entries (COR_F32 / COR_BF16 / COR_F16 / COR_I8 segments, mixed freely, a COR_I8 segment with its DEVICE row scales;
+ * seg_scale may be NULL when no segment is COR_I8), at most COR_DIFFUSE_SEGMAX segments with pairwise disjoint id ranges, copied into a
+ * by-value kernel argument together with the scalars: no device allocation, no workspace, no host-to-device copy, no host
+ * synchronisation; everything runs on `stream` and the call can be captured in a graph. scores f32 [Bq,kin] and idx i64 [Bq,kin],
+ * contiguous: lists as the searches, the merge or the re-scoring return them. out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_pos NULL or
+ * i32 [Bq,k]. Rows 16-byte aligned as for the searches.
+ * Definition, per query b, fixed to the bit: every * + - / and sqrtf below is ONE IEEE fp32 operation, correctly rounded, never
+ * contracted; fmaf is one fused operation.
+ *   Presence. Entry j < kin is PRESENT if idx[b,j] lies in some segment's [seg_offset[s], seg_offset[s] + seg_n[s]); the range test runs
+ *   before any address is formed, so ids may be arbitrary 64-bit values. Every other entry is MISSING: it is dropped and its score is
+ *   never read. Ids may repeat; a repeat is an entry of its own. n is the number of present entries, numbered p = 0 .. n-1 in list order.
+ *   Row value and similarity. x(r) and sim(r, r') are exactly those of cor_diversify_mmr: values widened exactly, an int8 value
+ *   (float)q * scale as one rounded multiply, sim the fmaf chain of oracle/c/sim_chain.c, bitwise symmetric. The result depends neither
+ *   on the storage dtype of equal values nor on how the rows are cut into segments.
+ *   Power. pw(v) = +0 if !(v > 0); otherwise w = v, then w = w * v repeated gamma - 1 times. No powf.
+ *   Affinity. a(p, p') = pw(sim(row_p, row_p')) for p != p' (by position, not by id: two entries with one id are neighbours); a(p, p) = 0.
+ *   Neighbours. N(p): the at most kd entries p' with the greatest a(p, p') > 0, ordered by (a desc, p' asc). M(p): the members p' of
+ *   N(p) with p in N(p'), the order kept: the mutual k-nearest-neighbour graph, symmetric because sim is.
+ *   Degree. d_p = +0, then d_p = d_p + a(p, p') over M(p) in that order. Scale. r_p = d_p > 0 ? 1.0f / sqrtf(d_p) : +0.
+ *   Edge weight. S(p, p') = a(p, p') * (r_p * r_p'), the inner product first.
+ *   Query vector. y_p = p < kq ? pw(scores[b, position of p]) : +0: only the query's kq best present entries inject mass; kq >= n: all.
+ *   Iteration. f(0) = y. For t = 0 .. iters-1 and every p: g = +0, then g = fmaf(S(p, p'), f(t)_p', g) over M(p) in its order;
+ *   f(t+1)_p = (alpha * g) + ((1.0f - alpha) * y_p). All of f(t+1) is computed from f(t) (Jacobi).
+ *   Ranking. The present entries are ranked by (f(iters) desc, id asc, position asc) with cor_merge_topk's rules: -0.0 ties with +0.0,
+ *   ids compare as 64-bit values. The first k go out: out_scores = f's bits, out_idx = the id, out_pos = the list position j. Slots
+ *   past n hold (-inf, -1, -1).
+ *   Preconditions: present entries have finite scores and rows. (Otherwise the result is unspecified, but every access stays in bounds.)
+ * Consequences. alpha = 0 returns y exactly: with gamma = 1 and kq >= n a searched list with positive scores comes back unchanged.
+ * kd >= n - 1 makes M(p) every p' with a(p, p') > 0. A row with no positive similarity to any other row keeps f = (1 - alpha) * y
+ * after the first step (as (alpha * 0) + that). n = 1 returns the entry with f = (alpha * 0) + ((1 - alpha) * y). f is never negative
+ * and never -0.0.
+ * One launch, one block per query, max(64, kin rounded up to a power of two) threads, one per candidate; all n * n chains are computed,
+ * 32 partner rows at a time: the block widens the partners into an LDS tile, every thread walks its own row 8 channels at a time against
+ * 32 accumulators and keeps its kd best affinities as a sorted list, in registers for kd <= 8, as a column in LDS for a larger kd (which is
+ * several times slower: DESIGN.md). The mutual test needs only each list's last pair. The
+ * iteration runs over two f vectors in LDS, a barrier per step; the ranking is cor_merge_topk's (bitonic sort in LDS of 8-byte keys
+ * [f key | position], the id read through the position on ties). No Gram matrix, no global workspace, no scratch.
+ * COR_EINVAL: a null scores / idx / out_scores / out_idx, a null segment array (seg_rows, seg_offset, seg_n, seg_dtype) with nseg > 0,
+ * Bq < 0, kin / k / kd / kq / gamma / iters < 1, nseg < 0, C < 1, a negative seg_n, a null seg_rows[s] with seg_n[s] > 0, a null scale
+ * (entry or array) for a non-empty COR_I8 segment, alpha NaN or outside [0, 1). COR_ENOSUPPORT: kin > COR_DIFFUSE_NMAX,
+ * kd > COR_DIFFUSE_KDMAX, gamma > 4, iters > 64, k > COR_TOPK_KMAX, nseg > COR_DIFFUSE_SEGMAX, C > 256 or C % 16 != 0, an unknown
+ * seg_dtype. All of these are decided before any HIP call. Bq == 0 is a successful no-op; nseg == 0 is legal (every entry is missing). */
+#define COR_DIFFUSE_NMAX 256     /* candidates per query */
+#define COR_DIFFUSE_KDMAX 32     /* graph neighbours per candidate */
+#define COR_DIFFUSE_SEGMAX 16
+int cor_rerank_diffusion(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                         const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C,
+                         int kd, int kq, int gamma, float alpha, int iters, int k,
+                         float* out_scores, long long* out_idx, int* out_pos, void* stream);
+
 /* Fusion of ranked lists: reciprocal-rank fusion (RRF; Cormack, Clarke & Buettcher, SIGIR 2009), CombSUM and CombMAX (Fox & Shaw, TREC-2
  * 1994). Per query, P rankings of the SAME request over the SAME global id space (several shots or views of one request, or several
  * galleries over one id space) become one ranking with one entry per distinct id. cor_merge_topk is not this: it ranks entries, not rows,
