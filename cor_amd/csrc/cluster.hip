@@ -1,0 +1,680 @@
+// cor_amd — clustering of a gallery: farthest-point seeding (cor_kmeans_seed) and the centre step of spherical k-means (cor_kmeans_update).
+// Contract and both definitions, fixed to the bit: include/cor_amd.h. The assignment step is the existing search and is not in this file.
+//
+// Rows. Both calls take the by-value segment table of cor_diversify_mmr. A FLAT position p in [0, n_total) numbers the rows of the table's
+// non-empty segments in the order the launcher hands them to the kernels: table order for the seeding (its tie rule reads the global id),
+// ASCENDING SEGMENT OFFSET for the update, so that there ascending p is ascending global id. km_locate turns p into (segment, local row)
+// with a uniform walk over the table; the range test comes first and only a hit forms an address. n_total < 2^31.
+//
+// cor_kmeans_seed: 2K launches (init, then K steps and K - 1 picks), the chosen row stays on the device (KmCur in the workspace).
+//   init    best[p] = -inf, NaN at the first row (NaN marks CHOSEN: `s > NaN` and `NaN < x` are false, so a chosen row is never
+//           updated and never picked); cur = the first row.
+//   step t  every block widens row c_t into 1 KiB of LDS (block 0 also writes out_ids[t] and out_centroids[t]); a thread owns rows
+//           p, p + grid, ...: the fmaf chain of oracle/c/sim_chain.c against the LDS row, 16 channels of loads in flight, best[p] raised,
+//           and the thread's smallest (best, id) kept; wave butterfly, the block's four waves through LDS, one partial per block.
+//   pick t  one block reduces the <= KM_SEED_BLOCKS partials, marks the winner chosen and writes cur for step t + 1.
+//   The comparison (best by IEEE <, then the smaller global id) is a total order on the rows, so neither the grid nor the segmentation
+//   changes the winner. The last step has no scoring and no pick.
+// cor_kmeans_update: 6 launches.
+//   keys    one block per tile of KM_TILE = 2048 flat positions: a 32-bit key [cluster: 14 bits | position in the tile: 11 bits] per row with
+//           an assign value in [0, K) (every other row: 0xffffffff, behind all keys), bitonic sort in LDS (ranklist.h), the sorted keys go
+//           to the workspace; the head of every run of one cluster finds the run's end by binary search and writes the tile's count for
+//           that cluster into the tiles x K table (the block zeroed its row of the table before). No atomics.
+//   columns one thread per cluster walks its column of the table: exclusive prefix over the tiles in place, the total is out_count.
+//   scan    one block: exclusive scans over the K counts (member-list base) and over the K chunk counts ceil(count / 256) (chunk base).
+//   place   one block per tile: member slot = base[cluster] + the tile's prefix + the key's rank inside its run (binary search for the run's
+//           head). The lists come out ascending by flat position inside every cluster: a stable counting sort.
+//   chunks  one WAVE per (cluster, chunk of 256 members), found by binary search in the chunk bases; expand.hip's layout: lane l owns
+//           channels [4l, 4l + 4), a member row is ONE coalesced wave load, 64 members are looked up at a time (lane j: member j) and
+//           walked in member order 8 rows at a time, all 8 loads issued before the first add. p_j = +0, then p_j = p_j + x. The members'
+//           scores are summed the same way from the lane that looked the member up. Partial rows go to the workspace.
+//   finish  one wave per cluster: v = +0, v = v + p_j for j ascending, the norm tree of cor_expand_queries, v / d; an empty cluster
+//           copies its row of prev (or writes +0).
+// Arithmetic: `#pragma clang fp contract(off)` holds for the whole file: every + * / is one separately rounded fp32 operation, the
+// chain's explicit fmaf stays an fma; a / b and __builtin_sqrtf are correctly rounded (no fast-math flag for this file in the Makefile).
+#include "ranklist.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int KM_SEGMAX = COR_CLUSTER_SEGMAX;
+constexpr int KM_CMAX = 256;                   // 64 lanes x 4 channels
+constexpr int KM_TILE_BITS = 11, KM_TILE = 1 << KM_TILE_BITS;   // rows per tile of the member-list build
+constexpr int KM_CHUNK = 256;                  // members per chunk sum (part of the definition)
+constexpr int KM_SEED_BLOCKS = 4096;           // most blocks (and partials) of a seeding step
+constexpr int KM_WPB = 4;                      // waves per block of the chunk and finish kernels
+constexpr unsigned KM_NOKEY = 0xffffffffu;
+constexpr unsigned KM_CHOSEN = 0x7fc00000u;    // best[] of a chosen row: a NaN
+static_assert(COR_KMEANS_KMAX <= (1 << 14) && COR_KMEANS_KMAX * (1ll << KM_TILE_BITS) < (1ll << 32) - 1, "a key is [cluster | position in the tile] in 32 bits");
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+#define KM_GLOBAL __attribute__((address_space(1)))
+
+// the segment table, passed BY VALUE in the kernel argument block (768 B): no device allocation, no copy, nothing to keep alive
+struct KmSegs {
+  const unsigned char* rows[KM_SEGMAX];
+  long long off[KM_SEGMAX];
+  int n[KM_SEGMAX];
+  int dt[KM_SEGMAX];
+  const float* scale[KM_SEGMAX];
+  const int* assign[KM_SEGMAX];                // cor_kmeans_update only
+  const float* score[KM_SEGMAX];               // ... and NULL without scores
+};
+
+__device__ __forceinline__ int km_esize(int dt) { return dt == COR_F32 ? 4 : dt == COR_I8 ? 1 : 2; }
+
+// flat position -> on_hit(segment, local row) and true, or false: p lies past the table. Every segment is visited (uniform trip count, the
+// table in scalar registers); the callers form their addresses inside on_hit, from a hit alone
+template <typename OnHit> __device__ __forceinline__ bool km_locate(const KmSegs& segs, int nseg, long long p, const OnHit on_hit) {
+  bool hit = false;
+  long long base = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const long long n = segs.n[s];
+    if (!hit && p >= base && p - base < n) {
+      hit = true;
+      on_hit(s, (int)(p - base));
+    }
+    base += n;
+  }
+  return hit;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- seeding
+
+struct KmCur {                                 // the chosen row of the current step, in the workspace
+  u64 row;
+  long long id;
+  float rs;
+  int dt;
+};
+struct KmPart {                                // a block's smallest (best, id); flat < 0: the block saw no row that is not chosen
+  long long id;
+  float v;
+  int flat;
+};
+
+// does (av, aid) come before (bv, bid)? A flat position < 0 is no entry
+__device__ __forceinline__ bool km_before(float av, long long aid, int af, float bv, long long bid, int bf) {
+  if (af < 0) return false;
+  if (bf < 0) return true;
+  if (av < bv) return true;
+  if (bv < av) return false;
+  return aid < bid;
+}
+
+// elements [8 c, 8 c + 8) of a row, as fp32 values (the dtype may differ between the threads of a wave); rows are 16-byte aligned
+__device__ __forceinline__ void km_load8(u64 row, int dt, float rs, int c, float (&g)[8]) {
+  if (dt == COR_F32) {
+    const u32x4 x = *(const KM_GLOBAL u32x4*)(row + 32u * c), y = *(const KM_GLOBAL u32x4*)(row + 32u * c + 16u);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { g[e] = __uint_as_float(x[e]); g[4 + e] = __uint_as_float(y[e]); }
+  } else if (dt == COR_I8) {
+    const u32x2 x = *(const KM_GLOBAL u32x2*)(row + 8u * c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = (float)(int)(signed char)(x[e >> 2] >> (8 * (e & 3))) * rs;
+  } else {
+    const u32x4 x = *(const KM_GLOBAL u32x4*)(row + 16u * c);
+    if (dt == COR_BF16) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { g[2 * e] = __uint_as_float(x[e] << 16); g[2 * e + 1] = __uint_as_float(x[e] & 0xffff0000u); }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(e & 1 ? x[e >> 1] >> 16 : x[e >> 1] & 0xffffu));
+    }
+  }
+}
+
+__device__ __forceinline__ void km_set_cur(const KmSegs& segs, int nseg, int C, long long p, KmCur* cur) {
+  km_locate(segs, nseg, p, [&](int s, int local) {
+    const int dt = segs.dt[s];
+    KmCur c;
+    c.row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
+    c.id = segs.off[s] + local;
+    c.rs = dt == COR_I8 ? segs.scale[s][local] : 0.f;
+    c.dt = dt;
+    *cur = c;
+  });
+}
+
+__global__ __launch_bounds__(256) void km_seed_init(const KmSegs segs, int nseg, long long n, int C, long long first, unsigned* __restrict__ best,
+                                                    KmCur* __restrict__ cur) {
+  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256)
+    best[p] = p == first ? KM_CHOSEN : RANK_NEG_INF;
+  if (blockIdx.x == 0 && threadIdx.x == 0) km_set_cur(segs, nseg, C, first, cur);
+}
+
+__global__ __launch_bounds__(256) void km_seed_step(const KmSegs segs, int nseg, long long n, int C, float* __restrict__ best,
+                                                    const KmCur* __restrict__ cur, KmPart* __restrict__ part, int t, int score,
+                                                    long long* __restrict__ out_ids, float* __restrict__ out_centroids) {
+  __shared__ __align__(16) float s_q[KM_CMAX];
+  __shared__ KmPart s_part[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const KmCur c = *cur;
+  if (tid < C / 8) {
+    float g[8];
+    km_load8(c.row, c.dt, c.rs, tid, g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s_q[8 * tid + e] = g[e];
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) out_centroids[(long long)t * C + 8 * tid + e] = g[e];
+    }
+  }
+  if (blockIdx.x == 0 && tid == 0) out_ids[t] = c.id;
+  if (!score) return;                                                    // (uniform) the last step: nothing is picked after it
+  __syncthreads();
+
+  float bv = 0.f;
+  long long bid = 0;
+  int bf = -1;
+  for (long long p = (long long)blockIdx.x * 256 + tid; p < n; p += (long long)gridDim.x * 256) {
+    u64 row = 0;
+    float rs = 0.f;
+    int dt = COR_F32;
+    long long id = 0;
+    const bool hit = km_locate(segs, nseg, p, [&](int s, int local) {    // the only place a row address is formed
+      dt = segs.dt[s];
+      row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
+      id = segs.off[s] + local;
+      if (dt == COR_I8) rs = segs.scale[s][local];
+    });
+    if (!hit) continue;                                                  // (p < n: never)
+    float a = 0.f;
+    for (int ch = 0; ch < C / 8; ch += 2) {                              // C % 16 == 0: two chunks of loads in flight
+      float g0[8], g1[8];
+      km_load8(row, dt, rs, ch, g0);
+      km_load8(row, dt, rs, ch + 1, g1);
+      const f32x4 q0 = ((const f32x4*)s_q)[2 * ch], q1 = ((const f32x4*)s_q)[2 * ch + 1];
+      const f32x4 q2 = ((const f32x4*)s_q)[2 * ch + 2], q3 = ((const f32x4*)s_q)[2 * ch + 3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        a = fmaf(g0[i], q0[i], a);
+        a = fmaf(g0[4 + i], q1[i], a);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        a = fmaf(g1[i], q2[i], a);
+        a = fmaf(g1[4 + i], q3[i], a);
+      }
+    }
+    float b = best[p];
+    if (a > b) {                                                         // false for a chosen row (NaN) and for a NaN score
+      b = a;
+      best[p] = b;
+    }
+    if (b == b && km_before(b, id, (int)p, bv, bid, bf)) { bv = b; bid = id; bf = (int)p; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const long long oid = __shfl_xor(bid, o, 64);
+    const int of = __shfl_xor(bf, o, 64);
+    if (km_before(ov, oid, of, bv, bid, bf)) { bv = ov; bid = oid; bf = of; }
+  }
+  if (lane == 0) { s_part[wave].v = bv; s_part[wave].id = bid; s_part[wave].flat = bf; }
+  __syncthreads();
+  if (tid == 0) {
+    KmPart w = s_part[0];
+    for (int k = 1; k < 4; ++k)
+      if (km_before(s_part[k].v, s_part[k].id, s_part[k].flat, w.v, w.id, w.flat)) w = s_part[k];
+    part[blockIdx.x] = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void km_seed_pick(const KmSegs segs, int nseg, int C, const KmPart* __restrict__ part, int nparts,
+                                                    unsigned* __restrict__ best, KmCur* __restrict__ cur) {
+  __shared__ KmPart s_part[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float bv = 0.f;
+  long long bid = 0;
+  int bf = -1;
+  for (int k = tid; k < nparts; k += 256) {
+    const KmPart w = part[k];
+    if (km_before(w.v, w.id, w.flat, bv, bid, bf)) { bv = w.v; bid = w.id; bf = w.flat; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const long long oid = __shfl_xor(bid, o, 64);
+    const int of = __shfl_xor(bf, o, 64);
+    if (km_before(ov, oid, of, bv, bid, bf)) { bv = ov; bid = oid; bf = of; }
+  }
+  if (lane == 0) { s_part[wave].v = bv; s_part[wave].id = bid; s_part[wave].flat = bf; }
+  __syncthreads();
+  if (tid == 0) {
+    KmPart w = s_part[0];
+    for (int k = 1; k < 4; ++k)
+      if (km_before(s_part[k].v, s_part[k].id, s_part[k].flat, w.v, w.id, w.flat)) w = s_part[k];
+    if (w.flat >= 0) {                                                   // (K <= n_total: a row that is not chosen exists)
+      best[w.flat] = KM_CHOSEN;
+      km_set_cur(segs, nseg, C, w.flat, cur);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- update
+
+__global__ __launch_bounds__(256) void km_tile_keys(const KmSegs segs, int nseg, long long n, int K, unsigned* __restrict__ keys,
+                                                    int* __restrict__ cnt) {
+  __shared__ unsigned key[KM_TILE];
+  const int tid = threadIdx.x;
+  const long long tile = blockIdx.x;
+  int* row = cnt + tile * K;
+  for (int c = tid; c < K; c += 256) row[c] = 0;
+  for (int i = tid; i < KM_TILE; i += 256) {
+    const long long p = tile * KM_TILE + i;
+    unsigned k = KM_NOKEY;
+    if (p < n)
+      km_locate(segs, nseg, p, [&](int s, int local) {
+        const int a = segs.assign[s][local];
+        if ((unsigned)a < (unsigned)K) k = ((unsigned)a << KM_TILE_BITS) | (unsigned)i;   // any other value: the row belongs to no cluster
+      });
+    key[i] = k;
+  }
+  __syncthreads();
+  block_bitonic_sort(key, KM_TILE, PlainBefore{});                       // ends with a barrier (the zeroes above are ordered by it too)
+  for (int i = tid; i < KM_TILE; i += 256) {
+    const unsigned k = key[i];
+    keys[tile * KM_TILE + i] = k;
+    if (k == KM_NOKEY) continue;
+    const unsigned c = k >> KM_TILE_BITS;
+    if (i > 0 && (key[i - 1] >> KM_TILE_BITS) == c) continue;
+    const unsigned lim = (c + 1) << KM_TILE_BITS;                        // the run of cluster c ends at the first key >= lim
+    int lo = i + 1, hi = KM_TILE;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (key[mid] < lim) lo = mid + 1; else hi = mid;
+    }
+    row[c] = lo - i;
+  }
+}
+
+__global__ __launch_bounds__(256) void km_columns(int* __restrict__ cnt, int tiles, int K, int* __restrict__ out_count) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= K) return;
+  int run = 0;
+  for (long long t = 0; t < tiles; ++t) {
+    const int v = cnt[t * K + c];
+    cnt[t * K + c] = run;
+    run += v;
+  }
+  out_count[c] = run;
+}
+
+// base[c] = the members before cluster c, cb[c] = the chunks before it, both with a K-th entry (the totals)
+__global__ __launch_bounds__(1024) void km_scan(const int* __restrict__ count, int K, int* __restrict__ base, int* __restrict__ cb) {
+  __shared__ int s_m[1024], s_c[1024];
+  const int tid = threadIdx.x;
+  const int per = (K + 1023) / 1024, c0 = tid * per, c1 = min(c0 + per, K);
+  int m = 0, ch = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int v = count[c];
+    m += v;
+    ch += (v + KM_CHUNK - 1) / KM_CHUNK;
+  }
+  s_m[tid] = m;
+  s_c[tid] = ch;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int xm = tid >= o ? s_m[tid - o] : 0, xc = tid >= o ? s_c[tid - o] : 0;
+    __syncthreads();
+    s_m[tid] += xm;
+    s_c[tid] += xc;
+    __syncthreads();
+  }
+  int rm = s_m[tid] - m, rc = s_c[tid] - ch;
+  for (int c = c0; c < c1; ++c) {
+    base[c] = rm;
+    cb[c] = rc;
+    const int v = count[c];
+    rm += v;
+    rc += (v + KM_CHUNK - 1) / KM_CHUNK;
+  }
+  if (tid == 1023) {
+    base[K] = s_m[1023];
+    cb[K] = s_c[1023];
+  }
+}
+
+__global__ __launch_bounds__(256) void km_place(const unsigned* __restrict__ keys, const int* __restrict__ cnt, const int* __restrict__ base,
+                                                int K, long long n, int* __restrict__ mem) {
+  __shared__ unsigned key[KM_TILE];
+  const int tid = threadIdx.x;
+  const long long tile = blockIdx.x;
+  for (int i = tid; i < KM_TILE; i += 256) key[i] = keys[tile * KM_TILE + i];
+  __syncthreads();
+  for (int i = tid; i < KM_TILE; i += 256) {
+    const unsigned k = key[i];
+    if (k == KM_NOKEY) continue;
+    const unsigned c = k >> KM_TILE_BITS, lim = c << KM_TILE_BITS;       // (c < K: km_tile_keys made the key)
+    int lo = 0, hi = i;                                                  // the run's head: the first key >= lim
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (key[mid] < lim) lo = mid + 1; else hi = mid;
+    }
+    const long long slot = (long long)base[c] + cnt[tile * K + c] + (i - lo);
+    if (slot < n) mem[slot] = (int)(tile * KM_TILE + (k & (KM_TILE - 1)));   // (always: the counts sum to at most n)
+  }
+}
+
+// the lane's four channels of one row, as stored: expand.hip's ex_load. ESZ = 4 / 2 / 1: every segment has rows of that element size;
+// ESZ = -1: sizes differ, a dword, a second dword and an 8-byte load at offsets chosen by the dtype, every one inside the row, no
+// branch around a load
+template <int ESZ> __device__ __forceinline__ u32x4 km_load(u64 row, int c0, int dt) {
+  u32x4 r = {0u, 0u, 0u, 0u};
+  if constexpr (ESZ == 4) {
+    r = *(const KM_GLOBAL u32x4*)(row + 4u * c0);
+  } else if constexpr (ESZ == 1) {
+    r[0] = *(const KM_GLOBAL unsigned*)(row + (unsigned)c0);
+  } else if constexpr (ESZ == 2) {
+    const u32x2 a = *(const KM_GLOBAL u32x2*)(row + 2u * c0);
+    r[0] = a[0]; r[1] = a[1];
+  } else {
+    const bool wide = dt == COR_F32, narrow = dt == COR_I8;
+    const unsigned o = wide ? 4u * c0 : narrow ? (unsigned)c0 : 2u * c0;
+    const unsigned a = *(const KM_GLOBAL unsigned*)(row + o), b = *(const KM_GLOBAL unsigned*)(row + o + (narrow ? 0u : 4u));
+    const u32x2 c = *(const KM_GLOBAL u32x2*)(row + (wide ? o + 8u : narrow ? (unsigned)c0 & ~7u : o));
+    r[0] = a; r[1] = b; r[2] = c[0]; r[3] = c[1];
+  }
+  return r;
+}
+// stored values -> fp32, exactly (dt is wave-uniform); an int8 value is (float)q * rs, one rounded multiply
+template <int ESZ> __device__ __forceinline__ void km_widen(const u32x4 r, int dt, float rs, float (&x)[4]) {
+  if (ESZ == 1 || (ESZ == -1 && dt == COR_I8)) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = (float)(int)(signed char)(r[0] >> (8 * e)) * rs;
+  } else if (ESZ == 4 || (ESZ == -1 && dt == COR_F32)) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(r[e]);
+  } else if (dt == COR_BF16) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(e & 1 ? r[e >> 1] & 0xffff0000u : r[e >> 1] << 16);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(e & 1 ? r[e >> 1] >> 16 : r[e >> 1] & 0xffffu));
+  }
+}
+
+// the next U members of `mask` (lowest bit first = member order): all U rows are requested before the first add
+template <int ESZ, int U>
+__device__ __forceinline__ void km_group(u64& mask, unsigned plo, unsigned phi, float sc, float rs, int dt, int c0, float (&v)[4], float& ps) {
+  u32x4 raw[U];
+  float cu[U], su[U];
+  int du[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = __builtin_ctzll(mask);                                 // mask has at least U bits set (the caller counted them)
+    mask &= mask - 1;
+    const u64 row = ((u64)(unsigned)__builtin_amdgcn_readlane((int)phi, j) << 32) | (unsigned)__builtin_amdgcn_readlane((int)plo, j);
+    cu[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), j));
+    du[u] = __builtin_amdgcn_readlane(dt, j);
+    su[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rs), j));
+    raw[u] = km_load<ESZ>(row, c0, du[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float x[4];
+    km_widen<ESZ>(raw[u], du[u], su[u], x);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] + x[e];
+    ps = ps + cu[u];
+  }
+}
+
+template <int ESZ>
+__global__ __launch_bounds__(64 * KM_WPB) void km_chunk_sum(const KmSegs segs, int nseg, int K, int C, int with_scores, const int* __restrict__ base,
+                                                            const int* __restrict__ cb, const int* __restrict__ mem, float* __restrict__ P,
+                                                            float* __restrict__ PS) {
+  const int lane = threadIdx.x & 63;
+  const long long w = (long long)blockIdx.x * KM_WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (w >= cb[K]) return;                                                // the whole wave leaves; no barrier follows
+  int lo = 0, hi = K - 1;                                                // the cluster: the last c with cb[c] <= w
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cb[mid] <= w) lo = mid; else hi = mid - 1;
+  }
+  const int c = lo;
+  const int m0 = base[c] + KM_CHUNK * (int)(w - cb[c]), m1 = min(m0 + KM_CHUNK, base[c + 1]);
+  const bool active = 4 * lane < C;
+  const int c0 = active ? 4 * lane : 0;                                  // a lane past the row reads channels 0..3 again: in bounds, unused
+
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  float ps = 0.f;
+  for (int j0 = m0; j0 < m1; j0 += 64) {
+    // lane j: member j0 + j
+    u64 row = 0;
+    float sc = 0.f, rs = 0.f;
+    int dt = COR_F32;
+    bool present = false;
+    if (j0 + lane < m1)
+      present = km_locate(segs, nseg, mem[j0 + lane], [&](int s, int local) {   // the only place a row address is formed
+        dt = segs.dt[s];
+        row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
+        if (dt == COR_I8) rs = segs.scale[s][local];
+        if (with_scores) sc = segs.score[s][local];
+      });
+    u64 mask = __ballot(present);
+    int cnt = __builtin_popcountll(mask);
+    const unsigned plo = (unsigned)row, phi = (unsigned)(row >> 32);
+    for (; cnt >= 8; cnt -= 8) km_group<ESZ, 8>(mask, plo, phi, sc, rs, dt, c0, v, ps);
+    if (cnt & 4) km_group<ESZ, 4>(mask, plo, phi, sc, rs, dt, c0, v, ps);
+    if (cnt & 2) km_group<ESZ, 2>(mask, plo, phi, sc, rs, dt, c0, v, ps);
+    if (cnt & 1) km_group<ESZ, 1>(mask, plo, phi, sc, rs, dt, c0, v, ps);
+  }
+  if (active) {
+    f32x4 y;
+    y[0] = v[0]; y[1] = v[1]; y[2] = v[2]; y[3] = v[3];
+    *(f32x4*)(P + w * C + 4 * lane) = y;
+  }
+  if (lane == 0) PS[w] = ps;
+}
+
+__global__ __launch_bounds__(64 * KM_WPB) void km_finish(int K, int C, const int* __restrict__ count, const int* __restrict__ cb,
+                                                         const float* __restrict__ P, const float* __restrict__ PS, const float* __restrict__ prev,
+                                                         float* __restrict__ out_centroids, float* __restrict__ out_score_sum) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * KM_WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (c >= K) return;
+  const bool active = 4 * lane < C;
+  const int c0 = active ? 4 * lane : 0;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  float ss = 0.f;
+  if (count[c] == 0) {                                                   // an empty cluster keeps its previous centre, bit for bit
+    if (prev) {
+      const f32x4 x = *(const f32x4*)(prev + (long long)c * C + c0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = x[e];
+    }
+  } else {
+    const long long j0 = cb[c], j1 = cb[c + 1];
+    for (long long j = j0; j < j1; ++j) {
+      const f32x4 x = *(const f32x4*)(P + j * C + c0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = v[e] + x[e];
+      ss = ss + PS[j];
+    }
+    // the norm: the stride-halving tree over 256 channel slots (expand.hip, step 3)
+    float s[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] = active ? v[e] * v[e] : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = s[e] + __shfl_xor(s[e], o, 64);
+    }
+    s[0] = s[0] + s[2];
+    s[1] = s[1] + s[3];
+    s[0] = s[0] + s[1];
+    const float s0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s[0])));
+    const float d = fmaxf(__builtin_sqrtf(s0), 1e-12f);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] / d;
+  }
+  if (active) {
+    f32x4 y;
+    y[0] = v[0]; y[1] = v[1]; y[2] = v[2]; y[3] = v[3];
+    *(f32x4*)(out_centroids + (long long)c * C + 4 * lane) = y;
+  }
+  if (out_score_sum && lane == 0) out_score_sum[c] = ss;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+
+inline size_t km_up(size_t b) { return (b + 255) & ~(size_t)255; }
+struct KmLayout {                                                        // byte offsets into the workspace; the two calls share it from 0
+  size_t keys, cnt, base, cb, mem, P, PS, update_end;
+  size_t best, part, cur, seed_end;
+  long long tiles, chunks;
+};
+inline KmLayout km_layout(long long n, int K, int C) {
+  KmLayout L;
+  L.tiles = (n + KM_TILE - 1) / KM_TILE;
+  L.chunks = n / KM_CHUNK + K;                                           // sum of ceil(count / 256) <= n / 256 + K
+  size_t o = 0;
+  L.keys = o; o += km_up((size_t)L.tiles * KM_TILE * 4);
+  L.cnt = o; o += km_up((size_t)L.tiles * K * 4);
+  L.base = o; o += km_up((size_t)(K + 1) * 4);
+  L.cb = o; o += km_up((size_t)(K + 1) * 4);
+  L.mem = o; o += km_up((size_t)n * 4);
+  L.P = o; o += km_up((size_t)L.chunks * C * 4);
+  L.PS = o; o += km_up((size_t)L.chunks * 4);
+  L.update_end = o;
+  o = 0;
+  L.best = o; o += km_up((size_t)n * 4);
+  L.part = o; o += km_up((size_t)KM_SEED_BLOCKS * sizeof(KmPart));
+  L.cur = o; o += km_up(sizeof(KmCur));
+  L.seed_end = o;
+  return L;
+}
+
+inline int km_shape_check(long long n, int K, int C) {
+  if (n < 0 || K < 1 || C < 1) return COR_EINVAL;
+  if (K > COR_KMEANS_KMAX || C > KM_CMAX || C % 16 != 0 || n > 0x7fffffffll) return COR_ENOSUPPORT;
+  return 0;
+}
+
+// the checks of the table both calls share, in the header's order; fills `segs` with the NON-EMPTY segments in table order
+inline int km_table(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n, const int* seg_dtype,
+                    int nseg, const int* const* seg_assign, bool need_assign, const float* const* seg_score, int K, int C, KmSegs& segs, int& live,
+                    long long& n_total, int& seen) {
+  if (nseg < 0 || K < 1 || C < 1) return COR_EINVAL;
+  if (nseg > 0 && (!seg_rows || !seg_offset || !seg_n || !seg_dtype || (need_assign && !seg_assign))) return COR_EINVAL;
+  if (nseg > KM_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
+  for (int s = 0; s < nseg; ++s)
+    if (seg_entry_bad(seg_n[s], seg_rows[s] && (seg_dtype[s] != COR_I8 || (seg_scale && seg_scale[s])) && (!need_assign || seg_assign[s]) &&
+                                    (!seg_score || seg_score[s])))
+      return COR_EINVAL;
+  n_total = 0;
+  for (int s = 0; s < nseg; ++s) n_total += seg_n[s];
+  if (const int rc = km_shape_check(n_total, K, C)) return rc;
+  segs = KmSegs{};
+  live = 0;
+  seen = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_dtype[s] != COR_F32 && seg_dtype[s] != COR_BF16 && seg_dtype[s] != COR_F16 && seg_dtype[s] != COR_I8) return COR_ENOSUPPORT;
+    if (seg_n[s] == 0) continue;
+    segs.rows[live] = (const unsigned char*)seg_rows[s];
+    segs.off[live] = seg_offset[s];
+    segs.n[live] = seg_n[s];
+    segs.dt[live] = seg_dtype[s];
+    segs.scale[live] = seg_dtype[s] == COR_I8 ? seg_scale[s] : nullptr;
+    segs.assign[live] = need_assign ? seg_assign[s] : nullptr;
+    segs.score[live] = seg_score ? seg_score[s] : nullptr;
+    seen |= 1 << seg_dtype[s];
+    ++live;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" long cor_kmeans_workspace_bytes(long n_total, int K, int C) {
+  if (const int rc = km_shape_check(n_total, K, C)) return rc;
+  const KmLayout L = km_layout(n_total, K, C);
+  return (long)(L.update_end > L.seed_end ? L.update_end : L.seed_end);
+}
+
+extern "C" int cor_kmeans_seed(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                               const int* seg_dtype, int nseg, int C, int K, long long first_id, long long* out_ids, float* out_centroids,
+                               void* workspace, void* stream) {
+  if (!out_ids || !out_centroids || !workspace) return COR_EINVAL;
+  KmSegs segs;
+  int live = 0, seen = 0;
+  long long n = 0;
+  if (const int rc = km_table(seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, nullptr, false, nullptr, K, C, segs, live, n, seen)) return rc;
+  if (K > n) return COR_EINVAL;
+  long long first = -1, base = 0;
+  for (int s = 0; s < live; ++s) {
+    if (first < 0 && first_id >= segs.off[s] && (u64)first_id - (u64)segs.off[s] < (u64)segs.n[s]) first = base + (first_id - segs.off[s]);
+    base += segs.n[s];
+  }
+  if (first < 0) return COR_EINVAL;                                      // first_id is held by no segment
+
+  const KmLayout L = km_layout(n, K, C);
+  unsigned char* ws = (unsigned char*)workspace;
+  float* best = (float*)(ws + L.best);
+  KmPart* part = (KmPart*)(ws + L.part);
+  KmCur* cur = (KmCur*)(ws + L.cur);
+  const long long want = (n + 255) / 256;
+  const int blocks = (int)(want < KM_SEED_BLOCKS ? want : KM_SEED_BLOCKS);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(km_seed_init, dim3(blocks), dim3(256), 0, st, segs, live, n, C, first, (unsigned*)best, cur);
+  for (int t = 0; t < K; ++t) {
+    const int score = t + 1 < K;
+    hipLaunchKernelGGL(km_seed_step, dim3(score ? blocks : 1), dim3(256), 0, st, segs, live, n, C, best, cur, part, t, score, out_ids, out_centroids);
+    if (score) hipLaunchKernelGGL(km_seed_pick, dim3(1), dim3(256), 0, st, segs, live, C, part, blocks, (unsigned*)best, cur);
+  }
+  COR_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int cor_kmeans_update(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                                 const int* seg_dtype, int nseg, const int* const* seg_assign, const float* const* seg_score, int C, int K,
+                                 const float* prev, float* out_centroids, int* out_count, float* out_score_sum, void* workspace, void* stream) {
+  if (!out_centroids || !out_count || !workspace || (seg_score != nullptr) != (out_score_sum != nullptr)) return COR_EINVAL;
+  KmSegs t;
+  int live = 0, seen = 0;
+  long long n = 0;
+  if (const int rc = km_table(seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, seg_assign, true, seg_score, K, C, t, live, n, seen)) return rc;
+  // ascending offset: ascending flat position is ascending global id (the ranges are disjoint)
+  int order[KM_SEGMAX];
+  for (int s = 0; s < live; ++s) order[s] = s;
+  for (int a = 1; a < live; ++a)
+    for (int b = a; b > 0 && t.off[order[b]] < t.off[order[b - 1]]; --b) { const int x = order[b]; order[b] = order[b - 1]; order[b - 1] = x; }
+  KmSegs segs = {};
+  for (int s = 0; s < live; ++s) {
+    const int o = order[s];
+    segs.rows[s] = t.rows[o]; segs.off[s] = t.off[o]; segs.n[s] = t.n[o]; segs.dt[s] = t.dt[o]; segs.scale[s] = t.scale[o];
+    segs.assign[s] = t.assign[o]; segs.score[s] = t.score[o];
+  }
+
+  const KmLayout L = km_layout(n, K, C);
+  unsigned char* ws = (unsigned char*)workspace;
+  unsigned* keys = (unsigned*)(ws + L.keys);
+  int* cnt = (int*)(ws + L.cnt);
+  int* base = (int*)(ws + L.base);
+  int* cb = (int*)(ws + L.cb);
+  int* mem = (int*)(ws + L.mem);
+  float* P = (float*)(ws + L.P);
+  float* PS = (float*)(ws + L.PS);
+  const int tiles = (int)L.tiles;
+  hipStream_t st = (hipStream_t)stream;
+  if (tiles > 0) hipLaunchKernelGGL(km_tile_keys, dim3(tiles), dim3(256), 0, st, segs, live, n, K, keys, cnt);
+  hipLaunchKernelGGL(km_columns, dim3((K + 255) / 256), dim3(256), 0, st, cnt, tiles, K, out_count);
+  hipLaunchKernelGGL(km_scan, dim3(1), dim3(1024), 0, st, out_count, K, base, cb);
+  if (tiles > 0) {
+    hipLaunchKernelGGL(km_place, dim3(tiles), dim3(256), 0, st, keys, cnt, base, K, n, mem);
+    const dim3 grid((unsigned)((L.chunks + KM_WPB - 1) / KM_WPB)), block(64 * KM_WPB);
+    const int with_scores = seg_score != nullptr;
+#define KM_CHUNKS(ESZ) hipLaunchKernelGGL(km_chunk_sum<ESZ>, grid, block, 0, st, segs, live, K, C, with_scores, base, cb, mem, P, PS)
+    if (seen == 1 << COR_F32) KM_CHUNKS(4);
+    else if (seen == 1 << COR_I8) KM_CHUNKS(1);
+    else if ((seen & ~((1 << COR_BF16) | (1 << COR_F16))) == 0) KM_CHUNKS(2);
+    else KM_CHUNKS(-1);
+#undef KM_CHUNKS
+  }
+  hipLaunchKernelGGL(km_finish, dim3((K + KM_WPB - 1) / KM_WPB), dim3(64 * KM_WPB), 0, st, K, C, out_count, cb, P, PS, prev, out_centroids, out_score_sum);
+  COR_CHECK_LAUNCH();
+  return 0;
+}

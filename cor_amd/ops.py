@@ -1148,6 +1148,99 @@ def rerank_diffusion(segments, scores, idx, k, kd=8, kq=None, gamma=3, alpha=0.9
     return (out_s, out_i, out_p) if return_pos else (out_s, out_i)
 
 
+def _kmeans_front(who, segments, K):
+    """The checks kmeans_seed and kmeans_update share -> (segments with int offsets, C, n_total); nothing touches the device."""
+    segments = _row_segments(who, segments, nat.CLUSTER_SEGMAX)
+    if not 1 <= int(K) <= nat.KMEANS_KMAX:
+        raise ValueError(f"{who}: K must be in [1, {nat.KMEANS_KMAX}], got {K}")
+    C = _row_segments_width(who, segments)
+    n = sum(seg[0].shape[0] for seg in segments)
+    if n >= 2 ** 31:
+        raise ValueError(f"{who}: {n} rows, one call takes fewer than 2^31")
+    return segments, C, n
+
+
+def _kmeans_workspace(n, K, C, dev):
+    nbytes = _lib().cor_kmeans_workspace_bytes(n, int(K), C)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_kmeans_workspace_bytes")
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
+
+def kmeans_seed(segments, K, first_id=None):
+    """Farthest-point ("max-min") seeding on the device (cor_kmeans_seed): K rows that are far from each other, deterministic, no random
+    numbers. segments as diversify_mmr takes them: a list of (rows, offset), rows [n,C] fp32 / bf16 / fp16 holding the global ids
+    [offset, offset + n), or of (rows_i8, scales, offset); at most nat.CLUSTER_SEGMAX (16), pairwise disjoint, dtypes free to differ.
+    -> (ids i64[K], centroids f32[K,C]): the chosen rows' global ids in the order they were chosen and their values. The first is
+    first_id (None: the smallest id present); then K - 1 times the row whose largest chain similarity to the rows chosen so far is
+    smallest, ties to the smallest id. The similarity is the fmaf chain of the searches over the rows' fp32 values, so neither the
+    segmentation nor the storage dtype of equal values changes a bit; include/cor_amd.h has the definition to the bit. 1 <= K <=
+    min(nat.KMEANS_KMAX, the number of rows), C <= 256 and C % 16 == 0. 2K launches, no host synchronisation; capturable in a graph."""
+    who = "kmeans_seed"
+    segments, C, n = _kmeans_front(who, segments, K)
+    if int(K) > n:
+        raise ValueError(f"{who}: K = {K} but the segments hold {n} rows")
+    live = [seg for seg in segments if seg[0].shape[0]]
+    first_id = min(seg[-1] for seg in live) if first_id is None else int(first_id)
+    if not any(seg[-1] <= first_id < seg[-1] + seg[0].shape[0] for seg in live):
+        raise ValueError(f"{who}: no segment holds first_id = {first_id}")
+    dev = _dev(*[t for seg in segments for t in seg[:-1]])
+    table, nseg, _keep = _row_table(segments)
+    ids = torch.empty((int(K),), dtype=torch.int64, device=dev)
+    cent = torch.empty((int(K), C), dtype=torch.float32, device=dev)
+    ws = _kmeans_workspace(n, K, C, dev)
+    nat.check(_lib().cor_kmeans_seed(*table, nseg, C, int(K), first_id, ids.data_ptr(), cent.data_ptr(), ws.data_ptr(), _s()), "cor_kmeans_seed")
+    return ids, cent
+
+
+def kmeans_update(segments, assigns, K, scores=None, prev=None, out=None):
+    """The centre step of spherical k-means on the device (cor_kmeans_update). segments as kmeans_seed takes them; assigns: one int32 [n]
+    tensor per segment, the cluster of each row (a value outside [0, K), e.g. -1: the row belongs to no cluster); scores: None, or one
+    f32 [n] tensor per segment, each row's score to its centre; prev: None or f32 [K,C], the centres an empty cluster keeps (None: a zero
+    row); out: None or f32 [K,C] to write into (not prev). -> (centroids f32[K,C], counts i32[K], score_sums f32[K] or None). A centre is
+    the sum of its members' values, taken in ascending global id in chunks of 256 members whose partial sums are then added up, divided by
+    its Euclidean norm (the norm tree of expand_queries); score_sums is the same two-level sum over the members' scores. Every step is
+    one rounded fp32 operation in an order include/cor_amd.h fixes, so the result does not depend on the segmentation, on the storage
+    dtype of equal values or on how skewed the clusters are. 1 <= K <= nat.KMEANS_KMAX (16384), C <= 256 and C % 16 == 0. Six launches,
+    no host synchronisation; capturable in a graph."""
+    who = "kmeans_update"
+    segments, C, n = _kmeans_front(who, segments, K)
+    K = int(K)
+
+    def per_segment(ts, dtype, name):
+        ts = list(ts)
+        if len(ts) != len(segments):
+            raise ValueError(f"{who}: {len(ts)} {name} tensors for {len(segments)} segments")
+        for t, seg in zip(ts, segments):
+            if t.dtype != dtype or t.dim() != 1 or t.shape[0] != seg[0].shape[0]:
+                raise ValueError(f"{who}: {name} must be {dtype} [{seg[0].shape[0]}] per segment, got {t.dtype} {tuple(t.shape)}")
+        return ts
+
+    assigns = per_segment(assigns, torch.int32, "assigns")
+    scores = None if scores is None else per_segment(scores, torch.float32, "scores")
+    for t, name in ((prev, "prev"), (out, "out")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (K, C) or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be contiguous float32 [{K}, {C}], got {t.dtype} {tuple(t.shape)}")
+    if out is not None and prev is not None and out.data_ptr() == prev.data_ptr():
+        raise ValueError(f"{who}: out must not be prev")
+    dev = _dev(prev, out, *assigns, *(scores or ()), *[t for seg in segments for t in seg[:-1]])
+    if dev is None:
+        raise ValueError(f"{who}: no tensor names a device (no segments and neither prev nor out)")
+    table, nseg, _keep = _row_table(segments)
+    assigns = [a.contiguous() for a in assigns]
+    scores = None if scores is None else [s.contiguous() for s in scores]
+    m = max(nseg, 1)
+    seg_a = (nat.C.c_void_p * m)(*[a.data_ptr() or None for a in assigns])
+    seg_s = None if scores is None else (nat.C.c_void_p * m)(*[s.data_ptr() or None for s in scores])
+    cent = torch.empty((K, C), dtype=torch.float32, device=dev) if out is None else out
+    counts = torch.empty((K,), dtype=torch.int32, device=dev)
+    sums = None if scores is None else torch.empty((K,), dtype=torch.float32, device=dev)
+    ws = _kmeans_workspace(n, K, C, dev)
+    nat.check(_lib().cor_kmeans_update(*table, nseg, seg_a, seg_s, C, K, _p(prev) or None, cent.data_ptr(), counts.data_ptr(), _p(sums) or None,
+                                       ws.data_ptr(), _s()), "cor_kmeans_update")
+    return cent, counts, sums
+
+
 _FUSE_MODES = {"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "max": nat.FUSE_MAX}
 _FUSE_NORMS = {"none": nat.FUSE_NORM_NONE, "minmax": nat.FUSE_NORM_MINMAX}
 _FUSE_MISSING = {"zero": nat.FUSE_MISSING_ZERO, "floor": nat.FUSE_MISSING_FLOOR}

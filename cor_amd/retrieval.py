@@ -14,6 +14,7 @@ lists go to one rank in ONE gather and are merged once on the host by (score des
 from __future__ import annotations
 
 import contextlib
+import math
 
 import torch
 
@@ -294,6 +295,69 @@ def _diffuse(who, table, dev, scores, idx, k, kd, kq, gamma, alpha, iters, retur
         return ops.rerank_diffusion(table, scores, idx, k, kd=kd, kq=kq, gamma=gamma, alpha=alpha, iters=iters, return_pos=return_pos)
 
 
+class Clustering:
+    """What .cluster of a GalleryShard, a QuantizedGallery or a GallerySet returns. centroids: a GalleryShard of K unit fp32 rows, offset 0
+    (its row index is the cluster id). assign: int32 on the device, the cluster of every row, one tensor per segment for a GallerySet (in
+    the order of its non-empty segments) and ONE tensor for a shard: usable as `groups=` / `labels=` of a shard over the same rows as it
+    is. counts: int32 [K] on the device. objective: a Python list, per assignment pass the mean over the rows of their score to their
+    centre. iters: the passes made. converged: the last pass changed no row."""
+
+    def __init__(self, centroids, assign, counts, objective, iters, converged):
+        self.centroids, self.assign, self.counts = centroids, assign, counts
+        self.objective, self.iters, self.converged = objective, iters, converged
+
+    def assign_queries(self, queries: torch.Tensor):
+        """queries f32[Bq,C] -> (scores f32[Bq,1], cluster ids i64[Bq,1]): the nearest centre of each query (centroids.search(q, 1))."""
+        return self.centroids.search(queries, 1)
+
+
+def _cluster(who, live, single, n_clusters, iters, init, first_id, batch):
+    """Spherical k-means over the non-empty segments `live`. The assignment is the chain-exact search of the rows in the centres, the
+    centre step is ops.kmeans_update: the whole loop is defined to the bit. One host synchronisation per pass."""
+    n = sum(len(sh) for sh in live)
+    K = int(n_clusters)
+    if n == 0:
+        raise ValueError(f"{who}: nothing to cluster (no rows)")
+    if not 1 <= K <= min(n, ops.nat.KMEANS_KMAX):
+        raise ValueError(f"{who}: n_clusters must be in [1, min({n} rows, {ops.nat.KMEANS_KMAX})], got {n_clusters}")
+    if int(iters) < 1 or int(batch) < 1:
+        raise ValueError(f"{who}: iters and batch must be at least 1, got iters={iters}, batch={batch}")
+    if len(live) > ops.nat.CLUSTER_SEGMAX:
+        raise ValueError(f"{who}: {len(live)} non-empty segments, one clustering spans at most {ops.nat.CLUSTER_SEGMAX}")
+    C = live[0].rows.shape[1]
+    if isinstance(init, torch.Tensor):
+        if init.dtype != torch.float32 or tuple(init.shape) != (K, C):
+            raise ValueError(f"{who}: init must be float32 [{K}, {C}], got {init.dtype} {tuple(init.shape)}")
+    elif init != "maxmin":
+        raise ValueError(f"{who}: init must be 'maxmin' or a float32 tensor [K, C], got {init!r}")
+    dev = live[0].rows.device
+    table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
+    with _on(dev):
+        cent = init.to(dev).contiguous().clone() if isinstance(init, torch.Tensor) else ops.kmeans_seed(table, K, first_id)[1]
+        assign = [torch.full((len(sh),), -1, dtype=torch.int32, device=dev) for sh in live]
+        objective, converged, passes, counts = [], False, 0, None
+        while passes < int(iters) and not converged:
+            centres = GalleryShard(cent, offset=0)
+            new, score = [], []
+            for sh in live:
+                a = torch.empty((len(sh),), dtype=torch.int32, device=dev)
+                s = torch.empty((len(sh),), dtype=torch.float32, device=dev)
+                for lo in range(0, len(sh), int(batch)):
+                    bs, bi = centres.search(_rows_as_queries(sh, lo, lo + int(batch)), 1)
+                    a[lo:lo + int(batch)] = bi[:, 0]
+                    s[lo:lo + int(batch)] = bs[:, 0]
+                new.append(a)
+                score.append(s)
+            changed = sum((a != b).sum() for a, b in zip(new, assign))
+            cent, counts, sums = ops.kmeans_update(table, new, K, scores=score, prev=cent)
+            host = torch.cat([sums.double(), changed.double().reshape(1)]).cpu().tolist()    # the pass's one synchronisation
+            objective.append(math.fsum(host[:K]) / n)
+            converged = host[K] == 0
+            assign = new
+            passes += 1
+    return Clustering(GalleryShard(cent, offset=0), assign[0] if single else assign, counts, objective, passes, converged)
+
+
 def _search(shard, who, fns, row_args, queries, k, query_labels, mode, distinct):
     """The search of GalleryShard and QuantizedShard: fns = the (plain, filtered, distinct) ops, row_args = (rows,) or (rows, scales).
     Both argument checks come before anything touches the device."""
@@ -442,6 +506,16 @@ class GalleryShard:
         to min(kin, 256). Entries this shard does not hold are dropped; fewer than k present: the (-inf, -1[, -1]) tail."""
         return _diffuse("GalleryShard.diffuse", [(self.rows, self.offset)], self.rows.device, scores, idx, k, kd, kq, gamma, alpha, iters, return_pos)
 
+    def cluster(self, n_clusters: int, iters: int = 20, init="maxmin", first_id=None, batch: int = 4096):
+        """Spherical k-means over this shard's rows -> Clustering (centroids, assign, counts, objective, iters, converged). init "maxmin": the
+        centres start as ops.kmeans_seed's farthest-point rows (first_id: the first of them, None: the smallest id), deterministic; or a
+        float32 tensor [n_clusters, C] of starting centres. Per pass every row is assigned to its nearest centre by the exact search
+        (centroids.search(rows, 1), `batch` rows at a time: the score is the chain score, ties go to the lower cluster) and
+        ops.kmeans_update recomputes the centres; a cluster that runs empty keeps its centre. The loop ends after a pass that changes no
+        row, or after `iters` passes. Search and centre step are defined to the bit, so is the result. ValueError for no rows or for
+        n_clusters above the row count."""
+        return _cluster("GalleryShard.cluster", [self] if len(self) else [], True, n_clusters, iters, init, first_id, batch)
+
     def quantized(self):
         """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
         coarse stage of two_stage_search over these rows. This shard is left untouched. The labels and the group ids are carried (the same
@@ -566,6 +640,11 @@ class QuantizedGallery(QuantizedShard):
         dequantized()'s fp32 rows."""
         return _diffuse("QuantizedGallery.diffuse", [(self.rows, self.scales, self.offset)], self.rows.device, scores, idx, k, kd, kq, gamma, alpha,
                         iters, return_pos)
+
+    def cluster(self, n_clusters: int, iters: int = 20, init="maxmin", first_id=None, batch: int = 4096):
+        """GalleryShard.cluster over the int8 rows: a row's value is float(q) * scale, the queries of the assignment are those values, so the
+        result equals bitwise the clustering of dequantized()'s fp32 rows."""
+        return _cluster("QuantizedGallery.cluster", [self] if len(self) else [], True, n_clusters, iters, init, first_id, batch)
 
     def dequantized(self, dtype: torch.dtype = torch.float32):
         """A GalleryShard (same offset, labels and groups) of the rows this shard stands for, float(q) * scale in fp32, rounded again to
@@ -777,6 +856,12 @@ class GallerySet:
         table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
         return _diffuse("GallerySet.diffuse", table, live[0].rows.device if live else scores.device, scores, idx, k, kd, kq, gamma, alpha, iters,
                         return_pos)
+
+    def cluster(self, n_clusters: int, iters: int = 20, init="maxmin", first_id=None, batch: int = 4096):
+        """GalleryShard.cluster over all segments as one gallery (at most 16 non-empty ones; their dtypes may differ, a plain
+        QuantizedShard included). Clustering.assign is a list, one tensor per non-empty segment in offset order. The result equals bitwise
+        that of a single fp32 GalleryShard over the concatenated widened / dequantised rows."""
+        return _cluster("GallerySet.cluster", self._live(), False, n_clusters, iters, init, first_id, batch)
 
     def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
         """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new

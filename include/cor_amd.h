@@ -885,6 +885,80 @@ long cor_fuse_lists_workspace_bytes(int P, int Bq, int kin, int k);
 int cor_fuse_lists(const float* scores, const long long* idx, int P, int Bq, int kin, const float* weights_host, int mode, int normalize,
                    int missing, float rrf_c, int k, float* out_scores, long long* out_idx, int* out_count, void* workspace, void* stream);
 
+/* Clustering of a gallery: spherical k-means (Dhillon & Modha, Machine Learning 2001) with farthest-point ("max-min") seeding (Gonzalez,
+ * Theoretical Computer Science 1985). The cluster of a row is an id like any other: as `groups` of a distinct search it gives k results
+ * from k modes of the gallery, as `labels` of a filtered search it confines a query to the cell of its nearest centre, and the centres are
+ * the coarse quantiser of a cell-probing search. The ASSIGNMENT step is the existing search (the centres as an fp32 gallery, the rows as
+ * queries, k = 1); these two calls are the seeding and the centre step. Both are defined to the bit.
+ *
+ * Common to both calls. The segment table is exactly that of cor_diversify_mmr: seg_rows / seg_scale / seg_offset / seg_n / seg_dtype are
+ * HOST arrays of nseg entries (COR_F32 / COR_BF16 / COR_F16 / COR_I8 segments, mixed freely, a COR_I8 segment with its DEVICE row scales;
+ * seg_scale may be NULL when no segment is COR_I8), at most COR_CLUSTER_SEGMAX segments with pairwise disjoint id ranges, copied into a
+ * by-value kernel argument. Rows 16-byte aligned as for the searches. A row's VALUE x(r)[c] is the stored value widened exactly to fp32; of
+ * an int8 row (float)q[c] * scale[row], ONE rounded fp32 multiply (the rule of cor_expand_queries_sq). n_total is the sum of seg_n.
+ * C <= 256 and C % 16 == 0; 1 <= K <= COR_KMEANS_KMAX; n_total < 2^31. The calls make no device allocation, no host-to-device copy and no
+ * host synchronisation; everything runs on `stream` and both calls can be captured in a graph. `workspace`: device memory of at least
+ * cor_kmeans_workspace_bytes(n_total, K, C) bytes, 256-byte aligned, contents free; the figure covers both calls (they may share the buffer
+ * when they do not run concurrently).
+ * Error order, both calls; all of it is decided before any HIP call. (1) COR_EINVAL: a null output or workspace pointer (cor_kmeans_update:
+ * out_score_sum NULL while seg_score is not, or the reverse); nseg < 0, K < 1, C < 1; a null segment array (seg_rows, seg_offset, seg_n,
+ * seg_dtype; cor_kmeans_update: seg_assign) with nseg > 0. (2) COR_ENOSUPPORT: nseg > COR_CLUSTER_SEGMAX (before the arrays are read).
+ * (3) COR_EINVAL: a negative seg_n; for a segment with seg_n > 0 a null seg_rows[s], a null scale (entry or array) of a COR_I8 segment, a
+ * null seg_assign[s], a null seg_score[s] while seg_score is given. (4) COR_ENOSUPPORT: K > COR_KMEANS_KMAX, C > 256 or C % 16 != 0,
+ * n_total >= 2^31, then an unknown seg_dtype. (5) cor_kmeans_seed only, COR_EINVAL: K > n_total, then a first_id that no segment holds.
+ * cor_kmeans_workspace_bytes returns the byte count, or COR_EINVAL (n_total < 0, K < 1, C < 1), then COR_ENOSUPPORT (as in (4)).
+ *
+ * cor_kmeans_seed: K rows that are far from each other, deterministic, no random numbers. out_ids i64 [K], out_centroids f32 [K,C].
+ * Definition, fixed to the bit:
+ *   sim(r, r') is the fmaf chain of oracle/c/sim_chain.c over x(r) and x(r') (neither re-rounded): acc = +0; for chunk c = 0 .. C/8 - 1 and
+ *   i = 0 .. 3: acc = fmaf(x(r)[8c+i], x(r')[8c+i], acc), then acc = fmaf(x(r)[8c+4+i], x(r')[8c+4+i], acc). It is bitwise symmetric.
+ *   c_0 = the row with global id first_id. best[g] = -inf for every row g. For t = 0 .. K-1:
+ *     1. out_ids[t] = the id of c_t, out_centroids[t,:] = x(c_t).
+ *     2. for every row g: s = sim(c_t, g); if (s > best[g]) best[g] = s.
+ *     3. c_t is CHOSEN.
+ *     4. c_{t+1} = the row that is not chosen with the smallest best by the IEEE `<` comparison (-0.0 and +0.0 tie); ties go to the
+ *        smallest global id.
+ *   Preconditions: finite rows. (Otherwise the result is unspecified, but every access stays in bounds.)
+ * The result depends only on the set of (id, value) pairs: not on how the rows are cut into segments, on the segments' order, on which
+ * dtype stores equal values, or on the launch geometry ((best, id) is a total order on the rows). Identical rows are chosen last: a twin
+ * of a chosen row has best = sim(r, r), the largest value a unit row reaches.
+ * 2K launches: one that sets best and the first row, then per step a scoring launch (at most 4096 blocks of 256 threads; a thread owns
+ * rows and walks their chains against c_t's row in LDS, keeps the smallest (best, id) it saw; one partial per block) and a one-block
+ * launch that reduces the partials, marks the winner and leaves it ON THE DEVICE for the next step; the last step only writes its output.
+ *
+ * cor_kmeans_update: the centre step. seg_assign: a HOST array of nseg DEVICE pointers, int32 [seg_n[s]], the cluster of each row.
+ * seg_score: NULL, or the same shape in f32: each row's score to its centre. prev: NULL or f32 [K,C]. out_centroids f32 [K,C], out_count
+ * i32 [K], out_score_sum f32 [K], NULL exactly when seg_score is.
+ * Definition, fixed to the bit: every + * / and sqrtf is ONE IEEE fp32 operation, correctly rounded, never contracted.
+ *   Membership. The members of cluster c are the rows with assign == c, in ASCENDING GLOBAL ID. A row whose assign value lies outside
+ *   [0, K) (-1, K, INT_MIN) belongs to no cluster; nothing but its assign entry is read.
+ *   Chunk sums. The members are taken in chunks of 256 consecutive members by ordinal. For chunk j: p_j[ch] = +0, then
+ *   p_j[ch] = p_j[ch] + x(member)[ch] in member order.
+ *   Total. v[ch] = +0, then v[ch] = v[ch] + p_j[ch] for j ascending. The two-level order is part of the definition: it lets a large
+ *   cluster be summed by several waves while the bits stay fixed.
+ *   Normalisation. Exactly step 3 of cor_expand_queries: s[ch] = v[ch] * v[ch] for ch < C and +0 for C <= ch < 256; for h = 128, 64, ..,
+ *   1: s[ch] = s[ch] + s[ch + h] for ch < h; d = max(sqrtf(s[0]), 1e-12f); out_centroids[c,ch] = v[ch] / d.
+ *   Counts and score sums. out_count[c] = the number of members. out_score_sum[c]: the same two-level sum over the members' scores
+ *   (q_j = +0, q_j = q_j + score in member order; then +0 plus the q_j for j ascending).
+ *   Empty cluster. out_centroids[c,:] = prev[c,:] bit for bit, or +0 if prev is NULL; out_count[c] = 0, out_score_sum[c] = +0.
+ *   Preconditions: finite rows and scores. prev and out_centroids must not overlap.
+ * The result does not depend on how the rows are cut into segments, on the segments' order or on which dtype stores equal values.
+ * n_total == 0 (also nseg == 0) is legal: every cluster is empty.
+ * 6 launches. The member lists are built in the workspace by a stable counting sort: rows in tiles of 2048 (ascending id); per tile a
+ * block sorts 32-bit keys [cluster | position in the tile] in LDS and writes the tile's count of every cluster into a tiles x K table;
+ * one thread per cluster scans its column; one block scans the K totals; per tile a block places its rows. No atomics, integer or
+ * float. Then one WAVE per (cluster, chunk): lane l owns channels [4l, 4l + 4), a member row is one coalesced wave load, eight loads are in
+ * flight before the first add; the partial rows go to the workspace and one wave per cluster adds them up and normalises. */
+#define COR_CLUSTER_SEGMAX 16
+#define COR_KMEANS_KMAX 16384
+long cor_kmeans_workspace_bytes(long n_total, int K, int C);
+int cor_kmeans_seed(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                    const int* seg_dtype, int nseg, int C, int K, long long first_id, long long* out_ids, float* out_centroids,
+                    void* workspace, void* stream);
+int cor_kmeans_update(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                      const int* seg_dtype, int nseg, const int* const* seg_assign, const float* const* seg_score, int C, int K,
+                      const float* prev, float* out_centroids, int* out_count, float* out_score_sum, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
