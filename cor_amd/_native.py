@@ -24,6 +24,7 @@ RERANK_SEGMAX = 16    # most graph segments one cor_knn_reciprocal / cor_rerank_
 DIVERSIFY_SEGMAX = 16    # most gallery segments one cor_diversify_mmr launch reads (COR_DIVERSIFY_SEGMAX)
 DIFFUSE_NMAX, DIFFUSE_KDMAX, DIFFUSE_SEGMAX = 256, 32, 16    # cor_rerank_diffusion: candidates per query, graph neighbours per candidate, gallery segments (COR_DIFFUSE_*)
 CLUSTER_SEGMAX, KMEANS_KMAX = 16, 16384    # cor_kmeans_seed / cor_kmeans_update: gallery segments, clusters (COR_CLUSTER_SEGMAX, COR_KMEANS_KMAX)
+IVF_NPROBE_MAX = 256    # most probes per query of cor_ivf_search (COR_IVF_NPROBE_MAX)
 FUSE_PMAX = 16   # most lists per query one cor_fuse_lists launch fuses (COR_FUSE_PMAX)
 FUSE_RRF, FUSE_SUM, FUSE_MAX = 0, 1, 2    # cor_fuse_lists modes (COR_FUSE_RRF / _SUM / _MAX)
 FUSE_NORM_NONE, FUSE_NORM_MINMAX = 0, 1    # ... score normalisation per list (COR_FUSE_NORM_*)
@@ -111,12 +112,17 @@ SIGNATURES = {
     "cor_kmeans_workspace_bytes": [_l, _i, _i],
     "cor_kmeans_seed": [_p, _p, _p, _p, _p, _i, _i, _i, _ll, _p, _p, _p, _p],
     "cor_kmeans_update": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p],
+    "cor_ivf_build_workspace_bytes": [_l, _i, _i],
+    "cor_ivf_build": [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "cor_ivf_search_workspace_bytes": [_i, _i, _i, _i, _i, _i],
+    "cor_ivf_search": [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
 }
 _RESTYPE = {"cor_topk_workspace_bytes": _l, "cor_topk_filtered_workspace_bytes": _l, "cor_topk_distinct_workspace_bytes": _l,
             "cor_range_workspace_bytes": _l, "cor_range_filtered_workspace_bytes": _l, "cor_topk_i8_workspace_bytes": _l,
             "cor_topk_i8_filtered_workspace_bytes": _l, "cor_topk_i8_distinct_workspace_bytes": _l,
             "cor_merge_topk_workspace_bytes": _l, "cor_rescore_workspace_bytes": _l,
-            "cor_rescore_i8_workspace_bytes": _l, "cor_fuse_lists_workspace_bytes": _l, "cor_kmeans_workspace_bytes": _l}
+            "cor_rescore_i8_workspace_bytes": _l, "cor_fuse_lists_workspace_bytes": _l, "cor_kmeans_workspace_bytes": _l,
+            "cor_ivf_build_workspace_bytes": _l, "cor_ivf_search_workspace_bytes": _l}
 
 _lib = None
 

@@ -1241,7 +1241,105 @@ def kmeans_update(segments, assigns, K, scores=None, prev=None, out=None):
     return cent, counts, sums
 
 
-_FUSE_MODES = {"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "max": nat.FUSE_MAX}
+def ivf_build(segments, assigns, K):
+    """Cell-contiguous storage of a clustered gallery on the device (cor_ivf_build). segments as kmeans_update takes them, but of ONE
+    dtype (float32 / bfloat16 / float16 rows, or int8 rows with their scales): rows are copied bit for bit, never converted; assigns: one
+    int32 [n] tensor per segment, the cell of each row (a value outside [0, K): the row is not indexed).
+    -> (rows [n_total,C] in the segments' dtype, scales f32[n_total] or None, ids i64[n_total], cell_start i32[K+1]). Cell c owns the
+    slots [cell_start[c], cell_start[c+1]), its rows in ascending global id; cell_start[K] is the number of indexed rows and the slots
+    behind it are left unwritten. The result does not depend on the segmentation. 1 <= K <= nat.KMEANS_KMAX, C <= 256 and C % 16 == 0.
+    Five launches, no host synchronisation; capturable in a graph."""
+    who = "ivf_build"
+    segments, C, n = _kmeans_front(who, segments, K)
+    K = int(K)
+    if not segments:
+        raise ValueError(f"{who}: no segment names a dtype and a device")
+    i8 = len(segments[0]) == 3
+    dtype = segments[0][0].dtype
+    if any((len(seg) == 3) != i8 or seg[0].dtype != dtype for seg in segments):
+        raise ValueError(f"{who}: the segments must share one dtype (rows are copied, never converted)")
+    assigns = list(assigns)
+    if len(assigns) != len(segments):
+        raise ValueError(f"{who}: {len(assigns)} assigns tensors for {len(segments)} segments")
+    for t, seg in zip(assigns, segments):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != seg[0].shape[0]:
+            raise ValueError(f"{who}: assigns must be {torch.int32} [{seg[0].shape[0]}] per segment, got {t.dtype} {tuple(t.shape)}")
+    dev = _dev(*assigns, *[t for seg in segments for t in seg[:-1]])
+    table, nseg, _keep = _row_table(segments)
+    assigns = [a.contiguous() for a in assigns]
+    seg_a = (nat.C.c_void_p * max(nseg, 1))(*[a.data_ptr() or None for a in assigns])
+    rows = torch.empty((n, C), dtype=dtype, device=dev)
+    scales = torch.empty((n,), dtype=torch.float32, device=dev) if i8 else None
+    ids = torch.empty((n,), dtype=torch.int64, device=dev)
+    cell_start = torch.empty((K + 1,), dtype=torch.int32, device=dev)
+    nbytes = _lib().cor_ivf_build_workspace_bytes(n, K, C)
+    if nbytes < 0:
+        nat.check(int(nbytes), "cor_ivf_build_workspace_bytes")
+    ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    # an empty tensor has no address: the library wants non-null outputs even when it writes nothing into them
+    hold = torch.empty((16,), dtype=torch.uint8, device=dev) if n == 0 else None
+    nat.check(_lib().cor_ivf_build(*table, nseg, seg_a, C, K, nat.I8 if i8 else _DT[dtype], _p(rows) or _p(hold), _p(scales) or _p(hold),
+                                   _p(ids) or _p(hold), cell_start.data_ptr(), ws.data_ptr(), _s()), "cor_ivf_build")
+    return rows, scales, ids, cell_start
+
+
+def ivf_search(Q, rows, scales, ids, cell_start, probes, k, max_cell, split=0, return_scanned=False):
+    """Exact top-k over the rows of the probed cells (cor_ivf_search). Q f32 [Bq,C]; rows, scales, ids, cell_start: what ivf_build
+    returned (scales None for float rows); probes i64 [Bq,nprobe], what a search over the centres returns: every value outside [0, K)
+    and every repeat is ignored; 1 <= nprobe <= nat.IVF_NPROBE_MAX, 1 <= k <= 256. max_cell: the largest cell's size (a hint >= 1) and
+    split (0: automatic, else that many partial lists per query, split * k <= nat.MERGE_NMAX) only deal the work out: the result's bits
+    do not depend on them. -> (scores f32[Bq,k], idx i64[Bq,k][, scanned i32[Bq]]): the lists of the exact search of that dtype over
+    the candidate rows alone, idx being global ids, then the (-inf, -1) tail; scanned: the number of candidate rows of each query.
+    Two launches, no host synchronisation; capturable in a graph."""
+    who = "ivf_search"
+    k, max_cell, split = int(k), int(max_cell), int(split)
+    if Q.dim() != 2 or Q.dtype != torch.float32:
+        raise ValueError(f"{who}: Q must be float32 [Bq, C], got {Q.dtype} {tuple(Q.shape)}")
+    Bq, C = Q.shape
+    if C < 16 or C > 256 or C % 16 != 0:
+        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
+    i8 = rows.dtype == torch.int8
+    if rows.dim() != 2 or rows.shape[1] != C or (not i8 and rows.dtype not in _DT) or rows.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: rows must be float32 / bfloat16 / float16 / int8 [n < 2^31, {C}], got {rows.dtype} {tuple(rows.shape)}")
+    n = rows.shape[0]
+    if i8 != (scales is not None):
+        raise ValueError(f"{who}: scales go with int8 rows and with int8 rows only")
+    if i8 and (scales.dtype != torch.float32 or scales.dim() != 1 or scales.shape[0] != n):
+        raise ValueError(f"{who}: scales must be float32 [{n}], got {scales.dtype} {tuple(scales.shape)}")
+    if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] != n:
+        raise ValueError(f"{who}: ids must be int64 [{n}], got {ids.dtype} {tuple(ids.shape)}")
+    if cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not 2 <= cell_start.shape[0] <= nat.KMEANS_KMAX + 1:
+        raise ValueError(f"{who}: cell_start must be int32 [K + 1] with 1 <= K <= {nat.KMEANS_KMAX}, got {cell_start.dtype} {tuple(cell_start.shape)}")
+    K = cell_start.shape[0] - 1
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != Bq or not 1 <= probes.shape[1] <= nat.IVF_NPROBE_MAX:
+        raise ValueError(f"{who}: probes must be int64 [{Bq}, 1..{nat.IVF_NPROBE_MAX}], got {probes.dtype} {tuple(probes.shape)}")
+    nprobe = probes.shape[1]
+    if not 1 <= k <= nat.TOPK_KMAX:
+        raise ValueError(f"{who}: k must be in [1, {nat.TOPK_KMAX}], got {k}")
+    if max_cell < 1:
+        raise ValueError(f"{who}: max_cell must be at least 1, got {max_cell}")
+    if split < 0 or split * k > nat.MERGE_NMAX:
+        raise ValueError(f"{who}: split must be 0 (automatic) or give split * k <= {nat.MERGE_NMAX}, got split={split}, k={k}")
+    dev = _dev(Q, rows, scales, ids, cell_start, probes)
+    out_s = torch.empty((Bq, k), dtype=torch.float32, device=dev)
+    out_i = torch.empty((Bq, k), dtype=torch.int64, device=dev)
+    scanned = torch.empty((Bq,), dtype=torch.int32, device=dev) if return_scanned else None
+    if Bq > 0:
+        Q, rows, ids, cell_start, probes = Q.contiguous(), rows.contiguous(), ids.contiguous(), cell_start.contiguous(), probes.contiguous()
+        scales = None if scales is None else scales.contiguous()
+        Q = Q.clone() if Q.data_ptr() % 16 else Q
+        nbytes = _lib().cor_ivf_search_workspace_bytes(Bq, K, C, nprobe, k, split)
+        if nbytes < 0:
+            nat.check(int(nbytes), "cor_ivf_search_workspace_bytes")
+        ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+        hold = torch.empty((16,), dtype=torch.uint8, device=dev) if n == 0 else None   # an index without rows: every list is the tail
+        nat.check(_lib().cor_ivf_search(Q.data_ptr(), _p(rows) or _p(hold), (_p(scales) or _p(hold)) if i8 else None, nat.I8 if i8 else _DT[rows.dtype],
+                                        _p(ids) or _p(hold), cell_start.data_ptr(), K, C, Bq, probes.data_ptr(), nprobe, k, max_cell, split,
+                                        out_s.data_ptr(), out_i.data_ptr(), _p(scanned) or None, ws.data_ptr(), _s()), "cor_ivf_search")
+    return (out_s, out_i, scanned) if return_scanned else (out_s, out_i)
+
+
+_FUSE_MODES ={"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "max": nat.FUSE_MAX}
 _FUSE_NORMS = {"none": nat.FUSE_NORM_NONE, "minmax": nat.FUSE_NORM_MINMAX}
 _FUSE_MISSING = {"zero": nat.FUSE_MISSING_ZERO, "floor": nat.FUSE_MISSING_FLOOR}
 

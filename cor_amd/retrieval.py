@@ -516,6 +516,11 @@ class GalleryShard:
         n_clusters above the row count."""
         return _cluster("GalleryShard.cluster", [self] if len(self) else [], True, n_clusters, iters, init, first_id, batch)
 
+    def ivf(self, n_clusters: int, nprobe: int = 8, **cluster_kwargs):
+        """cluster(n_clusters, **cluster_kwargs), then IVFIndex.build over the result: a cell-probing index of this shard's rows with `nprobe`
+        as its default number of probes."""
+        return _ivf(self, n_clusters, nprobe, cluster_kwargs)
+
     def quantized(self):
         """The int8 copy of this shard (a QuantizedShard with the same offset), quantised on the device (ops.quantize_rows_i8): the cheap
         coarse stage of two_stage_search over these rows. This shard is left untouched. The labels and the group ids are carried (the same
@@ -645,6 +650,11 @@ class QuantizedGallery(QuantizedShard):
         """GalleryShard.cluster over the int8 rows: a row's value is float(q) * scale, the queries of the assignment are those values, so the
         result equals bitwise the clustering of dequantized()'s fp32 rows."""
         return _cluster("QuantizedGallery.cluster", [self] if len(self) else [], True, n_clusters, iters, init, first_id, batch)
+
+    def ivf(self, n_clusters: int, nprobe: int = 8, **cluster_kwargs):
+        """cluster(n_clusters, **cluster_kwargs), then IVFIndex.build over the result: a cell-probing index of the int8 rows with `nprobe`
+        as its default number of probes."""
+        return _ivf(self, n_clusters, nprobe, cluster_kwargs)
 
     def dequantized(self, dtype: torch.dtype = torch.float32):
         """A GalleryShard (same offset, labels and groups) of the rows this shard stands for, float(q) * scale in fp32, rounded again to
@@ -863,6 +873,11 @@ class GallerySet:
         that of a single fp32 GalleryShard over the concatenated widened / dequantised rows."""
         return _cluster("GallerySet.cluster", self._live(), False, n_clusters, iters, init, first_id, batch)
 
+    def ivf(self, n_clusters: int, nprobe: int = 8, **cluster_kwargs):
+        """cluster(n_clusters, **cluster_kwargs), then IVFIndex.build over the result: a cell-probing index of all segments (they must share one dtype) with `nprobe`
+        as its default number of probes."""
+        return _ivf(self, n_clusters, nprobe, cluster_kwargs)
+
     def augmented(self, m: int, alpha: int = 3, batch: int = 4096, dtype: torch.dtype | None = None):
         """Database-side augmentation of every segment with the WHOLE set as neighbours (GalleryShard.augmented(neighbours=self)): a new
         GallerySet of new segments; this set and its segments are left untouched. An int8 segment becomes a new int8 segment
@@ -884,6 +899,95 @@ class GallerySet:
         equals bitwise that of a single GalleryShard over the concatenated rows with the same lists. ValueError if the set's non-empty
         segments are not the ones the graph was built from."""
         return _rerank("GallerySet.rerank", self._live(), scores, idx, graph, k1, lam, k)
+
+
+class IVFIndex:
+    """A cell-probing index ("IVF-flat") over a clustered gallery: the rows stored cell by cell (ops.ivf_build), searched by scoring only
+    the rows of the `nprobe` cells whose centres a query scores best against (ops.ivf_search). The result is the EXACT top-k of those
+    rows, by the gallery dtype's own score and order, with global ids; at nprobe = K it is the gallery's exact search bit for bit.
+    centroids: a GalleryShard of the K centres (offset 0: its row index is the cell). rows, scales (int8 rows only, else None), ids,
+    cell_start: the cell-contiguous storage. counts: int32 [K], the cells' sizes. max_cell: the largest of them, read ONCE at build (the
+    build's one host synchronisation). nprobe: the default number of probes.
+    The index is fixed at build: no rows are added or removed, and it takes no label filter, no distinct= and no range search."""
+
+    def __init__(self, centroids, rows, scales, ids, cell_start, counts, max_cell, nprobe=8):
+        self.centroids, self.rows, self.scales, self.ids, self.cell_start = centroids, rows, scales, ids, cell_start
+        self.counts, self.max_cell, self.nprobe = counts, int(max_cell), int(nprobe)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    @property
+    def n_cells(self):
+        return len(self.centroids)
+
+    @classmethod
+    def build(cls, gallery, clustering=None, *, centroids=None, assign=None, nprobe: int = 8):
+        """gallery: a GalleryShard, a QuantizedGallery (or QuantizedShard) or a GallerySet whose segments share one dtype. clustering: what
+        gallery.cluster returned; or centroids (float32 [K,C] tensor or a GalleryShard) and assign (int32, one tensor over all rows in
+        ascending global id, or one per non-empty segment in offset order), e.g. as save_gallery carried them. A row whose assign value
+        lies outside [0, K) is not indexed. One host synchronisation (max_cell)."""
+        who = "IVFIndex.build"
+        if (clustering is None) == (centroids is None and assign is None) or (clustering is None and (centroids is None or assign is None)):
+            raise ValueError(f"{who}: pass a Clustering, or both centroids= and assign=")
+        if clustering is not None:
+            centroids, assign = clustering.centroids, clustering.assign
+        if int(nprobe) < 1:
+            raise ValueError(f"{who}: nprobe must be at least 1, got {nprobe}")
+        live = gallery._live() if isinstance(gallery, GallerySet) else ([gallery] if len(gallery) else [])
+        if not live:
+            raise ValueError(f"{who}: nothing to index (no rows)")
+        if len(live) > ops.nat.CLUSTER_SEGMAX:
+            raise ValueError(f"{who}: {len(live)} non-empty segments, one index spans at most {ops.nat.CLUSTER_SEGMAX}")
+        if len({(isinstance(sh, QuantizedShard), sh.rows.dtype) for sh in live}) != 1:
+            raise ValueError(f"{who}: the segments must share one dtype (rows are copied, never converted)")
+        dev, C = live[0].rows.device, live[0].rows.shape[1]
+        cent = centroids.rows if isinstance(centroids, GalleryShard) else centroids
+        if not isinstance(cent, torch.Tensor) or cent.dtype != torch.float32 or cent.dim() != 2 or cent.shape[1] != C or not 1 <= cent.shape[0] <= ops.nat.KMEANS_KMAX:
+            raise ValueError(f"{who}: centroids must be float32 [1..{ops.nat.KMEANS_KMAX}, {C}]")
+        if isinstance(centroids, GalleryShard) and centroids.offset != 0:
+            raise ValueError(f"{who}: the centroid shard must start at offset 0 (its row index is the cell)")
+        K = cent.shape[0]
+        if isinstance(assign, torch.Tensor):
+            if assign.dim() != 1 or assign.shape[0] != sum(len(sh) for sh in live):
+                raise ValueError(f"{who}: assign has {tuple(assign.shape)} entries, the gallery {sum(len(sh) for sh in live)} rows")
+            assign = list(torch.split(assign, [len(sh) for sh in live]))
+        assign = list(assign)
+        if len(assign) != len(live) or any(a.dim() != 1 or a.shape[0] != len(sh) or a.dtype != torch.int32 for a, sh in zip(assign, live)):
+            raise ValueError(f"{who}: assign must be int32, one entry per row (one tensor per non-empty segment in offset order)")
+        table = [(sh.rows, sh.scales, sh.offset) if isinstance(sh, QuantizedShard) else (sh.rows, sh.offset) for sh in live]
+        with _on(dev):
+            rows, scales, ids, cell_start = ops.ivf_build(table, [a.to(dev) for a in assign], K)
+            counts = cell_start[1:] - cell_start[:-1]
+            max_cell = max(int(counts.max().item()), 1)                  # the build's one synchronisation
+            centres = centroids if isinstance(centroids, GalleryShard) and centroids.rows.device == dev else GalleryShard(cent.to(dev), offset=0)
+        return cls(centres, rows, scales, ids, cell_start, counts, max_cell, nprobe)
+
+    def search(self, queries: torch.Tensor, k: int, nprobe: int | None = None, return_scanned: bool = False):
+        """queries f32[Bq,C] -> (scores f32[Bq,k], global idx i64[Bq,k][, scanned i32[Bq]]) on the GPU; 1 <= k <= 256. The probes are
+        centroids.search(queries, min(nprobe, K)) (the exact search; nprobe defaults to the index's, at most 256), then ops.ivf_search
+        scores the rows of those cells: the exact top-k among them, then the (-inf, -1) tail. scanned: how many rows each query scored.
+        Nothing leaves the device and the host is not waited for."""
+        np_ = self.nprobe if nprobe is None else int(nprobe)
+        if np_ < 1:
+            raise ValueError(f"IVFIndex.search: nprobe must be at least 1, got {nprobe}")
+        if not 1 <= int(k) <= ops.nat.TOPK_KMAX:
+            raise ValueError(f"IVFIndex.search: k must be in [1, {ops.nat.TOPK_KMAX}], got {k}")
+        np_ = min(np_, self.n_cells, ops.nat.IVF_NPROBE_MAX)
+        dev = self.rows.device
+        q = queries.reshape(-1, queries.shape[-1]).to(dev, torch.float32).contiguous()
+        if q.shape[0] == 0:
+            s, i = _missing_lists(0, int(k), dev)
+            return (s, i, torch.empty((0,), dtype=torch.int32, device=dev)) if return_scanned else (s, i)
+        probes = self.centroids.search(q, np_)[1]
+        with _on(dev):
+            return ops.ivf_search(q, self.rows, self.scales, self.ids, self.cell_start, probes, int(k), self.max_cell,
+                                  return_scanned=return_scanned)
+
+
+def _ivf(gallery, n_clusters, nprobe, cluster_kwargs):
+    """.ivf of the gallery classes: cluster, then build."""
+    return IVFIndex.build(gallery, gallery.cluster(n_clusters, **cluster_kwargs), nprobe=nprobe)
 
 
 def _with_lists(shard):

@@ -959,6 +959,74 @@ int cor_kmeans_update(const void* const* seg_rows, const float* const* seg_scale
                       const int* seg_dtype, int nseg, const int* const* seg_assign, const float* const* seg_score, int C, int K,
                       const float* prev, float* out_centroids, int* out_count, float* out_score_sum, void* workspace, void* stream);
 
+/* Cell-probing search ("IVF-flat", Sivic & Zisserman ICCV 2003; Jegou, Douze & Schmid TPAMI 2011 without the product quantiser): the rows
+ * of a gallery are laid out cell by cell after a clustering, a query names the cells whose centres it scores best against (its PROBES: an
+ * exact search over the centres, made by the caller) and only those cells' rows are scored. The result is the EXACT top-k of those rows.
+ * Both calls make no device allocation, no host-to-device copy and no host synchronisation, run on `stream` and can be captured in a graph.
+ *
+ * cor_ivf_build: a segment table and a per-row cell id -> cell-contiguous storage. The table is that of cor_kmeans_update (seg_rows /
+ * seg_scale / seg_offset / seg_n / seg_dtype, nseg <= COR_CLUSTER_SEGMAX, pairwise disjoint id ranges) and seg_assign as it takes it: a HOST
+ * array of nseg DEVICE pointers, int32 [seg_n[s]]. dtype: COR_F32 / COR_BF16 / COR_F16 / COR_I8, the dtype of the index AND of every
+ * segment: rows are copied bit for bit, never converted. out_rows [n_total,C] in dtype (16-byte aligned), out_scale f32 [n_total] (required
+ * for COR_I8, ignored otherwise), out_ids i64 [n_total], out_cell_start i32 [K+1].
+ * Definition. The members of cell c are the rows with assign == c in ASCENDING GLOBAL ID (the member order of cor_kmeans_update). A row
+ * whose assign value lies outside [0, K) (-1, K, INT_MIN) is in no cell and is not indexed; nothing but its assign entry is read.
+ * cell_start[c] = the number of members of the cells < c; cell_start[K] = the number of indexed rows. The member with ordinal j of cell c
+ * goes to slot cell_start[c] + j: its stored row bits, its scale (COR_I8) and its global id. Slots >= cell_start[K] are not written. The
+ * result does not depend on how the rows are cut into segments or on the segments' order. n_total == 0 (also nseg == 0) is legal: every
+ * entry of cell_start is 0.
+ * Error order; all of it is decided before any HIP call. (1) COR_EINVAL: a null out_rows / out_ids / out_cell_start / workspace, a null
+ * out_scale with dtype COR_I8; nseg < 0, K < 1, C < 1; a null segment array with nseg > 0. (2) COR_ENOSUPPORT: nseg > COR_CLUSTER_SEGMAX.
+ * (3) COR_EINVAL: a negative seg_n; for a segment with rows a null seg_rows[s], scale or seg_assign[s]. (4) COR_ENOSUPPORT: K >
+ * COR_KMEANS_KMAX, C > 256 or C % 16 != 0, n_total >= 2^31, an unknown seg_dtype; then an unknown dtype, then a segment (an empty one
+ * included) of another dtype. (5) COR_EINVAL: out_rows or a segment's rows not 16-byte aligned, workspace not 256-byte aligned.
+ * workspace >= cor_ivf_build_workspace_bytes(n_total, K, C) bytes (or COR_EINVAL for n_total < 0, K < 1, C < 1, then COR_ENOSUPPORT as (4)).
+ * 5 launches: the stable counting sort of cor_kmeans_update (tile keys, column scan, scan, place; no atomics), then a copy in which one
+ * wave moves a row with one coalesced load and one coalesced store.
+ *
+ * cor_ivf_search: Q f32 [Bq,C]; the index: rows [n,C] in dtype, scale f32 [n] (COR_I8; else ignored), ids i64 [n], cell_start i32 [K+1] as
+ * cor_ivf_build wrote them; probes i64 [Bq,nprobe] contiguous, exactly what a search over the centres returns, 1 <= nprobe <=
+ * COR_IVF_NPROBE_MAX; 1 <= k <= COR_TOPK_KMAX. out_scores f32 [Bq,k], out_idx i64 [Bq,k], out_scanned i32 [Bq] or NULL.
+ * Definition. P(b) = the set of distinct values c in probes[b,:] with 0 <= c < K; every other value is ignored (-1 tails, repeats,
+ * arbitrary 64-bit values: no address is formed from a probe that has not passed the range test). Cand(b) = the slots of the cells in
+ * P(b); out_scanned[b] = |Cand(b)|.
+ *   SCORE, float dtypes: the fmaf chain of cor_similarity_topk (acc = +0; for chunk c = 0 .. C/8 - 1 and i = 0 .. 3: acc = fmaf(x[8c+i],
+ *   q[8c+i], acc), then acc = fmaf(x[8c+4+i], q[8c+4+i], acc): oracle/c/sim_chain.c), x the stored values widened exactly, q the query,
+ *   rounded to the row dtype and widened back for 16-bit rows. COR_I8: the score of cor_similarity_topk_i8: the query quantised inside the
+ *   call by the rule of cor_quantize_rows_i8, d the int32 dot product (exact), score = ((float)d * qscale) * scale[slot], two separately
+ *   rounded multiplies.
+ *   ORDER: that dtype's exact search with the global id ids[slot] in place of the row index. Float dtypes: score descending as floats
+ *   (-0.0 and +0.0 tie), then id ascending; score bits are carried through unchanged. COR_I8: the order-preserving key of the score's BITS
+ *   descending (+0.0 above -0.0), then id ascending. The first k entries go out, then the (-inf, -1) tail.
+ * Equivalently: the lists equal bit for bit those of cor_similarity_topk / cor_similarity_topk_i8 run over a gallery that holds exactly
+ * the candidate rows in ascending global id, indices mapped back to global ids; with every cell probed this is the exact search of the
+ * indexed rows. Preconditions: finite rows; the ids of the index are pairwise distinct.
+ * max_cell (>= 1: the largest cell's size, a HINT) and split (0: automatic; > 0: that many partial lists per query) change only how the work
+ * is dealt out: any max_cell >= 1 and any legal split give the same bits. A cell larger than max_cell is still scanned to its end.
+ * Error order; all of it is decided before any HIP call. (1) COR_EINVAL: a null Q / rows / ids / cell_start / probes / out_scores /
+ * out_idx / workspace, a null scale with dtype COR_I8; Bq < 0; K, C, k, nprobe or max_cell < 1; split < 0. (2) COR_ENOSUPPORT: k >
+ * COR_TOPK_KMAX, nprobe > COR_IVF_NPROBE_MAX, K > COR_KMEANS_KMAX, C > 256 or C % 16 != 0; split * k > COR_MERGE_NMAX; an unknown dtype.
+ * (3) COR_EINVAL: Q or rows not 16-byte aligned, workspace not 256-byte aligned. Bq == 0 is a successful no-op. workspace >=
+ * cor_ivf_search_workspace_bytes(Bq, K, C, nprobe, k, split) bytes, the same `split` as the call's (the query reports (1) and (2) as
+ * negative values; it covers every max_cell).
+ * 2 launches. Scan: the work units of a query are (probe j, slice s of its cell), S = ceil(max_cell / 512) slices per cell, slice s
+ * walking the tiles s, s + S, ... of 512 slots; they are dealt round-robin to P blocks per query (automatic: P = min(ceil(1024 / Bq),
+ * COR_MERGE_NMAX / k, the number of units)). A block keeps the query in LDS, a thread scores two rows at a time, reading each in whole
+ * 128-byte lines, with plain interleaved fmaf chains (int8: 4-way integer dot products), and the block carries ONE running top-k in LDS:
+ * after the first k rows the k-th key is a threshold, only rows at or above it are appended, and the buffer is sorted again (bitonic
+ * network, ties by the id) when a tile might not fit. A probe is dropped inside the kernel if an earlier probe names the same cell.
+ * Every block writes one partial list of k. Finish: one block per query ranks the P lists by the same order. (score, id) is a total
+ * order on a query's candidates, so P, S and the order of the appends cannot show in the result. */
+#define COR_IVF_NPROBE_MAX 256
+long cor_ivf_build_workspace_bytes(long n_total, int K, int C);
+int cor_ivf_build(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n,
+                  const int* seg_dtype, int nseg, const int* const* seg_assign, int C, int K, int dtype, void* out_rows, float* out_scale,
+                  long long* out_ids, int* out_cell_start, void* workspace, void* stream);
+long cor_ivf_search_workspace_bytes(int Bq, int K, int C, int nprobe, int k, int split);
+int cor_ivf_search(const float* Q, const void* rows, const float* scale, int dtype, const long long* ids, const int* cell_start, int K, int C,
+                   int Bq, const long long* probes, int nprobe, int k, int max_cell, int split, float* out_scores, long long* out_idx,
+                   int* out_scanned, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
