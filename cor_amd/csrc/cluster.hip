@@ -1,7 +1,8 @@
 // cor_amd — clustering of a gallery: farthest-point seeding (cor_kmeans_seed) and the centre step of spherical k-means (cor_kmeans_update).
 // Contract and both definitions, fixed to the bit: include/cor_amd.h. The assignment step is the existing search and is not in this file.
 //
-// Rows. Both calls take the by-value segment table of cor_diversify_mmr (member_sort.h: KmSegs, flat positions, km_locate). The order of
+// Rows. Both calls take the by-value segment table of segrows.h (SegRowsAssign; its row address, loaders and norm tree too) through the
+// flat positions of member_sort.h (km_locate). The order of
 // the flat positions: table order for the seeding (its tie rule reads the global id), ASCENDING SEGMENT OFFSET for the update, so that
 // there ascending p is ascending global id. n_total < 2^31.
 //
@@ -16,11 +17,11 @@
 //   changes the winner. The last step has no scoring and no pick.
 // cor_kmeans_update: 6 launches.
 //   keys, columns, scan, place: the member lists by the stable counting sort of member_sort.h, shared with cor_ivf_build. No atomics.
-//   chunks  one WAVE per (cluster, chunk of 256 members), found by binary search in the chunk bases; expand.hip's layout: lane l owns
+//   chunks  one WAVE per (cluster, chunk of 256 members), found by binary search in the chunk bases; segrows.h's lane layout: lane l owns
 //           channels [4l, 4l + 4), a member row is ONE coalesced wave load, 64 members are looked up at a time (lane j: member j) and
 //           walked in member order 8 rows at a time, all 8 loads issued before the first add. p_j = +0, then p_j = p_j + x. The members'
 //           scores are summed the same way from the lane that looked the member up. Partial rows go to the workspace.
-//   finish  one wave per cluster: v = +0, v = v + p_j for j ascending, the norm tree of cor_expand_queries, v / d; an empty cluster
+//   finish  one wave per cluster: v = +0, v = v + p_j for j ascending, the norm tree (seg_lane_norm), v / d; an empty cluster
 //           copies its row of prev (or writes +0).
 // Arithmetic: `#pragma clang fp contract(off)` holds for the whole file: every + * / is one separately rounded fp32 operation, the
 // chain's explicit fmaf stays an fma; a / b and __builtin_sqrtf are correctly rounded (no fast-math flag for this file in the Makefile).
@@ -33,9 +34,6 @@ namespace {
 constexpr int KM_SEED_BLOCKS = 4096;           // most blocks (and partials) of a seeding step
 constexpr int KM_WPB = 4;                      // waves per block of the chunk and finish kernels
 constexpr unsigned KM_CHOSEN = 0x7fc00000u;    // best[] of a chosen row: a NaN
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define KM_GLOBAL __attribute__((address_space(1)))
 
 // ---------------------------------------------------------------------------------------------------------------- seeding
 
@@ -60,18 +58,21 @@ __device__ __forceinline__ bool km_before(float av, long long aid, int af, float
   return aid < bid;
 }
 
-// elements [8 c, 8 c + 8) of a row, as fp32 values (the dtype may differ between the threads of a wave); rows are 16-byte aligned
+// The seeding kernels keep their own spelling of segrows.h's seg_row and seg_load8 (here the 16-bit load is shared by bf16 and fp16).
+// With seg_load8 as the header has it, and seg_row in km_set_cur, all three compiled to other code and cor_kmeans_seed measured 2.0 %
+// slower at 98 304 bf16 rows, K = 8, against a parent spread of 0.2 % (profiles/row_tables_ab_shared.jsonl); with seg_row in
+// km_seed_step and this loader, 2.2 % (profiles/row_tables_ab_common16.jsonl). DESIGN.md has both runs
 __device__ __forceinline__ void km_load8(u64 row, int dt, float rs, int c, float (&g)[8]) {
   if (dt == COR_F32) {
-    const u32x4 x = *(const KM_GLOBAL u32x4*)(row + 32u * c), y = *(const KM_GLOBAL u32x4*)(row + 32u * c + 16u);
+    const u32x4 x = *(const SEG_GLOBAL u32x4*)(row + 32u * c), y = *(const SEG_GLOBAL u32x4*)(row + 32u * c + 16u);
 #pragma unroll
     for (int e = 0; e < 4; ++e) { g[e] = __uint_as_float(x[e]); g[4 + e] = __uint_as_float(y[e]); }
   } else if (dt == COR_I8) {
-    const u32x2 x = *(const KM_GLOBAL u32x2*)(row + 8u * c);
+    const u32x2 x = *(const SEG_GLOBAL u32x2*)(row + 8u * c);
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = (float)(int)(signed char)(x[e >> 2] >> (8 * (e & 3))) * rs;
   } else {
-    const u32x4 x = *(const KM_GLOBAL u32x4*)(row + 16u * c);
+    const u32x4 x = *(const SEG_GLOBAL u32x4*)(row + 16u * c);
     if (dt == COR_BF16) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) { g[2 * e] = __uint_as_float(x[e] << 16); g[2 * e + 1] = __uint_as_float(x[e] & 0xffff0000u); }
@@ -82,11 +83,11 @@ __device__ __forceinline__ void km_load8(u64 row, int dt, float rs, int c, float
   }
 }
 
-__device__ __forceinline__ void km_set_cur(const KmSegs& segs, int nseg, int C, long long p, KmCur* cur) {
+__device__ __forceinline__ void km_set_cur(const SegRowsAssign& segs, int nseg, int C, long long p, KmCur* cur) {
   km_locate(segs, nseg, p, [&](int s, int local) {
     const int dt = segs.dt[s];
     KmCur c;
-    c.row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
+    c.row = (u64)segs.rows[s] + (u64)local * (u64)(C * seg_esize(dt));
     c.id = segs.off[s] + local;
     c.rs = dt == COR_I8 ? segs.scale[s][local] : 0.f;
     c.dt = dt;
@@ -94,14 +95,14 @@ __device__ __forceinline__ void km_set_cur(const KmSegs& segs, int nseg, int C, 
   });
 }
 
-__global__ __launch_bounds__(256) void km_seed_init(const KmSegs segs, int nseg, long long n, int C, long long first, unsigned* __restrict__ best,
+__global__ __launch_bounds__(256) void km_seed_init(const SegRowsAssign segs, int nseg, long long n, int C, long long first, unsigned* __restrict__ best,
                                                     KmCur* __restrict__ cur) {
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256)
     best[p] = p == first ? KM_CHOSEN : RANK_NEG_INF;
   if (blockIdx.x == 0 && threadIdx.x == 0) km_set_cur(segs, nseg, C, first, cur);
 }
 
-__global__ __launch_bounds__(256) void km_seed_step(const KmSegs segs, int nseg, long long n, int C, float* __restrict__ best,
+__global__ __launch_bounds__(256) void km_seed_step(const SegRowsAssign segs, int nseg, long long n, int C, float* __restrict__ best,
                                                     const KmCur* __restrict__ cur, KmPart* __restrict__ part, int t, int score,
                                                     long long* __restrict__ out_ids, float* __restrict__ out_centroids) {
   __shared__ __align__(16) float s_q[KM_CMAX];
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256) void km_seed_step(const KmSegs segs, int nseg,
     long long id = 0;
     const bool hit = km_locate(segs, nseg, p, [&](int s, int local) {    // the only place a row address is formed
       dt = segs.dt[s];
-      row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
+      row = (u64)segs.rows[s] + (u64)local * (u64)(C * seg_esize(dt));
       id = segs.off[s] + local;
       if (dt == COR_I8) rs = segs.scale[s][local];
     });
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void km_seed_step(const KmSegs segs, int nseg,
   }
 }
 
-__global__ __launch_bounds__(256) void km_seed_pick(const KmSegs segs, int nseg, int C, const KmPart* __restrict__ part, int nparts,
+__global__ __launch_bounds__(256) void km_seed_pick(const SegRowsAssign segs, int nseg, int C, const KmPart* __restrict__ part, int nparts,
                                                     unsigned* __restrict__ best, KmCur* __restrict__ cur) {
   __shared__ KmPart s_part[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -212,72 +213,8 @@ __global__ __launch_bounds__(256) void km_seed_pick(const KmSegs segs, int nseg,
 
 // ---------------------------------------------------------------------------------------------------------------- update
 
-// the lane's four channels of one row, as stored: expand.hip's ex_load. ESZ = 4 / 2 / 1: every segment has rows of that element size;
-// ESZ = -1: sizes differ, a dword, a second dword and an 8-byte load at offsets chosen by the dtype, every one inside the row, no
-// branch around a load
-template <int ESZ> __device__ __forceinline__ u32x4 km_load(u64 row, int c0, int dt) {
-  u32x4 r = {0u, 0u, 0u, 0u};
-  if constexpr (ESZ == 4) {
-    r = *(const KM_GLOBAL u32x4*)(row + 4u * c0);
-  } else if constexpr (ESZ == 1) {
-    r[0] = *(const KM_GLOBAL unsigned*)(row + (unsigned)c0);
-  } else if constexpr (ESZ == 2) {
-    const u32x2 a = *(const KM_GLOBAL u32x2*)(row + 2u * c0);
-    r[0] = a[0]; r[1] = a[1];
-  } else {
-    const bool wide = dt == COR_F32, narrow = dt == COR_I8;
-    const unsigned o = wide ? 4u * c0 : narrow ? (unsigned)c0 : 2u * c0;
-    const unsigned a = *(const KM_GLOBAL unsigned*)(row + o), b = *(const KM_GLOBAL unsigned*)(row + o + (narrow ? 0u : 4u));
-    const u32x2 c = *(const KM_GLOBAL u32x2*)(row + (wide ? o + 8u : narrow ? (unsigned)c0 & ~7u : o));
-    r[0] = a; r[1] = b; r[2] = c[0]; r[3] = c[1];
-  }
-  return r;
-}
-// stored values -> fp32, exactly (dt is wave-uniform); an int8 value is (float)q * rs, one rounded multiply
-template <int ESZ> __device__ __forceinline__ void km_widen(const u32x4 r, int dt, float rs, float (&x)[4]) {
-  if (ESZ == 1 || (ESZ == -1 && dt == COR_I8)) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = (float)(int)(signed char)(r[0] >> (8 * e)) * rs;
-  } else if (ESZ == 4 || (ESZ == -1 && dt == COR_F32)) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(r[e]);
-  } else if (dt == COR_BF16) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = __uint_as_float(e & 1 ? r[e >> 1] & 0xffff0000u : r[e >> 1] << 16);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(e & 1 ? r[e >> 1] >> 16 : r[e >> 1] & 0xffffu));
-  }
-}
-
-// the next U members of `mask` (lowest bit first = member order): all U rows are requested before the first add
-template <int ESZ, int U>
-__device__ __forceinline__ void km_group(u64& mask, unsigned plo, unsigned phi, float sc, float rs, int dt, int c0, float (&v)[4], float& ps) {
-  u32x4 raw[U];
-  float cu[U], su[U];
-  int du[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int j = __builtin_ctzll(mask);                                 // mask has at least U bits set (the caller counted them)
-    mask &= mask - 1;
-    const u64 row = ((u64)(unsigned)__builtin_amdgcn_readlane((int)phi, j) << 32) | (unsigned)__builtin_amdgcn_readlane((int)plo, j);
-    cu[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sc), j));
-    du[u] = __builtin_amdgcn_readlane(dt, j);
-    su[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rs), j));
-    raw[u] = km_load<ESZ>(row, c0, du[u]);
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    float x[4];
-    km_widen<ESZ>(raw[u], du[u], su[u], x);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = v[e] + x[e];
-    ps = ps + cu[u];
-  }
-}
-
 template <int ESZ>
-__global__ __launch_bounds__(64 * KM_WPB) void km_chunk_sum(const KmSegs segs, int nseg, int K, int C, int with_scores, const int* __restrict__ base,
+__global__ __launch_bounds__(64 * KM_WPB) void km_chunk_sum(const SegRowsAssign segs, int nseg, int K, int C, int with_scores, const int* __restrict__ base,
                                                             const int* __restrict__ cb, const int* __restrict__ mem, float* __restrict__ P,
                                                             float* __restrict__ PS) {
   const int lane = threadIdx.x & 63;
@@ -303,18 +240,15 @@ __global__ __launch_bounds__(64 * KM_WPB) void km_chunk_sum(const KmSegs segs, i
     bool present = false;
     if (j0 + lane < m1)
       present = km_locate(segs, nseg, mem[j0 + lane], [&](int s, int local) {   // the only place a row address is formed
-        dt = segs.dt[s];
-        row = (u64)segs.rows[s] + (u64)local * (u64)(C * km_esize(dt));
-        if (dt == COR_I8) rs = segs.scale[s][local];
+        seg_row(segs, s, local, C, dt, row, rs);
         if (with_scores) sc = segs.score[s][local];
       });
-    u64 mask = __ballot(present);
-    int cnt = __builtin_popcountll(mask);
-    const unsigned plo = (unsigned)row, phi = (unsigned)(row >> 32);
-    for (; cnt >= 8; cnt -= 8) km_group<ESZ, 8>(mask, plo, phi, sc, rs, dt, c0, v, ps);
-    if (cnt & 4) km_group<ESZ, 4>(mask, plo, phi, sc, rs, dt, c0, v, ps);
-    if (cnt & 2) km_group<ESZ, 2>(mask, plo, phi, sc, rs, dt, c0, v, ps);
-    if (cnt & 1) km_group<ESZ, 1>(mask, plo, phi, sc, rs, dt, c0, v, ps);
+    // the members in member order, 8 rows at a time: p = p + x, and the member's score from the lane that looked it up
+    seg_lane_walk<ESZ>(present, row, sc, rs, dt, c0, [&](float scj, const float (&x)[4]) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = v[e] + x[e];
+      ps = ps + scj;
+    });
   }
   if (active) {
     f32x4 y;
@@ -348,20 +282,7 @@ __global__ __launch_bounds__(64 * KM_WPB) void km_finish(int K, int C, const int
       for (int e = 0; e < 4; ++e) v[e] = v[e] + x[e];
       ss = ss + PS[j];
     }
-    // the norm: the stride-halving tree over 256 channel slots (expand.hip, step 3)
-    float s[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s[e] = active ? v[e] * v[e] : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[e] = s[e] + __shfl_xor(s[e], o, 64);
-    }
-    s[0] = s[0] + s[2];
-    s[1] = s[1] + s[3];
-    s[0] = s[0] + s[1];
-    const float s0 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s[0])));
-    const float d = fmaxf(__builtin_sqrtf(s0), 1e-12f);
+    const float d = seg_lane_norm(v, active);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = v[e] / d;
   }
@@ -413,10 +334,10 @@ extern "C" int cor_kmeans_seed(const void* const* seg_rows, const float* const* 
                                const int* seg_dtype, int nseg, int C, int K, long long first_id, long long* out_ids, float* out_centroids,
                                void* workspace, void* stream) {
   if (!out_ids || !out_centroids || !workspace) return COR_EINVAL;
-  KmSegs segs;
+  SegRowsAssign segs;
   int live = 0, seen = 0;
   long long n = 0;
-  if (const int rc = km_table(seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, nullptr, false, nullptr, K, C, segs, live, n, seen)) return rc;
+  if (const int rc = km_table({seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, true}, K, C, segs, live, n, seen)) return rc;
   if (K > n) return COR_EINVAL;
   long long first = -1, base = 0;
   for (int s = 0; s < live; ++s) {
@@ -447,11 +368,11 @@ extern "C" int cor_kmeans_update(const void* const* seg_rows, const float* const
                                  const int* seg_dtype, int nseg, const int* const* seg_assign, const float* const* seg_score, int C, int K,
                                  const float* prev, float* out_centroids, int* out_count, float* out_score_sum, void* workspace, void* stream) {
   if (!out_centroids || !out_count || !workspace || (seg_score != nullptr) != (out_score_sum != nullptr)) return COR_EINVAL;
-  KmSegs t;
+  SegRowsAssign t;
   int live = 0, seen = 0;
   long long n = 0;
-  if (const int rc = km_table(seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, seg_assign, true, seg_score, K, C, t, live, n, seen)) return rc;
-  const KmSegs segs = km_by_offset(t, live);                             // ascending flat position is ascending global id
+  if (const int rc = km_table({seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, true, seg_assign, true, seg_score}, K, C, t, live, n, seen)) return rc;
+  const SegRowsAssign segs = km_by_offset(t, live);                             // ascending flat position is ascending global id
 
   const KmLayout L = km_layout(n, K, C);
   unsigned char* ws = (unsigned char*)workspace;

@@ -37,32 +37,21 @@
 // 1.0f / sqrtf(d) must be the two correctly rounded IEEE operations: hipcc's default for HIP code is (the expansion around v_sqrt_f32, and
 // v_div_scale / v_div_fmas / v_div_fixup). NO FLAG MAY CHANGE THAT: this file is built without -ffast-math, -fno-hip-fp32-correctly-
 // rounded-divide-sqrt, -fapprox-func or any denormal-flushing option (cor_amd/csrc/Makefile gives it no FLAGS_ line).
-// The row loaders below restate diversify.hip's (that file is left as it is).
-#include "ranklist.h"
+// The segment table, the row address and the row loader are segrows.h's, shared with the other calls that read gallery rows.
+#include "segrows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int DF_SEGMAX = COR_DIFFUSE_SEGMAX;
 constexpr int DF_NMAX = COR_DIFFUSE_NMAX;
 constexpr int DF_KDMAX = COR_DIFFUSE_KDMAX;
 constexpr int DF_CMAX = 256;                   // embedding width limit of the searches
 constexpr int DF_TP = 32;                      // partner rows per tile = chain accumulators per thread
 constexpr int DF_KD_SMALL = 8;                // kernel variants: kd <= 8 keeps a thread's neighbour list in 8 + 8 registers, a larger kd in LDS
 constexpr int DF_JB = 4;                      // pairs of partner rows whose chains a thread advances side by side
-constexpr int DF_MIXED = -1;                   // kernel variant: the dtype is read per candidate
 static_assert(DF_NMAX <= 256, "neighbour indices are stored as bytes and a block has one thread per candidate");
 static_assert(DF_NMAX <= COR_MERGE_NMAX, "the rank keys carry the list position");
-
-// the segment table, passed BY VALUE in the kernel argument block (512 B): no device allocation, no copy, nothing to keep alive
-struct DfSegs {
-  const unsigned char* rows[DF_SEGMAX];
-  long long off[DF_SEGMAX];
-  int n[DF_SEGMAX];
-  int dt[DF_SEGMAX];
-  const float* scale[DF_SEGMAX];
-};
 
 // the scalars of the definition
 struct DfParams {
@@ -70,34 +59,7 @@ struct DfParams {
   float alpha;
 };
 
-__device__ __forceinline__ int df_esize(int dt) { return dt == COR_F32 ? 4 : dt == COR_I8 ? 1 : 2; }
-
-// elements [8 s, 8 s + 8) of a row in global memory, as fp32 values: fp32 as stored, bf16 / fp16 widened exactly, int8 (float)q * rs (one
-// rounded multiply). Two 16-byte loads (fp32), one (16-bit) or one 8-byte load (int8); rows are 16-byte aligned and C % 16 == 0. DT >= 0:
-// the dtype of every row; DF_MIXED: `dt` decides. The address travels as an integer and the loads name the GLOBAL address space
-#define DF_GLOBAL __attribute__((address_space(1)))
-typedef unsigned int df_u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int DT> __device__ __forceinline__ void df_load8(u64 row, int dt, float rs, int s, float (&g)[8]) {
-  const int d = DT >= 0 ? DT : dt;
-  if (d == COR_F32) {
-    const u32x4 x = *(const DF_GLOBAL u32x4*)(row + 32u * s), y = *(const DF_GLOBAL u32x4*)(row + 32u * s + 16u);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { g[e] = __uint_as_float(x[e]); g[4 + e] = __uint_as_float(y[e]); }
-  } else if (d == COR_I8) {
-    const df_u32x2 x = *(const DF_GLOBAL df_u32x2*)(row + 8u * s);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)(int)(signed char)(x[e >> 2] >> (8 * (e & 3))) * rs;
-  } else if (d == COR_BF16) {
-    const u32x4 x = *(const DF_GLOBAL u32x4*)(row + 16u * s);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { g[2 * e] = __uint_as_float(x[e] << 16); g[2 * e + 1] = __uint_as_float(x[e] & 0xffff0000u); }
-  } else {
-    const u32x4 x = *(const DF_GLOBAL u32x4*)(row + 16u * s);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(e & 1 ? x[e >> 1] >> 16 : x[e >> 1] & 0xffffu));
-  }
-}
 
 // pw(v): +0 unless v > 0, else v multiplied gamma - 1 times by v, each product rounded
 __device__ __forceinline__ float df_pw(float v, int gamma) {
@@ -113,7 +75,7 @@ __host__ __device__ inline size_t df_lds_bytes(int T, int C, int kd) {
 }
 
 template <int DT, int KD>
-__global__ __launch_bounds__(256) void rerank_diffusion_kernel(const DfSegs segs, int nseg, const float* __restrict__ scores,
+__global__ __launch_bounds__(256) void rerank_diffusion_kernel(const SegRowsSq segs, int nseg, const float* __restrict__ scores,
                                                                const long long* __restrict__ idx, const DfParams P,
                                                                unsigned* __restrict__ out_scores, long long* __restrict__ out_idx,
                                                                int* __restrict__ out_pos) {
@@ -147,11 +109,7 @@ __global__ __launch_bounds__(256) void rerank_diffusion_kernel(const DfSegs segs
     float sr = 0.f;
     bool present = false;
     if (tid < kin)
-      present = seg_lookup(segs, nseg, ids[tid], [&](int sg, u64 local) {      // the only place a row address is formed
-        dt = segs.dt[sg];
-        r = (u64)segs.rows[sg] + local * (u64)(C * df_esize(dt));
-        if (dt == COR_I8) sr = segs.scale[sg][local];
-      });
+      present = seg_lookup(segs, nseg, ids[tid], [&](int sg, u64 local) { seg_row(segs, sg, local, C, dt, r, sr); });   // the only place a row address is formed
     const unsigned long long bal = __ballot(present);
     if (lane == 0) s_wcount[wave] = __popcll(bal);
     __syncthreads();
@@ -189,7 +147,7 @@ __global__ __launch_bounds__(256) void rerank_diffusion_kernel(const DfSegs segs
       for (int e = tid; e < DF_TP * chunks; e += T) {
         const int s = e / DF_TP, r = e - s * DF_TP, q = t0 + r;      // (DF_TP is a power of two)
         float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (q < n) df_load8<DT>(e_row[q], e_dt[q], e_rs[q], s, g);  // rows past n: zeros, never used
+        if (q < n) seg_load8<DT>(e_row[q], e_dt[q], e_rs[q], s, g);  // rows past n: zeros, never used
         // tile[s][r / 2][t][r % 2], t the place of the element in the chain's order (8 c + i, then 8 c + 4 + i): float offset 16 (s 16 + r / 2) + 2 t + r % 2
         float* dst = tile + 16 * (s * (DF_TP / 2) + (r >> 1)) + (r & 1);
 #pragma unroll
@@ -204,10 +162,10 @@ __global__ __launch_bounds__(256) void rerank_diffusion_kernel(const DfSegs segs
       for (int j = 0; j < DF_TP / 2; ++j) acc2[j] = f32x2{0.f, 0.f};
       if (act) {
         float g[8];
-        df_load8<DT>(myrow, mydt, myrs, 0, g);
+        seg_load8<DT>(myrow, mydt, myrs, 0, g);
         for (int c = 0; c < chunks; ++c) {
           float gn[8];                                               // the next chunk of the own row is on its way while this one is used
-          df_load8<DT>(myrow, mydt, myrs, c + 1 < chunks ? c + 1 : c, gn);
+          seg_load8<DT>(myrow, mydt, myrs, c + 1 < chunks ? c + 1 : c, gn);
           const f32x4* tq = (const f32x4*)tile + 4 * (DF_TP / 2) * c;
 #pragma unroll
           for (int jb = 0; jb < DF_TP / 2; jb += DF_JB) {            // DF_JB pairs of partners at a time: independent chains side by side
@@ -352,7 +310,7 @@ __global__ __launch_bounds__(256) void rerank_diffusion_kernel(const DfSegs segs
 }
 
 template <int DT>
-int launch_diffusion(const DfSegs& segs, int nseg, const float* scores, const long long* idx, int Bq, const DfParams& P, float* out_scores,
+int launch_diffusion(const SegRowsSq& segs, int nseg, const float* scores, const long long* idx, int Bq, const DfParams& P, float* out_scores,
                      long long* out_idx, int* out_pos, hipStream_t st) {
   const int npad = next_pow2(P.kin);
   const int threads = npad < 64 ? 64 : npad;                         // 64, 128 or 256: one thread per candidate
@@ -380,34 +338,16 @@ extern "C" int cor_rerank_diffusion(const void* const* seg_rows, const float* co
                                     void* stream) {
   if (!scores || !idx || !out_scores || !out_idx || Bq < 0 || kin < 1 || k < 1 || kd < 1 || kq < 1 || gamma < 1 || iters < 1 || nseg < 0 || C < 1)
     return COR_EINVAL;
-  if (nseg > 0 && (!seg_rows || !seg_offset || !seg_n || !seg_dtype)) return COR_EINVAL;
   if (!(alpha >= 0.f && alpha < 1.f)) return COR_EINVAL;                 // (a NaN alpha fails both comparisons)
-  if (nseg > DF_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
-  for (int s = 0; s < nseg; ++s)
-    if (seg_entry_bad(seg_n[s], seg_rows[s] && (seg_dtype[s] != COR_I8 || (seg_scale && seg_scale[s])))) return COR_EINVAL;
+  const SegArrays t = {seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, true};
+  if (const int rc = seg_table_check(t)) return rc;
   if (kin > DF_NMAX || kd > DF_KDMAX || gamma > 4 || iters > 64 || k > COR_TOPK_KMAX || C > DF_CMAX || C % 16 != 0) return COR_ENOSUPPORT;
-  DfSegs segs = {};
-  int seen = 0;                                                          // bit dt: a non-empty segment of that dtype
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_dtype[s] != COR_F32 && seg_dtype[s] != COR_BF16 && seg_dtype[s] != COR_F16 && seg_dtype[s] != COR_I8) return COR_ENOSUPPORT;
-    segs.rows[s] = (const unsigned char*)seg_rows[s];
-    segs.off[s] = seg_offset[s];
-    segs.n[s] = seg_n[s];
-    segs.dt[s] = seg_dtype[s];
-    segs.scale[s] = seg_dtype[s] == COR_I8 && seg_scale ? seg_scale[s] : nullptr;
-    if (seg_n[s] > 0) seen |= 1 << seg_dtype[s];
-  }
+  SegRowsSq segs;
+  int seen = 0;
+  if (const int rc = seg_table_fill(t, false, segs, nseg, seen)) return rc;
   if (Bq == 0) return 0;
   const DfParams P = {kin, C, kd, kq, gamma, iters, k, alpha};
-  hipStream_t st = (hipStream_t)stream;
-#define DF_LAUNCH(DT) launch_diffusion<DT>(segs, nseg, scores, idx, Bq, P, out_scores, out_idx, out_pos, st)
-  switch (seen) {
-    case 0:                                                              // no rows at all: every entry is missing
-    case 1 << COR_F32: return DF_LAUNCH(COR_F32);
-    case 1 << COR_BF16: return DF_LAUNCH(COR_BF16);
-    case 1 << COR_F16: return DF_LAUNCH(COR_F16);
-    case 1 << COR_I8: return DF_LAUNCH(COR_I8);
-    default: return DF_LAUNCH(DF_MIXED);
-  }
-#undef DF_LAUNCH
+  return seg_dispatch_dtype(seen, [&](auto dt) {
+    return launch_diffusion<decltype(dt)::value>(segs, nseg, scores, idx, Bq, P, out_scores, out_idx, out_pos, (hipStream_t)stream);
+  });
 }

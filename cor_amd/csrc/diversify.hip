@@ -30,69 +30,37 @@
 //   The loop leaves (uniformly) when no slot holds an entry; the rest of the k outputs get (-inf, -1, -1, -inf).
 // Arithmetic: `#pragma clang fp contract(off)` holds for the whole file, so f is four separately rounded operations and an int8 value's
 // (float)q * scale is never fused into the chain; the chain's explicit fmaf stays an fma.
-#include "ranklist.h"
+#include "segrows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int DV_SEGMAX = COR_DIVERSIFY_SEGMAX;
 constexpr int DV_CMAX = 256;                   // embedding width limit of the searches
 constexpr int DV_NI = 4;                       // most candidates per thread (the direct form interleaves their chains)
-constexpr int DV_MIXED = -1;                   // kernel variant: the dtype is read per candidate
 
 // the staged similarity pass (every table of ONE storage dtype): per wave an LDS image of 64 rows x 128 bytes, rows 144 bytes apart
 constexpr int DV_TILE_ROWB = 128, DV_TILE_STRIDE = 144, DV_TILE_BYTES = 64 * DV_TILE_STRIDE;
 constexpr int DV_WIDE_THREADS = 256;           // up to that many threads a block has one thread per candidate
 
-// the segment table, passed BY VALUE in the kernel argument block (512 B): no device allocation, no copy, nothing to keep alive
-struct DvSegs {
-  const unsigned char* rows[DV_SEGMAX];
-  long long off[DV_SEGMAX];
-  int n[DV_SEGMAX];
-  int dt[DV_SEGMAX];
-  const float* scale[DV_SEGMAX];
-};
-
-__device__ __forceinline__ int dv_esize(int dt) { return dt == COR_F32 ? 4 : dt == COR_I8 ? 1 : 2; }
-
-// one chunk of the chain (8 elements) as stored, w[0 .. 2 ESZ), -> fp32 values: fp32 as stored, bf16 / fp16 widened exactly, int8
-// (float)q * rs (one rounded multiply). DT >= 0: the dtype of every row; DV_MIXED: `dt` decides
-template <int DT> __device__ __forceinline__ void dv_widen8(const unsigned (&w)[8], int dt, float rs, float (&g)[8]) {
-  const int d = DT >= 0 ? DT : dt;
-  if (d == COR_F32) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = __uint_as_float(w[e]);
-  } else if (d == COR_I8) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)(int)(signed char)(w[e >> 2] >> (8 * (e & 3))) * rs;
-  } else if (d == COR_BF16) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { g[2 * e] = __uint_as_float(w[e] << 16); g[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)__builtin_bit_cast(_Float16, (unsigned short)(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xffffu));
-  }
-}
-
-// elements [8 s, 8 s + 8) of a row in global memory, as fp32 values: two 16-byte loads (fp32), one (16-bit) or one 8-byte load (int8);
-// rows are 16-byte aligned and C % 16 == 0. The address travels as an integer and the loads name the GLOBAL address space
-#define DV_GLOBAL __attribute__((address_space(1)))
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// seg_load8 for this file: a table of one dtype takes the shared loader (same code); the mixed kernel keeps its own spelling, one load per
+// element size and then seg_widen8. With seg_load8 as the header has it the kernel compiled to shorter code (1913 against 2132 lines)
+// that measured 31 % slower, 1181 -> 1544 us at kin = 256, k = 50 (profiles/row_tables_ab_shared.jsonl); with the 16-bit load shared by
+// bf16 and fp16, 30 % (profiles/row_tables_ab_common16.jsonl). DESIGN.md has both runs
 template <int DT> __device__ __forceinline__ void dv_load8(u64 row, int dt, float rs, int s, float (&g)[8]) {
-  const int d = DT >= 0 ? DT : dt;
+  if constexpr (DT >= 0) return seg_load8<DT>(row, dt, rs, s, g);
   unsigned w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-  if (d == COR_F32) {
-    const u32x4 x = *(const DV_GLOBAL u32x4*)(row + 32u * s), y = *(const DV_GLOBAL u32x4*)(row + 32u * s + 16u);
+  if (dt == COR_F32) {
+    const u32x4 x = *(const SEG_GLOBAL u32x4*)(row + 32u * s), y = *(const SEG_GLOBAL u32x4*)(row + 32u * s + 16u);
     w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3]; w[4] = y[0]; w[5] = y[1]; w[6] = y[2]; w[7] = y[3];
-  } else if (d == COR_I8) {
-    const u32x2 x = *(const DV_GLOBAL u32x2*)(row + 8u * s);
+  } else if (dt == COR_I8) {
+    const u32x2 x = *(const SEG_GLOBAL u32x2*)(row + 8u * s);
     w[0] = x[0]; w[1] = x[1];
   } else {
-    const u32x4 x = *(const DV_GLOBAL u32x4*)(row + 16u * s);
+    const u32x4 x = *(const SEG_GLOBAL u32x4*)(row + 16u * s);
     w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3];
   }
-  dv_widen8<DT>(w, dt, rs, g);
+  seg_widen8<DT>(w, dt, rs, g);
 }
 
 // does entry a (value fa at position pa) win against entry b? A position < 0 is no entry. Equal values (-0.0 == +0.0): the smaller id,
@@ -108,7 +76,7 @@ __device__ __forceinline__ bool dv_wins(float fa, int pa, float fb, int pb, cons
 }
 
 template <int DT>
-__global__ __launch_bounds__(1024) void diversify_mmr_kernel(const DvSegs segs, int nseg, const float* __restrict__ scores,
+__global__ __launch_bounds__(1024) void diversify_mmr_kernel(const SegRowsSq segs, int nseg, const float* __restrict__ scores,
                                                              const long long* __restrict__ idx, int kin, int C, float lam, float max_sim, int k,
                                                              unsigned* __restrict__ out_scores, long long* __restrict__ out_idx,
                                                              int* __restrict__ out_pos, float* __restrict__ out_value) {
@@ -136,11 +104,8 @@ __global__ __launch_bounds__(1024) void diversify_mmr_kernel(const DvSegs segs, 
       int dt = COR_F32;
       u64 r = 0;
       float sr = 0.f;
-      const bool present = seg_lookup(segs, nseg, ids[pos], [&](int sg, u64 local) {    // the only place a row address is formed
-        dt = segs.dt[sg];
-        r = (u64)segs.rows[sg] + local * (u64)(C * dv_esize(dt));
-        if (dt == COR_I8) sr = segs.scale[sg][local];
-      });
+      // the only place a row address is formed
+      const bool present = seg_lookup(segs, nseg, ids[pos], [&](int sg, u64 local) { seg_row(segs, sg, local, C, dt, r, sr); });
       if (present) {                                               // a missing entry's score is never read
         row[j] = r; rs[j] = sr; s[j] = sc[pos];
         dts |= dt << (8 * j);
@@ -239,7 +204,7 @@ __global__ __launch_bounds__(1024) void diversify_mmr_kernel(const DvSegs segs, 
             const u64 rp = ((u64)(unsigned)__shfl((int)shi, src, 64) << 32) | (unsigned)__shfl((int)slo, src, 64);
             const int off = o + 16 * sub;
             v[i] = u32x4{0u, 0u, 0u, 0u};
-            if (rp != 0 && off < RB) v[i] = *(const DV_GLOBAL u32x4*)(rp + (unsigned)off);   // inside the row: off + 16 <= RB
+            if (rp != 0 && off < RB) v[i] = *(const SEG_GLOBAL u32x4*)(rp + (unsigned)off);   // inside the row: off + 16 <= RB
           }
 #pragma unroll
           for (int i = 0; i < 8; ++i) *(u32x4*)(tile + (8 * i + grp) * DV_TILE_STRIDE + 16 * sub) = v[i];
@@ -262,7 +227,7 @@ __global__ __launch_bounds__(1024) void diversify_mmr_kernel(const DvSegs segs, 
                 }
               }
               float g[8];
-              dv_widen8<DT>(w, DT, rs[j], g);
+              seg_widen8<DT>(w, DT, rs[j], g);
               const int c = o / CB + u;
               const f32x4 q0 = ((const f32x4*)s_wrow)[2 * c], q1 = ((const f32x4*)s_wrow)[2 * c + 1];
 #pragma unroll
@@ -320,7 +285,7 @@ __global__ __launch_bounds__(1024) void diversify_mmr_kernel(const DvSegs segs, 
 }
 
 template <int DT>
-int launch_diversify(const DvSegs& segs, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam, float max_sim,
+int launch_diversify(const SegRowsSq& segs, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam, float max_sim,
                      int k, float* out_scores, long long* out_idx, int* out_pos, float* out_value, hipStream_t st) {
   const int npad = next_pow2(kin);
   const int wide = npad < DV_WIDE_THREADS ? npad : DV_WIDE_THREADS;  // one candidate per thread up to DV_WIDE_THREADS threads
@@ -342,33 +307,16 @@ extern "C" int cor_diversify_mmr(const void* const* seg_rows, const float* const
                                  const int* seg_dtype, int nseg, const float* scores, const long long* idx, int Bq, int kin, int C, float lam,
                                  float max_sim, int k, float* out_scores, long long* out_idx, int* out_pos, float* out_value, void* stream) {
   if (!scores || !idx || !out_scores || !out_idx || Bq < 0 || kin < 1 || k < 1 || nseg < 0 || C < 1) return COR_EINVAL;
-  if (nseg > 0 && (!seg_rows || !seg_offset || !seg_n || !seg_dtype)) return COR_EINVAL;
   if (!(lam >= 0.f && lam <= 1.f) || max_sim != max_sim) return COR_EINVAL;   // (a NaN lam fails both comparisons)
-  if (nseg > DV_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
-  for (int s = 0; s < nseg; ++s)
-    if (seg_entry_bad(seg_n[s], seg_rows[s] && (seg_dtype[s] != COR_I8 || (seg_scale && seg_scale[s])))) return COR_EINVAL;
+  const SegArrays t = {seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, true};
+  if (const int rc = seg_table_check(t)) return rc;
   if (kin > COR_MERGE_NMAX || k > COR_TOPK_KMAX || C > DV_CMAX || C % 16 != 0) return COR_ENOSUPPORT;
-  DvSegs segs = {};
-  int seen = 0;                                                          // bit dt: a non-empty segment of that dtype
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_dtype[s] != COR_F32 && seg_dtype[s] != COR_BF16 && seg_dtype[s] != COR_F16 && seg_dtype[s] != COR_I8) return COR_ENOSUPPORT;
-    segs.rows[s] = (const unsigned char*)seg_rows[s];
-    segs.off[s] = seg_offset[s];
-    segs.n[s] = seg_n[s];
-    segs.dt[s] = seg_dtype[s];
-    segs.scale[s] = seg_dtype[s] == COR_I8 && seg_scale ? seg_scale[s] : nullptr;
-    if (seg_n[s] > 0) seen |= 1 << seg_dtype[s];
-  }
+  SegRowsSq segs;
+  int seen = 0;
+  if (const int rc = seg_table_fill(t, false, segs, nseg, seen)) return rc;
   if (Bq == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-#define DV_LAUNCH(DT) launch_diversify<DT>(segs, nseg, scores, idx, Bq, kin, C, lam, max_sim, k, out_scores, out_idx, out_pos, out_value, st)
-  switch (seen) {
-    case 0:                                                              // no rows at all: every entry is missing
-    case 1 << COR_F32: return DV_LAUNCH(COR_F32);
-    case 1 << COR_BF16: return DV_LAUNCH(COR_BF16);
-    case 1 << COR_F16: return DV_LAUNCH(COR_F16);
-    case 1 << COR_I8: return DV_LAUNCH(COR_I8);
-    default: return DV_LAUNCH(DV_MIXED);
-  }
-#undef DV_LAUNCH
+  return seg_dispatch_dtype(seen, [&](auto dt) {
+    return launch_diversify<decltype(dt)::value>(segs, nseg, scores, idx, Bq, kin, C, lam, max_sim, k, out_scores, out_idx, out_pos, out_value,
+                                                 (hipStream_t)stream);
+  });
 }

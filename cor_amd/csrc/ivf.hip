@@ -45,7 +45,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------------------------- build
 
-__global__ __launch_bounds__(256) void ivf_copy(const KmSegs segs, int nseg, int rowbytes, int K, const int* __restrict__ cell_start,
+__global__ __launch_bounds__(256) void ivf_copy(const SegRowsAssign segs, int nseg, int rowbytes, int K, const int* __restrict__ cell_start,
                                                 const int* __restrict__ mem, unsigned char* __restrict__ out_rows,
                                                 float* __restrict__ out_scale, long long* __restrict__ out_ids) {
   const int lane = threadIdx.x & 63;
@@ -398,17 +398,17 @@ extern "C" int cor_ivf_build(const void* const* seg_rows, const float* const* se
                              const int* seg_dtype, int nseg, const int* const* seg_assign, int C, int K, int dtype, void* out_rows,
                              float* out_scale, long long* out_ids, int* out_cell_start, void* workspace, void* stream) {
   if (!out_rows || !out_ids || !out_cell_start || !workspace || (dtype == COR_I8 && !out_scale)) return COR_EINVAL;
-  KmSegs t;
+  SegRowsAssign t;
   int live = 0, seen = 0;
   long long n = 0;
-  if (const int rc = km_table(seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, seg_assign, true, nullptr, K, C, t, live, n, seen)) return rc;
+  if (const int rc = km_table({seg_rows, seg_scale, seg_offset, seg_n, seg_dtype, nseg, true, seg_assign, true}, K, C, t, live, n, seen)) return rc;
   if (!ivf_dtype_ok(dtype)) return COR_ENOSUPPORT;
   for (int s = 0; s < nseg; ++s)
     if (seg_dtype[s] != dtype) return COR_ENOSUPPORT;                    // rows are copied, never converted
   if (((uintptr_t)out_rows & 15) || ((uintptr_t)workspace & 255)) return COR_EINVAL;
   for (int s = 0; s < live; ++s)
     if ((uintptr_t)t.rows[s] & 15) return COR_EINVAL;
-  const KmSegs segs = km_by_offset(t, live);                             // ascending flat position is ascending global id
+  const SegRowsAssign segs = km_by_offset(t, live);                             // ascending flat position is ascending global id
 
   const IvfBuildLayout L = ivf_build_layout(n, K);
   unsigned char* ws = (unsigned char*)workspace;
@@ -416,7 +416,7 @@ extern "C" int cor_ivf_build(const void* const* seg_rows, const float* const* se
   hipStream_t st = (hipStream_t)stream;
   km_member_lists(segs, live, n, K, (unsigned*)(ws + L.keys), (int*)(ws + L.cnt), (int*)(ws + L.count), out_cell_start, (int*)(ws + L.cb), mem, st);
   if (n > 0) {
-    const int rowbytes = C * (dtype == COR_F32 ? 4 : dtype == COR_I8 ? 1 : 2);
+    const int rowbytes = C * seg_esize(dtype);
     const long long waves = (n + IVF_CPW - 1) / IVF_CPW;
     hipLaunchKernelGGL(ivf_copy, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, segs, live, rowbytes, K, out_cell_start, mem,
                        (unsigned char*)out_rows, dtype == COR_I8 ? out_scale : nullptr, out_ids);

@@ -1,5 +1,7 @@
-// cor_amd — the by-value segment table of the clustering calls and the stable counting sort that turns a per-row cell id into member lists,
-// shared by cluster.hip (cor_kmeans_update: the members of a cluster) and ivf.hip (cor_ivf_build: the rows of a cell). Integer code only.
+// cor_amd — the flat positions of the clustering calls' segment table (segrows.h: SegRowsAssign) and the stable counting sort that turns a
+// per-row cell id into member lists, shared by cluster.hip (cor_kmeans_update: the members of a cluster) and ivf.hip (cor_ivf_build: the
+// rows of a cell). The code of this file is integer code only; segrows.h, included for the table, also holds the floating-point row
+// loaders: forced-inline templates that set their own fp contract pragma and are used only by files that set it for the whole file.
 //
 // Rows. A FLAT position p in [0, n_total) numbers the rows of the table's non-empty segments in the order the launcher hands them to the
 // kernels; with the segments in ASCENDING OFFSET (km_by_offset) ascending p is ascending global id. km_locate turns p into (segment, local
@@ -14,33 +16,19 @@
 //   place   one block per tile: member slot = base[cluster] + the tile's prefix + the key's rank inside its run (binary search for the run's
 //           head). The lists come out ascending by flat position inside every cluster: a stable counting sort.
 #pragma once
-#include "ranklist.h"
+#include "segrows.h"
 
 namespace {
 
-constexpr int KM_SEGMAX = COR_CLUSTER_SEGMAX;
 constexpr int KM_CMAX = 256;                   // 64 lanes x 4 channels
 constexpr int KM_TILE_BITS = 11, KM_TILE = 1 << KM_TILE_BITS;   // rows per tile of the member-list build
 constexpr int KM_CHUNK = 256;                  // members per chunk sum (part of cor_kmeans_update's definition)
 constexpr unsigned KM_NOKEY = 0xffffffffu;
 static_assert(COR_KMEANS_KMAX <= (1 << 14) && COR_KMEANS_KMAX * (1ll << KM_TILE_BITS) < (1ll << 32) - 1, "a key is [cluster | position in the tile] in 32 bits");
 
-// the segment table, passed BY VALUE in the kernel argument block (768 B): no device allocation, no copy, nothing to keep alive
-struct KmSegs {
-  const unsigned char* rows[KM_SEGMAX];
-  long long off[KM_SEGMAX];
-  int n[KM_SEGMAX];
-  int dt[KM_SEGMAX];
-  const float* scale[KM_SEGMAX];
-  const int* assign[KM_SEGMAX];                // cor_kmeans_update and cor_ivf_build only
-  const float* score[KM_SEGMAX];               // ... and NULL without scores
-};
-
-__device__ __forceinline__ int km_esize(int dt) { return dt == COR_F32 ? 4 : dt == COR_I8 ? 1 : 2; }
-
 // flat position -> on_hit(segment, local row) and true, or false: p lies past the table. Every segment is visited (uniform trip count, the
 // table in scalar registers); the callers form their addresses inside on_hit, from a hit alone
-template <typename OnHit> __device__ __forceinline__ bool km_locate(const KmSegs& segs, int nseg, long long p, const OnHit on_hit) {
+template <typename OnHit> __device__ __forceinline__ bool km_locate(const SegRowsAssign& segs, int nseg, long long p, const OnHit on_hit) {
   bool hit = false;
   long long base = 0;
   for (int s = 0; s < nseg; ++s) {
@@ -54,7 +42,7 @@ template <typename OnHit> __device__ __forceinline__ bool km_locate(const KmSegs
   return hit;
 }
 
-__global__ __launch_bounds__(256) void km_tile_keys(const KmSegs segs, int nseg, long long n, int K, unsigned* __restrict__ keys,
+__global__ __launch_bounds__(256) void km_tile_keys(const SegRowsAssign segs, int nseg, long long n, int K, unsigned* __restrict__ keys,
                                                     int* __restrict__ cnt) {
   __shared__ unsigned key[KM_TILE];
   const int tid = threadIdx.x;
@@ -168,45 +156,22 @@ inline int km_shape_check(long long n, int K, int C) {
 }
 
 // the checks of the table the calls share, in the header's order; fills `segs` with the NON-EMPTY segments in table order
-inline int km_table(const void* const* seg_rows, const float* const* seg_scale, const long long* seg_offset, const int* seg_n, const int* seg_dtype,
-                    int nseg, const int* const* seg_assign, bool need_assign, const float* const* seg_score, int K, int C, KmSegs& segs, int& live,
-                    long long& n_total, int& seen) {
-  if (nseg < 0 || K < 1 || C < 1) return COR_EINVAL;
-  if (nseg > 0 && (!seg_rows || !seg_offset || !seg_n || !seg_dtype || (need_assign && !seg_assign))) return COR_EINVAL;
-  if (nseg > KM_SEGMAX) return COR_ENOSUPPORT;                           // (before the arrays are read: they hold nseg entries)
-  for (int s = 0; s < nseg; ++s)
-    if (seg_entry_bad(seg_n[s], seg_rows[s] && (seg_dtype[s] != COR_I8 || (seg_scale && seg_scale[s])) && (!need_assign || seg_assign[s]) &&
-                                    (!seg_score || seg_score[s])))
-      return COR_EINVAL;
+inline int km_table(const SegArrays& t, int K, int C, SegRowsAssign& segs, int& live, long long& n_total, int& seen) {
+  if (t.nseg < 0 || K < 1 || C < 1) return COR_EINVAL;
+  if (const int rc = seg_table_check(t)) return rc;
   n_total = 0;
-  for (int s = 0; s < nseg; ++s) n_total += seg_n[s];
+  for (int s = 0; s < t.nseg; ++s) n_total += t.n[s];
   if (const int rc = km_shape_check(n_total, K, C)) return rc;
-  segs = KmSegs{};
-  live = 0;
-  seen = 0;
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_dtype[s] != COR_F32 && seg_dtype[s] != COR_BF16 && seg_dtype[s] != COR_F16 && seg_dtype[s] != COR_I8) return COR_ENOSUPPORT;
-    if (seg_n[s] == 0) continue;
-    segs.rows[live] = (const unsigned char*)seg_rows[s];
-    segs.off[live] = seg_offset[s];
-    segs.n[live] = seg_n[s];
-    segs.dt[live] = seg_dtype[s];
-    segs.scale[live] = seg_dtype[s] == COR_I8 ? seg_scale[s] : nullptr;
-    segs.assign[live] = need_assign ? seg_assign[s] : nullptr;
-    segs.score[live] = seg_score ? seg_score[s] : nullptr;
-    seen |= 1 << seg_dtype[s];
-    ++live;
-  }
-  return 0;
+  return seg_table_fill(t, true, segs, live, seen);
 }
 
 // the table in ascending offset: ascending flat position is ascending global id (the ranges are disjoint)
-inline KmSegs km_by_offset(const KmSegs& t, int live) {
-  int order[KM_SEGMAX];
+inline SegRowsAssign km_by_offset(const SegRowsAssign& t, int live) {
+  int order[SEG_MAX];
   for (int s = 0; s < live; ++s) order[s] = s;
   for (int a = 1; a < live; ++a)
     for (int b = a; b > 0 && t.off[order[b]] < t.off[order[b - 1]]; --b) { const int x = order[b]; order[b] = order[b - 1]; order[b - 1] = x; }
-  KmSegs segs = {};
+  SegRowsAssign segs = {};
   for (int s = 0; s < live; ++s) {
     const int o = order[s];
     segs.rows[s] = t.rows[o]; segs.off[s] = t.off[o]; segs.n[s] = t.n[o]; segs.dt[s] = t.dt[o]; segs.scale[s] = t.scale[o];
@@ -216,7 +181,7 @@ inline KmSegs km_by_offset(const KmSegs& t, int live) {
 }
 
 // the four launches: keys / cnt / mem are workspace (tiles * KM_TILE keys, tiles * K counts, n positions), count [K], base and cb [K + 1]
-inline void km_member_lists(const KmSegs& segs, int live, long long n, int K, unsigned* keys, int* cnt, int* count, int* base, int* cb, int* mem,
+inline void km_member_lists(const SegRowsAssign& segs, int live, long long n, int K, unsigned* keys, int* cnt, int* count, int* base, int* cb, int* mem,
                             hipStream_t st) {
   const int tiles = (int)((n + KM_TILE - 1) / KM_TILE);
   if (tiles > 0) hipLaunchKernelGGL(km_tile_keys, dim3(tiles), dim3(256), 0, st, segs, live, n, K, keys, cnt);

@@ -1,6 +1,7 @@
-// cor_amd — the device steps the one-block-per-query list kernels share (merge.hip, rescore.hip, rescore_i8.hip, rerank.hip) and the id -> segment lookup
-// (expand.hip, rerank.hip, diversify.hip). Integer code only: the files that include this keep their own floating-point rules. Not for retrieval.hip,
-// whose block_sort_u64 / rank_key use another key layout.
+// cor_amd — the device steps the one-block-per-query list kernels share (merge.hip, rescore.hip, rescore_i8.hip, rerank.hip, diffuse.hip, fuse.hip;
+// the bitonic sort also member_sort.h and ivf.hip) and the id -> segment lookup (rerank.hip, and through segrows.h, which holds the tables of
+// gallery rows and their loaders, expand.hip, diversify.hip and diffuse.hip). Integer code only: the files that include this keep their own
+// floating-point rules. Not for retrieval.hip, whose block_sort_u64 / rank_key use another key layout.
 //
 // Rank keys. An entry of a list of n <= COR_MERGE_NMAX = 4096 becomes a 64-bit key in LDS,
 //     [score key: 32 bits | 0: 19 bits | -0.0 flag: bit 12 | position in the list: 12 bits],

@@ -895,11 +895,7 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
     definition to the bit), so the result does not depend on how the rows are cut into segments. An id of no segment (-1, another
     shard's, any 64-bit value) contributes nothing and its score is not read. 1 <= m <= min(kin, 256), 0 <= alpha <= 8, C <= 256 and
     C % 16 == 0. out: an optional contiguous [Bq,C] tensor of out_dtype to write into. No host synchronisation; capturable in a graph."""
-    segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
-    if any(len(seg) not in (2, 3) for seg in segments):
-        raise ValueError("expand_queries: a segment is (rows, offset) or (rows_i8, scales, offset)")
-    if len(segments) > nat.EXPAND_SEGMAX:
-        raise ValueError(f"expand_queries: {len(segments)} segments, one call reads at most {nat.EXPAND_SEGMAX}")
+    segments = _row_segments("expand_queries", segments, nat.EXPAND_SEGMAX)
     Bq, kin = _list_front("expand_queries", scores, idx)
     if not 1 <= int(m) <= min(kin, nat.TOPK_KMAX):
         raise ValueError(f"expand_queries: m must be in [1, min(kin, {nat.TOPK_KMAX})] (kin = {kin}), got {m}")
@@ -917,15 +913,7 @@ def expand_queries(Q, segments, scores, idx, m, alpha=3, query_weight=1.0, norma
         raise ValueError(f"expand_queries: the width must be a multiple of 16 up to 256, got {C}")
     if out_dtype not in _DT:
         raise ValueError(f"expand_queries: out_dtype must be float32 / bfloat16 / float16, got {out_dtype}")
-    for seg in segments:
-        r = seg[0]
-        if len(seg) == 3:
-            if r.dim() != 2 or r.shape[1] != C or r.dtype != torch.int8 or r.shape[0] >= 2 ** 31:
-                raise ValueError(f"expand_queries: a segment with scales must be int8 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
-            if seg[1].dtype != torch.float32 or seg[1].dim() != 1 or seg[1].shape[0] != r.shape[0]:
-                raise ValueError(f"expand_queries: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
-        elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
-            raise ValueError(f"expand_queries: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+    _row_segment_tensors("expand_queries", segments, C)
     _disjoint_spans("expand_queries", segments)
     if out is not None and (out.shape != (Bq, C) or out.dtype != out_dtype or not out.is_contiguous()):
         raise ValueError(f"expand_queries: out must be a contiguous {out_dtype} [{Bq}, {C}] tensor")
@@ -1032,7 +1020,7 @@ def rerank_reciprocal(scores, idx, segments, k1, lam, k, return_pos=False):
 
 
 def _row_segments(who, segments, segmax):
-    """The gallery-row segments of diversify_mmr / rerank_diffusion, offsets as ints: each (rows, offset) or (rows_i8, scales, offset), at most segmax."""
+    """The gallery-row segments of a call that reads rows through a segment table, offsets as ints: each (rows, offset) or (rows_i8, scales, offset), at most segmax."""
     segments = [tuple(seg[:-1]) + (int(seg[-1]),) for seg in segments]
     if any(len(seg) not in (2, 3) for seg in segments):
         raise ValueError(f"{who}: a segment is (rows, offset) or (rows_i8, scales, offset)")
@@ -1041,11 +1029,8 @@ def _row_segments(who, segments, segmax):
     return segments
 
 
-def _row_segments_width(who, segments):
-    """The checks of such segments' tensors (one width C, a multiple of 16 up to 256; dtypes; scales; disjoint id ranges) -> C."""
-    C = segments[0][0].shape[-1] if segments and segments[0][0].dim() == 2 else 16    # (no segment: every entry is missing, any width will do)
-    if C < 16 or C > 256 or C % 16 != 0:
-        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
+def _row_segment_tensors(who, segments, C):
+    """The checks of each such segment's tensors: rows [n < 2^31, C] of a storage dtype, or int8 rows with float32 [n] scales."""
     for seg in segments:
         r = seg[0]
         if len(seg) == 3:
@@ -1055,6 +1040,14 @@ def _row_segments_width(who, segments):
                 raise ValueError(f"{who}: scales must be float32 [{r.shape[0]}], got {seg[1].dtype} {tuple(seg[1].shape)}")
         elif r.dim() != 2 or r.shape[1] != C or r.dtype not in _DT or r.shape[0] >= 2 ** 31:
             raise ValueError(f"{who}: a segment must be float32 / bfloat16 / float16 [n < 2^31, {C}], got {r.dtype} {tuple(r.shape)}")
+
+
+def _row_segments_width(who, segments):
+    """The checks of such segments' tensors (one width C, a multiple of 16 up to 256; dtypes; scales; disjoint id ranges) -> C."""
+    C = segments[0][0].shape[-1] if segments and segments[0][0].dim() == 2 else 16    # (no segment: every entry is missing, any width will do)
+    if C < 16 or C > 256 or C % 16 != 0:
+        raise ValueError(f"{who}: the width must be a multiple of 16 up to 256, got {C}")
+    _row_segment_tensors(who, segments, C)
     _disjoint_spans(who, segments)
     return C
 

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Same-process A/B between ANOTHER build of the library (the parent commit's libcor_amd.so) and this one, for changes that must leave
-results and speed as they are. Two case tables: `topk`, the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct, and the
-same three over an int8 gallery, quantised once and shared by both builds), and `lists`, the list kernels (cor_merge_topk, cor_rescore_topk,
-cor_rescore_topk_i8, cor_rerank_reciprocal, cor_knn_reciprocal, cor_expand_queries) at the shapes of their own bench tools.
+results and speed as they are. Three case tables: `topk`, the wide top-k family (similarity_topk at k > 32, _filtered `ne`, _distinct, and the
+same three over an int8 gallery, quantised once and shared by both builds), `lists`, the list kernels (cor_merge_topk, cor_rescore_topk,
+cor_rescore_topk_i8, cor_rerank_reciprocal, cor_knn_reciprocal, cor_expand_queries) at the shapes of their own bench tools, and `rows`, the
+calls that read gallery rows through a segment table (cor_diversify_mmr, cor_rerank_diffusion, cor_kmeans_seed, cor_kmeans_update,
+cor_expand_queries_sq, cor_ivf_build) at their bench tools' shapes scaled to seconds, each over a table of one storage dtype (bf16) and over
+an fp32 + bf16 + int8 table (cor_ivf_build, which copies rows and takes one dtype only: int8 instead), and the lane-loader calls also over
+fp32, fp32 + bf16 (cor_expand_queries) and int8 tables, so that every instantiation of their kernels is launched.
     python tools/topk_family_ab.py PARENT_LIB.so [ROUNDS=5] [OUT=profiles/topk_family_ab.jsonl] [TABLE=topk]
 "This one" is the library cor_amd loads (COR_AMD_LIB selects another build of it).
 Both sides are called through ctypes with preallocated outputs and workspace, so they carry the same host work. Per case: the results of
@@ -164,6 +168,72 @@ def list_caller(lib, kernel, d, Bq, kin, k, variant):
     return _enqueue(lib.cor_rerank_reciprocal, args, (outs, tabs)), outs
 
 
+ROWS_N, ROWS_C = 3 * 32768, 256                              # three segments of 32768 rows
+
+
+def rows_data(table):
+    """the inputs of the `rows` cases, shared by both builds: the gallery as three segments (`bf16`: all bf16; `f32`: all fp32; `i8`: all int8
+    with their scales; `f32bf16`: fp32, bf16, fp32; `mixed`: fp32, bf16, int8), lists whose ids walk 2^17 ids (a quarter of the entries names
+    no row), a cell id and a score per row"""
+    n = ROWS_N // 3
+    G = torch.nn.functional.normalize(_rand((ROWS_N, ROWS_C), 11) - 0.5, dim=-1)
+    kinds = dict(bf16=("bf16",) * 3, f32=("f32",) * 3, i8=("i8",) * 3, f32bf16=("f32", "bf16", "f32"), mixed=("f32", "bf16", "i8"))[table]
+    segs = []                                                # (rows, scales or None, dtype code)
+    for s, kind in enumerate(kinds):
+        part = G[s * n:(s + 1) * n]
+        if kind == "i8":
+            segs.append((*quantized(part.contiguous()), nat.I8))
+        else:
+            segs.append((part.to(torch.bfloat16 if kind == "bf16" else torch.float32).contiguous(), None, nat.BF16 if kind == "bf16" else nat.F32))
+    g = torch.Generator(device=dev).manual_seed(12)
+    return dict(segs=segs, Q=torch.nn.functional.normalize(_rand((512, ROWS_C), 3) - 0.5, dim=-1),
+                scores=torch.sort(_rand((512, 256), 256), dim=1, descending=True).values.contiguous(), idx=_ids(512, 256, 131072, 257),
+                assign=torch.randint(0, 256, (ROWS_N,), device=dev, generator=g).to(torch.int32), score=_rand((ROWS_N,), 13))
+
+
+def rows_caller(lib, call, d):
+    """(fn, outputs): fn() enqueues one call over the segment table on the current stream"""
+    segs, n, nseg, Cc = d["segs"], ROWS_N // 3, 3, ROWS_C
+    arr = lambda ptrs: (C.c_void_p * nseg)(*ptrs)
+    tabs = (arr([r.data_ptr() for r, _, _ in segs]), arr([s.data_ptr() if s is not None else None for _, s, _ in segs]),
+            (C.c_longlong * nseg)(*[i * n for i in range(nseg)]), (C.c_int * nseg)(*[n] * nseg), (C.c_int * nseg)(*[dt for _, _, dt in segs]))
+    Bq, kin = d["scores"].shape
+    lists = (d["scores"].data_ptr(), d["idx"].data_ptr(), Bq, kin)
+    if call == "diversify":                                  # tools/diversify_bench.py: kin = 256, k = 50
+        outs = _outputs(Bq, 50, True) + [torch.empty((Bq, 50), device=dev)]
+        args = (*tabs, nseg, *lists, Cc, 0.5, 0.95, 50, *[o.data_ptr() for o in outs])
+        return _enqueue(lib.cor_diversify_mmr, args, (outs, tabs)), outs
+    if call == "diffusion":                                  # tools/diffuse_bench.py: kin = 256, kd = 8, kq = k = kin
+        outs = _outputs(Bq, kin, True)
+        args = (*tabs, nseg, *lists, Cc, 8, kin, 3, 0.9, 20, kin, *[o.data_ptr() for o in outs])
+        return _enqueue(lib.cor_rerank_diffusion, args, (outs, tabs)), outs
+    if call == "expand_sq":                                  # tools/expand_bench.py: m = 100
+        outs = [torch.empty((Bq, Cc), device=dev)]
+        args = (d["Q"].data_ptr(), 1.0, *tabs, nseg, d["scores"].data_ptr(), d["idx"].data_ptr(), Bq, kin, 100, Cc, 3, 1, outs[0].data_ptr(), nat.F32)
+        return _enqueue(lib.cor_expand_queries_sq, args, (outs, tabs)), outs
+    if call == "expand":                                     # the call without scales: fp32 / 16-bit tables only
+        outs = [torch.empty((Bq, Cc), device=dev)]
+        args = (d["Q"].data_ptr(), 1.0, tabs[0], *tabs[2:], nseg, d["scores"].data_ptr(), d["idx"].data_ptr(), Bq, kin, 100, Cc, 3, 1, outs[0].data_ptr(), nat.F32)
+        return _enqueue(lib.cor_expand_queries, args, (outs, tabs)), outs
+    K = 8 if call == "kmeans_seed" else 256                  # the seeding is 2 K launches
+    assign = arr([d["assign"][i * n:(i + 1) * n].data_ptr() for i in range(nseg)])
+    if call == "ivf_build":
+        dt = segs[0][2]
+        ws = torch.empty((lib.cor_ivf_build_workspace_bytes(ROWS_N, K, Cc),), dtype=torch.uint8, device=dev)
+        outs = [torch.empty((ROWS_N, Cc * (1 if dt == nat.I8 else 2)), dtype=torch.uint8, device=dev), torch.zeros((ROWS_N,), device=dev),
+                torch.empty((ROWS_N,), dtype=torch.int64, device=dev), torch.empty((K + 1,), dtype=torch.int32, device=dev)]
+        args = (*tabs, nseg, assign, Cc, K, dt, *[o.data_ptr() for o in outs], ws.data_ptr())
+        return _enqueue(lib.cor_ivf_build, args, (outs, tabs, assign, ws)), outs
+    ws = torch.empty((lib.cor_kmeans_workspace_bytes(ROWS_N, K, Cc),), dtype=torch.uint8, device=dev)
+    if call == "kmeans_seed":
+        outs = [torch.empty((K,), dtype=torch.int64, device=dev), torch.empty((K, Cc), device=dev)]
+        return _enqueue(lib.cor_kmeans_seed, (*tabs, nseg, Cc, K, 5, outs[0].data_ptr(), outs[1].data_ptr(), ws.data_ptr()), (outs, tabs, ws)), outs
+    score = arr([d["score"][i * n:(i + 1) * n].data_ptr() for i in range(nseg)])
+    outs = [torch.empty((K, Cc), device=dev), torch.empty((K,), dtype=torch.int32, device=dev), torch.empty((K,), device=dev)]
+    args = (*tabs, nseg, assign, score, Cc, K, None, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), ws.data_ptr())
+    return _enqueue(lib.cor_kmeans_update, args, (outs, tabs, assign, score, ws)), outs
+
+
 def ab(desc, fp, outs_p, fn, outs_n):
     """one case: bitwise-equal outputs, then the alternating rounds and the yardstick"""
     for f in (fp, fn, fp, fn, fp, fn):                       # warm-up, and the results to compare
@@ -193,7 +263,19 @@ LIST_CASES = ([("merge", 512, kin, kin, None, v) for kin in (100, 256) for v in 
               + [("rescore", 512, kin, 10, dt, v) for kin in (256, 4096) for dt in (torch.float32, torch.bfloat16) for v in (("", "i8") if dt == torch.float32 else ("",))]
               + [("rerank", 512, kin, 10, None, "") for kin in (256, 1024)] + [("knn", 0, 20, 20, None, "")]
               + [("expand", 512, 256, m, torch.bfloat16, "") for m in (10, 256)])
+# (call, table); the tables beyond bf16 and mixed reach the other instantiations of the lane-loader kernels: fp32 alone (ESZ = 4), fp32 and
+# 16-bit (ESZ = 0), int8 alone (ESZ = 1)
+ROWS_CASES = ([(call, table) for call in ("diversify", "diffusion", "kmeans_seed", "kmeans_update", "expand_sq") for table in ("bf16", "mixed")]
+              + [("ivf_build", "bf16"), ("ivf_build", "i8"), ("expand", "f32"), ("expand", "f32bf16"), ("expand_sq", "i8"), ("kmeans_update", "i8")])
+ROWS_SHAPE = dict(diversify=dict(Bq=512, kin=256, k=50), diffusion=dict(Bq=512, kin=256, k=256), expand=dict(Bq=512, kin=256, m=100),
+                  expand_sq=dict(Bq=512, kin=256, m=100), kmeans_seed=dict(K=8), kmeans_update=dict(K=256), ivf_build=dict(K=256))
 rows, data = [], None
+for call, table in sorted(ROWS_CASES, key=lambda c: c[1]) if TABLE == "rows" else []:
+    if data is None or data[0] != table:
+        data = (table, rows_data(table))
+    fp, outs_p = rows_caller(parent, call, data[1])
+    fn, outs_n = rows_caller(new, call, data[1])
+    rows.append(ab(dict(route=call, table=table, rows=ROWS_N, C=ROWS_C, **ROWS_SHAPE[call]), fp, outs_p, fn, outs_n))
 for route, Bq, Ng, k, Cc, dt in CASES if TABLE == "topk" else []:
     if data is None or data[0] != (Bq, Ng, Cc, dt):
         data, G8 = ((Bq, Ng, Cc, dt), gallery(Bq, Ng, Cc, dt)), None
@@ -215,4 +297,4 @@ with open(OUT, "w") as f:
     for r in rows:
         f.write(json.dumps(r) + "\n")
 bad = [r for r in rows if not r["within_margin"]]
-assert not bad, f"slower than the parent beyond its own spread: {[(r['route'], r['Bq'], r.get('Ng', r.get('kin')), r['k']) for r in bad]}"
+assert not bad, f"slower than the parent beyond its own spread: {[(r['route'], r.get('table', r.get('Bq')), r.get('Ng', r.get('kin', r.get('K'))), r.get('k')) for r in bad]}"
