@@ -145,41 +145,59 @@ def layernorm(x, w, b, eps, out_dtype=None, act=ACT_NONE, out=None, reverse=Fals
     return out
 
 
-def attention(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=None):
-    """q [B*Tq, >=H*hd] / k,v [B*Tk, ...] row-major 2-D views (e.g. column slices of a fused qkv activation)."""
-    _dev(q, k, v)
+def _attn_out(out, rows, cols, dtype, device, strided):
+    """The output of an attention call: a fresh [rows, cols] tensor, or the caller's `out` held to the same shape and dtype. strided:
+    the entry point takes a row stride (any stride(0) >= cols); otherwise `out` must be contiguous like the allocation it replaces."""
+    if out is None:
+        return torch.empty((rows, cols), dtype=dtype, device=device)
+    assert out.is_cuda and out.device == device and out.dtype == dtype and out.dim() == 2 and tuple(out.shape) == (rows, cols), \
+        (out.shape, out.dtype, out.device, rows, cols, dtype)
+    if strided:
+        assert out.stride(1) == 1 and (rows == 1 or out.stride(0) >= cols), out.stride()
+    else:
+        assert out.is_contiguous(), out.stride()
+    return out
+
+
+def attention(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=None, out=None):
+    """q [B*Tq, >=H*hd] / k,v [B*Tk, ...] row-major 2-D views (e.g. column slices of a fused qkv activation).
+    out: optional [B*Tq, H*hd] row-major view to write into (its row stride is passed on), of dtype out_dtype (default: q's)."""
+    _dev(q, k, v, out)
     assert q.dtype == k.dtype == v.dtype
     for t, T in ((q, Tq), (k, Tk), (v, Tk)):
         assert t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * T and t.shape[1] == H * hd, (t.shape, B, T, H, hd)
-    out = torch.empty((B * Tq, H * hd), dtype=out_dtype or q.dtype, device=q.device)
+    out = _attn_out(out, B * Tq, H * hd, out_dtype or q.dtype, q.device, True)
+    ld = out.stride(0) if B * Tq > 1 else max(out.stride(0), H * hd)
     nat.check(_lib().cor_attention(q.data_ptr(), Tq * q.stride(0), q.stride(0), k.data_ptr(), Tk * k.stride(0), k.stride(0),
-                                   v.data_ptr(), Tk * v.stride(0), v.stride(0), _dt(q), out.data_ptr(), Tq * H * hd, H * hd,
+                                   v.data_ptr(), Tk * v.stride(0), v.stride(0), _dt(q), out.data_ptr(), Tq * ld, ld,
                                    _dt(out), B, H, Tq, Tk, hd, float(scale), _s()), "cor_attention")
     return out
 
 
-def attention_f32(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=torch.float32):
+def attention_f32(q, k, v, B, H, Tq, Tk, hd, scale, out_dtype=torch.float32, out=None):
     """flash_fwd_f32 (cor_attention_f32): exact-fp32 MHA on the f32 matrix cores. q [B*Tq, >=H*hd] / k,v [B*Tk, ...] fp32 row-major 2-D
-    views (e.g. column slices of an fp32 qkv activation) -> fp32 [B*Tq, H*hd] or, out_dtype X3, split rows [B*Tq, 3*H*hd]."""
-    _dev(q, k, v)
+    views (e.g. column slices of an fp32 qkv activation) -> fp32 [B*Tq, H*hd] or, out_dtype X3, split rows [B*Tq, 3*H*hd].
+    out: optional row-major view of that shape and type to write into (its row stride is passed on)."""
+    _dev(q, k, v, out)
     for t, T in ((q, Tq), (k, Tk), (v, Tk)):
         assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * T and t.shape[1] == H * hd, (t.shape, B, T, H, hd)
     if out_dtype == X3:
-        out = torch.empty((B * Tq, 3 * H * hd), dtype=torch.bfloat16, device=q.device)
+        out = _attn_out(out, B * Tq, 3 * H * hd, torch.bfloat16, q.device, True)
         o_dt = nat.BF16X3
     else:
         assert out_dtype == torch.float32
-        out = torch.empty((B * Tq, H * hd), dtype=torch.float32, device=q.device)
+        out = _attn_out(out, B * Tq, H * hd, torch.float32, q.device, True)
         o_dt = F32
-    ld = out.shape[1]
+    ld = out.stride(0) if B * Tq > 1 else max(out.stride(0), out.shape[1])
     nat.check(_lib().cor_attention_f32(q.data_ptr(), Tq * q.stride(0), q.stride(0), k.data_ptr(), Tk * k.stride(0), k.stride(0),
                                        v.data_ptr(), Tk * v.stride(0), v.stride(0), out.data_ptr(), Tq * ld, ld, o_dt,
                                        B, H, Tq, Tk, hd, float(scale), _s()), "cor_attention_f32")
     return out
 
 
-def sam_attention(qkv, pad_row, rel_h, rel_w, B, H, grid, window, out_dtype=None, variant=0, q_prescale=1.0, reverse=False):
-    _dev(qkv, pad_row, rel_h, rel_w)
+def sam_attention(qkv, pad_row, rel_h, rel_w, B, H, grid, window, out_dtype=None, variant=0, q_prescale=1.0, reverse=False, out=None):
+    """out: optional contiguous [B*grid*grid, H*hd] tensor to write into, of dtype out_dtype (default: qkv's)."""
+    _dev(qkv, pad_row, rel_h, rel_w, out)
     hd = rel_h.shape[1]
     d = H * hd
     assert qkv.is_contiguous() and qkv.shape == (B * grid * grid, 3 * d), qkv.shape
@@ -188,7 +206,7 @@ def sam_attention(qkv, pad_row, rel_h, rel_w, B, H, grid, window, out_dtype=None
         assert r.dtype == torch.float32 and r.is_contiguous() and r.shape == (2 * S - 1, hd), r.shape
     if window > 0:
         assert pad_row is not None and pad_row.dtype == qkv.dtype and pad_row.is_contiguous() and pad_row.numel() == 3 * d
-    out = torch.empty((B * grid * grid, d), dtype=out_dtype or qkv.dtype, device=qkv.device)
+    out = _attn_out(out, B * grid * grid, d, out_dtype or qkv.dtype, qkv.device, False)
     nat.check(_lib().cor_sam_attention(qkv.data_ptr(), _dt(qkv), out.data_ptr(), _dt(out), _p(pad_row), rel_h.data_ptr(),
                                        rel_w.data_ptr(), B, H, hd, grid, window, float(q_prescale), int(variant) | (nat.ORDER_REVERSE if reverse else 0), _s()), "cor_sam_attention")
     return out
